@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: tiles/s (640x640) forward + backward + optimizer step of the metayolo detector on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic tiles already resident in HBM: HIP-plan forward of
@@ -9,21 +9,28 @@ backbone + neck + detection convs (bf16 operands, fp32 accumulate), target assig
 backward, wgrad, dgrad), the RCCL gradient all-reduce when N > 1, and the SGD(Nesterov) update.  Workload = BASELINE.json
 configs[1]: yolov5s, 8 classes, batch 64 per GPU, 640x640 (weak scaling: per-GPU batch fixed).  One JSON line on rank 0.
 
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the line: `value` (tiles/s) and `ms_per_step` are that block.
+--dump-outputs DIR  after the timed block, what its last step handed the caller, as DIR/<name>.npy (float32): the loss terms (`loss.*`), every
+                    parameter after the optimizer step (`param.*`, fp32 masters) and the floating BatchNorm buffers (`buffer.*`); above 64 MB a
+                    fixed, seeded sample of each tensor.  The inputs are seeded: the same arguments give the same inputs on every run.
+--full              also the side measurements below that take runs of their own: `steady_state`, `roofline`, `roofline_hbm`, `infer`,
+                    `cpu_baseline` (each still switched off by its --no-* flag).  Without it they are absent or None.
+
 Extra objects on the line:
-  roofline      the kernel on the layer the north star names — the fused 3x3 conv 64->64 at 80x80, batch 64 (filter-resident
+  roofline      (--full) the kernel on the layer the north star names — the fused 3x3 conv 64->64 at 80x80, batch 64 (filter-resident
                 conv3x3_c64) — timed live with HIP events on the launch stream; achieved = 2*N*K*C*9*Ho*Wo / t.  Its `layers_3x3`
                 lists EVERY 3x3 convolution launch of the benchmarked model (forward and data gradient) timed alone, `min_frac` is the
                 worst of them: the named kernel is 2 % of the step, the others are where the time goes.  Each row also names the
                 roofline that bounds THAT layer (`bound`: max(FLOPs / 2.5 PFLOP/s, read-once/write-once bytes / 8 TB/s)) and its
                 `frac_of_bound`: the stride-2 layers at 320x320 / 160x160 are HBM-bound (0.24 of the MFMA peak AT the HBM roofline).
-  roofline_hbm  the step's dominant HBM-bound kernel (BatchNorm backward over the largest activation) timed alone, bytes / time vs 8 TB/s;
+  roofline_hbm  (--full) the step's dominant HBM-bound kernel (BatchNorm backward over the largest activation) timed alone, bytes / time vs 8 TB/s;
                 `all_launches`: the same over every BatchNorm-backward call of the plan (the kernel family with the most time in the step).
   step          whole-step fractions: conv FLOPs of the step / time / 2.5 PFLOP/s and read-once/write-once bytes of its conv and
                 BatchNorm launches / time / 8 TB/s.
-  infer         BASELINE configs[3] (yolov5l, batch 128, 1024x1024 inference): tiles/s, decode and NMS microseconds per tile.
-  cpu_baseline  the CPU oracle (oracle/ref_net.py, a torch-fp32 port of the reference path) doing the same training step on
+  infer         (--full) BASELINE configs[3] (yolov5l, batch 128, 1024x1024 inference): tiles/s, decode and NMS microseconds per tile.
+  cpu_baseline  (--full) the CPU oracle (oracle/ref_net.py, a torch-fp32 port of the reference path) doing the same training step on
                 a bounded sample (a few 640x640 tiles) on this host's cores.
-  steady_state  a SECOND block of K timed steps right after the headline block (same fences): what the step costs once clocks and caches are warm.
+  steady_state  (--full) a SECOND block of K timed steps right after the headline block (same fences): what the step costs once clocks and caches are warm.
                 `value` / `ms_per_step` are always the first block — W warm-up steps, then exactly K timed steps, no pre-warm (HDY_BENCH_PREWARM_S opts in).
   config        also carries the self-diagnosis of an N > 1 run: allreduce_exposed_ms (main stream waiting for the collectives in front of the
                 optimizer), rank_step_ms_min / max, hw_queues / hw_queues_in_time, allreduce_expected against allreduce_calls_per_step / _mb_per_step.
@@ -188,6 +195,41 @@ def reference_c1():
         return None
 
 
+DUMP_BUDGET_BYTES = 63 * 2**20          # --dump-outputs: the arrays' bytes; the rest of the 64 MB is left to the .npy headers
+
+
+def dump_outputs(out_dir, losses, model):
+    """--dump-outputs: what the last timed step handed its caller, one float32 DIR/<name>.npy per tensor — the loss terms (`loss.*`), every
+    parameter the optimizer step just wrote (`param.*`) and the floating BatchNorm buffers the forward updated (`buffer.*`).  Above the
+    budget every tensor keeps the same fraction of its elements, at indices drawn from a generator seeded by its name: the same sample on
+    every run."""
+    import zlib
+    import numpy as np
+    arrays = {}
+
+    def add(prefix, d):
+        for k, v in d.items():
+            if isinstance(v, dict):
+                add(f'{prefix}{k}.', v)
+            elif torch.is_tensor(v):
+                arrays[prefix + k] = v
+    add('loss.', losses)
+    for k, p in model.named_parameters():
+        arrays['param.' + k] = p
+    for k, b in model.named_buffers():
+        if b.is_floating_point():
+            arrays['buffer.' + k] = b
+    frac = min(1.0, DUMP_BUDGET_BYTES / (4 * sum(t.numel() for t in arrays.values())))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        keep = max(1, int(a.size * frac))
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return len(arrays), frac
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -201,6 +243,8 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-infer', action='store_true', help='skip the C4 inference measurement (yolov5l, batch 128, 1024x1024)')
+    ap.add_argument('--full', action='store_true', help='also the side measurements: steady_state, roofline, roofline_hbm, infer, cpu_baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB)')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -277,7 +321,7 @@ def main():
         loss.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
-        return loss
+        return losses
 
     def fence():
         if world > 1 or force_dist:
@@ -288,8 +332,8 @@ def main():
     # driver's `--warmup W` measurement: with lr = 0 the SGD kernel still integrates the momentum buffers and BatchNorm's running statistics
     # move).  When asked for, the untimed steps run with the schedule held at iteration 0 and the optimizer's momentum buffers and the BatchNorm
     # running statistics are put back afterwards, so the counted warm-up starts from the state it would have had; `prewarm_steps` says how many
-    # ran.  The default line is W warm-up steps, then EXACTLY K timed steps (`value`), then a SECOND block of K timed steps reported beside it as
-    # `steady_state` (same fences; by then the clocks and caches are warm) — both numbers, never only the better one.
+    # ran.  The line is W warm-up steps, then EXACTLY K timed steps (`value`); with --full a SECOND block of K timed steps follows, reported beside
+    # it as `steady_state` (same fences; by then the clocks and caches are warm) — both numbers, never only the better one.
     prewarm_target = float(os.environ.get('HDY_BENCH_PREWARM_S', '0'))
     prewarm_s, prewarm_steps = 0.0, 0
     if prewarm_target > 0:
@@ -339,9 +383,10 @@ def main():
         net.reducer.exposed_events = []             # two events around the main stream's wait for the communication stream, every step from here on
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        losses = step()
     fence()
     dt = time.perf_counter() - t0
+    loss = losses['det']['det_loss']
     dt_min = dt
     if dp_on:
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -359,9 +404,14 @@ def main():
         tex = torch.tensor([mine], device=device, dtype=torch.float64)
         dist.all_reduce(tex, op=dist.ReduceOp.MAX)
         exposed_ms = tex.item()
-    # second block of K steps, same fences: the steady-state number beside the headline (never instead of it).  HDY_BENCH_SECOND_BLOCK=0 (the
-    # profiling scripts, which count kernels per step over warm-up + K steps) skips it.
-    second = os.environ.get('HDY_BENCH_SECOND_BLOCK', '1') != '0'
+    # before anything else runs on the model: the state the headline block's last step left
+    if args.dump_outputs and rank == 0:
+        n_dumped, dump_frac = dump_outputs(args.dump_outputs, losses, model)
+        print(f'bench.py: {n_dumped} arrays of the last timed step in {args.dump_outputs}'
+              + ('' if dump_frac == 1.0 else f' (a seeded sample of {dump_frac:.3f} of each)'), file=sys.stderr, flush=True)
+    # --full: a second block of K steps, same fences: the steady-state number beside the headline (never instead of it).  HDY_BENCH_SECOND_BLOCK=0
+    # (the profiling scripts, which count kernels per step over warm-up + K steps) skips it.
+    second = args.full and os.environ.get('HDY_BENCH_SECOND_BLOCK', '1') != '0'
     t0 = time.perf_counter()
     for _ in range(args.steps if second else 0):
         step()
@@ -428,19 +478,19 @@ def main():
             tr = json.load(open(os.path.join(pdir, tj)))
             line['step'].update(traffic_gb_per_step=tr['hbm_gb_per_step'], traffic_ratio=round(tr['hbm_gb_per_step'] / (by / 1e9), 3),
                                 traffic_source='profiles/' + tj)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             line['roofline'] = conv_roofline(device)
             rows = bench_util.conv3x3_table(plan, PEAK_BF16_TFLOPS)
             line['roofline']['layers_3x3'] = rows
             line['roofline']['min_frac'] = min(r['frac'] for r in rows)
             line['roofline']['min_frac_of_bound'] = min(r['frac_of_bound'] for r in rows)
             line['roofline_hbm'] = bench_util.hbm_kernel_roofline(plan, PEAK_HBM_GBS)
-        if world == 1 and not args.no_infer and args.variant == 's' and args.batch == 64:
+        if args.full and world == 1 and not args.no_infer and args.variant == 's' and args.batch == 64:
             try:
                 line['infer'] = bench_util.infer_benchmark('l', 128, 1024, 3, device, cpu_nms=None if args.no_cpu_baseline else cpu_nms_baseline)
             except Exception as e:                                     # never lose the headline line to the side measurement
                 line['infer'] = {'error': repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args.variant, args.nc, args.size)
             ref = reference_c1()
             if ref is not None:

@@ -22,8 +22,8 @@
 //                  logits gradient straight into the NHWC buffer the backward plan consumes (bf16 or fp32, zero padded channels)
 //   final_kernel   loss = (box*sum_l mean_l + obj*sum_l balance_l*mean_l + cls*sum_l mean_l) * batch, and the three items
 //
-// Records of one cell are summed in list order, which depends on the order the matches arrived in: run-to-run differences are in the
-// last bits only (and only where three or more matches share a cell and anchor); every mean is taken over fp64 sums.
+// Records of one cell and anchor are summed in list order when there are at most two of them (the fp32 sum is then the same either way)
+// and in increasing candidate order from three on, so the logits gradient is the same on every run; every mean is taken over fp64 sums.
 #include <stdlib.h>
 
 #include "common.h"
@@ -277,7 +277,9 @@ __global__ __launch_bounds__(256) void dense_kernel(const LossArgs p) {
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
                     const int ob = half ? o0 - no : o0;                    // output index of channel 0 relative to this anchor
-                    for (int r = half ? r1 : r0; r != 0;) {
+                    const int rh = half ? r1 : r0;
+                    int n = 0;
+                    for (int r = rh; r != 0; ++n) {
                         const float* rec = p.recs + (size_t)(r - 1) * p.rs;
                         const f32x4 h1 = *(const f32x4*)(rec + 4);
 #pragma unroll
@@ -291,6 +293,36 @@ __global__ __launch_bounds__(256) void dense_kernel(const LossArgs p) {
                             } else if (p.nc > 1) v[i] += rec[8 + o - 5];
                         }
                         r = __float_as_int(h1[2]);
+                    }
+                    // The list is in the order the matches arrived in, which changes from run to run.  Up to two records their fp32 sum does
+                    // not depend on it (0 + a + b == 0 + b + a); from three on it does, so those lists are summed again in increasing
+                    // candidate order (unique within a list): the same bits on every run.  Such lists are rare; each pass picks the next record.
+                    if (n > 2) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int o = ob + i;
+                            if (o >= 0 && o < no && o != 4) v[i] = 0.f;          // this half's channels: nothing else adds to them
+                        }
+                        int last = -1;
+                        for (int k = 0; k < n; ++k) {
+                            int pick = 0, nxt = 0x7fffffff;
+                            for (int r = rh; r != 0;) {
+                                const f32x4 h1 = *(const f32x4*)(p.recs + (size_t)(r - 1) * p.rs + 4);
+                                const int order = __float_as_int(h1[1]);
+                                if (order > last && order < nxt) { nxt = order; pick = r; }
+                                r = __float_as_int(h1[2]);
+                            }
+                            if (!pick) break;
+                            last = nxt;
+                            const float* rec = p.recs + (size_t)(pick - 1) * p.rs;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                const int o = ob + i;
+                                if (o < 0 || o >= no || o == 4) continue;
+                                if (o < 4) v[i] += rec[o];
+                                else if (p.nc > 1) v[i] += rec[8 + o - 5];
+                            }
+                        }
                     }
                 }
             }

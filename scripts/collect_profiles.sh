@@ -7,9 +7,9 @@ R=${1:-r06}
 OUT=gpurun_out/prof_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-export HDY_BENCH_SECOND_BLOCK=0   # (round 6: bench.py times a second block of K steps by default; the per-step divisions here count warm-up + K)
+export HDY_BENCH_SECOND_BLOCK=0   # (bench.py --full times a second block of K steps; the per-step divisions here count warm-up + K)
 export HDY_BENCH_PREWARM_S=0      # the profiled runs count kernels per step: no untimed pre-warm steps in the trace (bench.py)
-rocprofv3 --kernel-trace --stats -d $OUT/bench -o bench --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-infer > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/bench -o bench --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-infer > $OUT/bench.log 2>&1
 rocprofv3 --kernel-trace --stats -d $OUT/roof -o roof --output-format csv -- python3 scripts/roofline_kernel.py > $OUT/roof.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o fetch --output-format csv -- python3 scripts/roofline_kernel.py > $OUT/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o write --output-format csv -- python3 scripts/roofline_kernel.py > $OUT/write.log 2>&1

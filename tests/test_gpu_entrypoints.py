@@ -134,9 +134,10 @@ def test_bench_py_single_rank_over_rccl():
     """The N > 1 path with the real collective library: one rank, backend nccl (= RCCL), process group + DataParallel + the overlapped
     bucketed all-reduce on the comm stream — what a one-GPU box can exercise of `python bench.py --gpus N`."""
     import json
-    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    # GPU_MAX_HW_QUEUES left out: what is pinned is the queue count the package itself sets, which an inherited value would override
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'GPU_MAX_HW_QUEUES')}
     env.update(HDY_FORCE_DIST='1', HDY_DIST_BACKEND='nccl', YOLOv5_VERBOSE='false', HSA_ENABLE_IPC_MODE_LEGACY='0', MASTER_PORT='29547')
-    p = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '8', '--no-roofline', '--no-cpu-baseline',
+    p = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '8', '--full', '--no-roofline', '--no-cpu-baseline',
                         '--no-infer'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=500)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])
@@ -154,7 +155,8 @@ def test_bench_py_single_rank_over_rccl():
 
 def _bench_line(env_extra, *flags):
     import json
-    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'HDY_FORCE_DIST')}
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'HDY_FORCE_DIST',
+                                                          'GPU_MAX_HW_QUEUES')}          # the package's own queue count, as in the test above
     env.update(YOLOv5_VERBOSE='false', HSA_ENABLE_IPC_MODE_LEGACY='0', **env_extra)
     p = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--no-roofline', '--no-cpu-baseline', '--no-infer'] + list(flags), cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
@@ -185,3 +187,37 @@ def test_bench_size_step_with_overlapped_rccl_allreduce_costs_a_few_percent():
     plain = min(a['ms_per_step'], b['ms_per_step'])
     print(f'bench-size step: plain {a["ms_per_step"]} / {b["ms_per_step"]} ms, over RCCL (1 rank, overlapped) {d["ms_per_step"]} ms, ratio {d["ms_per_step"] / plain:.3f}')
     assert d['ms_per_step'] <= RCCL_OVERLAP_MAX_RATIO * plain, (a['ms_per_step'], d['ms_per_step'], b['ms_per_step'])
+
+
+def test_bench_py_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run is the headline alone (no second block, no roofline / inference / CPU legs: those come with --full), and
+    --dump-outputs DIR writes what the last timed step computed — loss terms, the parameters the optimizer step wrote, the BatchNorm buffers —
+    as float32 .npy files (the same names on every run, at most 64 MB).  Two runs with the same arguments start from the same inputs and weights,
+    so what they dump must agree up to rounding — that is what lets two builds be compared output for output.  Both runs are the same build on
+    the same inputs, so bf16 operands are no reason for them to drift apart.  The bound is 1e-5 of each array's largest magnitude, well above
+    fp32 rounding over a few steps.  It is far below the percent-level drift that an order-dependent reduction builds up over a few training
+    steps: the loss's per-cell match records, summed in arrival order, did that."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'HDY_FORCE_DIST')}
+    env.update(YOLOv5_VERBOSE='false')
+    lines, dumps = [], []
+    for run_id in ('a', 'b'):
+        d = tmp_path / run_id
+        p = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '4', '--warmup', '1', '--batch', '8', '--size', '128',
+                            '--dump-outputs', str(d)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=500)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        lines.append(json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1]))
+        dumps.append({f.name[:-4]: np.load(f) for f in sorted(d.glob('*.npy'))})
+    line = lines[0]
+    assert line['steps'] == 4 and line['ms_per_step'] > 0 and abs(line['value'] - 8 * 1000.0 / line['ms_per_step']) <= 0.01 * line['value'], line
+    assert line['steady_state'] is None and not {'roofline', 'roofline_hbm', 'infer', 'cpu_baseline'} & set(line), sorted(line)
+    a, b = dumps
+    assert sorted(a) == sorted(b) and 'loss.det.det_loss' in a and any(k.startswith('param.') for k in a) and any(k.startswith('buffer.') for k in a)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(f.stat().st_size for f in (tmp_path / 'a').glob('*.npy')) <= 64 * 2**20
+    assert abs(float(a['loss.det.det_loss']) - line['final_loss']) <= 1e-3 * max(1.0, abs(line['final_loss']))
+    drift = {k: float(np.abs(a[k].astype(np.float64) - b[k]).max() / max(float(np.abs(a[k]).max()), 1e-30)) for k in a}
+    worst = sorted(drift.items(), key=lambda kv: -kv[1])[:5]
+    print('largest run-to-run drift (relative to the array\'s scale):', worst)
+    assert worst[0][1] <= 1e-5, worst
