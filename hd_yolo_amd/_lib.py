@@ -90,6 +90,8 @@ SIGNATURES = {
     'hdy_det_targets': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     'hdy_det_loss_workspace_bytes': (_Z, [_I, _P, _P, _I, _I, _I, _I]),
     'hdy_det_loss': (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _F, _F, _F, _F, _F, _P, _P, _Z, _P]),
+    'hdy_det_loss_ex': (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _I,
+                             _P, _P, _Z, _P]),
     'hdy_scale_inplace': (_I, [_P, _L, _P, _I, _P]),
     'hdy_sppf_pool_fwd': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'hdy_sppf_pool_bwd': (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -22,9 +22,22 @@
 //                  logits gradient straight into the NHWC buffer the backward plan consumes (bf16 or fp32, zero padded channels)
 //   final_kernel   loss = (box*sum_l mean_l + obj*sum_l balance_l*mean_l + cls*sum_l mean_l) * batch, and the three items
 //
+// Loss forms (template parameter of match_kernel and dense_kernel):
+//   BCE     the class and objectness terms are BCE with logits (pos_weight; class weights on the class term).
+//   FOCAL   the reference's FocalLoss (metayolo/models/loss.py:68-94) around the same BCE, B = w * bce(x, t; pw):
+//             s = sigmoid(x), p_t = t*s + (1-t)*(1-s), q = 1 - p_t, a = t*alpha + (1-t)*(1-alpha),  L = B * (a * q^gamma)
+//             dL/dx = a * (B' * q^gamma + B * gamma * q^(gamma-1) * (1-2t) * s * (1-s))
+//           in the reference's fp32 operation order, with the general (soft) target t.  At q == 0 (then t is 0 or 1 and s == t) the
+//           second term is defined as 0, its limit: the reference's autograd gives 0 * inf = NaN there for gamma < 1.
+// Objectness target of a cell (runtime flags, dense_kernel): by default the record with the highest candidate order; with sort_obj_iou the
+// largest clamped IoU of the cell's records (= the reference's ascending sort + last write: equal IoUs carry equal values); with gr < 1 the
+// winner becomes (1 - gr) + gr * iou (cells without a record stay 0).
+//
 // Records of one cell and anchor are summed in list order when there are at most two of them (the fp32 sum is then the same either way)
 // and in increasing candidate order from three on, so the logits gradient is the same on every run; every mean is taken over fp64 sums.
 #include <stdlib.h>
+
+#include <cmath>
 
 #include "common.h"
 
@@ -32,6 +45,8 @@ namespace {
 
 constexpr int MAXL = 5, MAXA = 8, MAXC = 128;
 constexpr int OSL = 64;      // objectness-sum slots per level: a workgroup adds to slot (its index % OSL); atomics on one address serialise
+
+enum LossForm { BCE = 0, FOCAL = 1 };
 
 template <typename T> struct Quad;                        // 4 consecutive channels in memory
 template <> struct Quad<float> { typedef f32x4 type; };
@@ -70,7 +85,11 @@ struct LossArgs {
     const float* gts;            // [nt][5] img, cx, cy, w, h (normalised)
     const float* tcls;           // [nt][nc] class targets (one- or multi-hot)
     float cw[MAXC];
-    float cls_pw, obj_pw, anchor_t, smooth;
+    float pw[MAXC];              // class pos_weight per class
+    float obj_pw, anchor_t, smooth;
+    float fl_gamma, fl_alpha, fl_alpha1;   // FOCAL: gamma, alpha, (float)(1 - (double)alpha)
+    float gr, gr1;               // objectness target (1 - gr) + gr * iou when gr < 1; gr1 = (float)(1 - (double)gr)
+    int sort_obj_iou;            // objectness target: the largest iou of the cell, not the last candidate
     float h_box, h_obj, h_cls;
     double* acc;                 // [MAXL][6]: sum(1-ciou), n, sum cls bce, n_cls rows, unused x2; then [MAXL][OSL] partial sums of the obj bce
     float* out;                  // loss, lbox, lobj, lcls
@@ -86,6 +105,17 @@ __device__ __forceinline__ float bce(float x, float t, float pw, float* grad) {
     *grad = s * (1.f - t + pw * t) - pw * t;
     return -(pw * t * ls + (1.f - t) * l1s);
 }
+// focal modulation of a BCE term: b = its value, db = its gradient (see the header comment for the formula and the q == 0 rule)
+__device__ __forceinline__ float focal(float x, float t, float b, float db, float gamma, float alpha, float alpha1, float* grad) {
+    const float s = sigm(x);
+    const float pt = t * s + (1.f - t) * (1.f - s);
+    const float q = 1.f - pt;
+    const float af = t * alpha + (1.f - t) * alpha1;
+    const float mf = q > 0.f ? powf(q, gamma) : 0.f;
+    const float dm = q > 0.f ? gamma * powf(q, gamma - 1.f) * ((1.f - 2.f * t) * (s * (1.f - s))) : 0.f;
+    *grad = af * (db * mf + b * dm);
+    return b * (af * mf);
+}
 
 __global__ __launch_bounds__(256) void zero_kernel(uint4* p, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = uint4{0, 0, 0, 0};
@@ -93,6 +123,7 @@ __global__ __launch_bounds__(256) void zero_kernel(uint4* p, size_t n16) {
 
 // grid.y = pyramid level: the levels are independent and each is a chain of dependent global accesses per lane (target row -> logits ->
 // atomics), so they run side by side in one launch (three launches back to back: 178 us per yolov5s step)
+template <int FORM>
 __global__ __launch_bounds__(256) void match_kernel(const LossArgs p) {
     const int l = blockIdx.y;
     const int na = p.na, nt = p.nt, nc = p.nc, no = p.no;
@@ -210,9 +241,14 @@ __global__ __launch_bounds__(256) void match_kernel(const LossArgs p) {
                 float gd = 0.f;
                 if (any > 0.f) {
                     const float tt = tc[c] - (tc[c] - 0.5f) * p.smooth;
-                    const float ls = bce(lg[5 + c], tt, p.cls_pw, &gd);
-                    s_cls += (double)(ls * p.cw[c]);
-                    gd *= p.cw[c];
+                    const float ls = bce(lg[5 + c], tt, p.pw[c], &gd);
+                    if (FORM == FOCAL) {
+                        const float bw = ls * p.cw[c];
+                        s_cls += (double)focal(lg[5 + c], tt, bw, gd * p.cw[c], p.fl_gamma, p.fl_alpha, p.fl_alpha1, &gd);
+                    } else {
+                        s_cls += (double)(ls * p.cw[c]);
+                        gd *= p.cw[c];
+                    }
                 }
                 rec[8 + c] = gd;
             }
@@ -237,7 +273,7 @@ __global__ __launch_bounds__(256) void match_kernel(const LossArgs p) {
 // list — empty for ~96 % of them — adding the box / class gradients of its channels and, for an objectness channel, keeping the iou of
 // the record with the highest candidate order.  Requires ldl % 4 == 0 and ldg % 4 == 0 (checked by the launcher).
 // grid.y = pyramid level (one launch for all levels); index arithmetic in 32 bits (the launcher checks cells * groups < 2^31).
-template <typename T>
+template <typename T, int FORM>
 __global__ __launch_bounds__(256) void dense_kernel(const LossArgs p) {
     const int l = blockIdx.y;
     const int na = p.na, no = p.no, ny = p.ny[l], nx = p.nx[l];
@@ -289,7 +325,10 @@ __global__ __launch_bounds__(256) void dense_kernel(const LossArgs p) {
                             if (o < 4) v[i] += rec[o];
                             else if (o == 4) {
                                 const int order = __float_as_int(h1[1]);
-                                if (order > best) { best = order; tgt = h1[0]; }
+                                if (p.sort_obj_iou) {
+                                    if (best < 0 || h1[0] > tgt) tgt = h1[0];
+                                    best = max(best, order);
+                                } else if (order > best) { best = order; tgt = h1[0]; }
                             } else if (p.nc > 1) v[i] += rec[8 + o - 5];
                         }
                         r = __float_as_int(h1[2]);
@@ -328,8 +367,10 @@ __global__ __launch_bounds__(256) void dense_kernel(const LossArgs p) {
             }
             float g_obj = 0.f;
             if (has_obj) {
+                if (best >= 0 && p.gr < 1.f) tgt = p.gr1 + p.gr * tgt;
                 float go;
-                s_obj += (double)bce(lg_obj, tgt, p.obj_pw, &go);
+                const float ls = bce(lg_obj, tgt, p.obj_pw, &go);
+                s_obj += (double)(FORM == FOCAL ? focal(lg_obj, tgt, ls, go, p.fl_gamma, p.fl_alpha, p.fl_alpha1, &go) : ls);
                 g_obj = go * k_obj;
             }
             int a = a0, o = o0;
@@ -537,11 +578,15 @@ size_t hdy_det_loss_workspace_bytes(int nl, const int* ny, const int* nx, int B,
     return n + a16((size_t)nl * 5 * na * (size_t)nt * det_loss_record_floats(nc) * sizeof(float));
 }
 
-int hdy_det_loss(const float* const* logits, int ldl, void* const* gdet, int ldg, int dtype, const int* ny, const int* nx, int nl, int B,
-                 int na, int nc, const float* anchors_grid, const float* balance, const float* gts, const float* tcls, int nt,
-                 const float* cls_cw, float cls_pw, float obj_pw, float anchor_t, float label_smoothing, float h_box, float h_obj, float h_cls,
-                 float* out, void* workspace, size_t ws_bytes, void* stream) {
-    HDY_ARG(logits && gdet && ny && nx && anchors_grid && balance && cls_cw && out && workspace, "det_loss: null pointer");
+int hdy_det_loss_ex(const float* const* logits, int ldl, void* const* gdet, int ldg, int dtype, const int* ny, const int* nx, int nl, int B,
+                    int na, int nc, const float* anchors_grid, const float* balance, const float* gts, const float* tcls, int nt,
+                    const float* cls_cw, const float* cls_pw, float obj_pw, float anchor_t, float label_smoothing, float h_box, float h_obj,
+                    float h_cls, float fl_gamma, float fl_alpha, float gr, int sort_obj_iou, float* out, void* workspace, size_t ws_bytes,
+                    void* stream) {
+    HDY_ARG(std::isfinite(fl_gamma) && fl_gamma >= 0.f, "det_loss: fl_gamma must be finite and >= 0 (got %g)", (double)fl_gamma);
+    HDY_ARG(std::isfinite(fl_alpha), "det_loss: fl_alpha must be finite (got %g)", (double)fl_alpha);
+    HDY_ARG(std::isfinite(gr), "det_loss: gr must be finite (got %g)", (double)gr);
+    HDY_ARG(logits && gdet && ny && nx && anchors_grid && balance && cls_cw && cls_pw && out && workspace, "det_loss: null pointer");
     HDY_ARG(nl >= 1 && nl <= MAXL && na >= 1 && na <= MAXA && nc >= 1 && nc <= MAXC && B >= 1 && nt >= 0, "det_loss: bad sizes");
     HDY_ARG(nt == 0 || (gts && tcls), "det_loss: targets missing");
     const int no = nc + 5;
@@ -565,8 +610,11 @@ int hdy_det_loss(const float* const* logits, int ldl, void* const* gdet, int ldg
         for (int i = 0; i < na; ++i) { a.anc[l][i][0] = anchors_grid[(l * na + i) * 2]; a.anc[l][i][1] = anchors_grid[(l * na + i) * 2 + 1]; }
     }
     a.nl = nl; a.B = B; a.na = na; a.nc = nc; a.no = no; a.ldl = ldl; a.ldg = ldg; a.nt = nt; a.gts = gts; a.tcls = tcls;
-    for (int c = 0; c < nc; ++c) a.cw[c] = cls_cw[c];
-    a.cls_pw = cls_pw; a.obj_pw = obj_pw; a.anchor_t = anchor_t; a.smooth = label_smoothing;
+    for (int c = 0; c < nc; ++c) { a.cw[c] = cls_cw[c]; a.pw[c] = cls_pw[c]; }
+    a.fl_gamma = fl_gamma; a.fl_alpha = fl_alpha; a.fl_alpha1 = (float)(1.0 - (double)fl_alpha);
+    a.gr = gr; a.gr1 = (float)(1.0 - (double)gr); a.sort_obj_iou = sort_obj_iou ? 1 : 0;
+    const bool focal_form = fl_gamma > 0.f;
+    a.obj_pw = obj_pw; a.anchor_t = anchor_t; a.smooth = label_smoothing;
     a.h_box = h_box; a.h_obj = h_obj; a.h_cls = h_cls; a.out = out;
     hipStream_t st = (hipStream_t)stream;
     const size_t used = (size_t)(w - (char*)workspace);          // sums, record counter, list heads: zeroed; the records behind them are not
@@ -577,7 +625,9 @@ int hdy_det_loss(const float* const* logits, int ldl, void* const* gdet, int ldg
     HDY_LAUNCH_CHECK("det_loss zero");
     if (nt > 0) {
         const int total = 5 * na * nt;
-        hipLaunchKernelGGL(match_kernel, dim3(cdiv(total, 1024) < 1024 ? cdiv(total, 1024) : 1024, nl), dim3(256), 0, st, a);
+        const dim3 mgrid(cdiv(total, 1024) < 1024 ? cdiv(total, 1024) : 1024, nl);
+        if (focal_form) hipLaunchKernelGGL(match_kernel<FOCAL>, mgrid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(match_kernel<BCE>, mgrid, dim3(256), 0, st, a);
         HDY_LAUNCH_CHECK("det_loss match");
     }
     long long most = 0;
@@ -590,12 +640,28 @@ int hdy_det_loss(const float* const* logits, int ldl, void* const* gdet, int ldg
     // with 1024 workgroups) — hence the OSL slots per level
     const int dense_grid = hdy_opt(HDY_OPT_LOSS_GRID);
     const int grid = (int)((most + 255) / 256 < dense_grid ? (most + 255) / 256 : dense_grid);
-    if (dtype == HDY_BF16) hipLaunchKernelGGL(dense_kernel<bf16_t>, dim3(grid, nl), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(dense_kernel<float>, dim3(grid, nl), dim3(256), 0, st, a);
+    if (dtype == HDY_BF16) {
+        if (focal_form) hipLaunchKernelGGL((dense_kernel<bf16_t, FOCAL>), dim3(grid, nl), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((dense_kernel<bf16_t, BCE>), dim3(grid, nl), dim3(256), 0, st, a);
+    } else {
+        if (focal_form) hipLaunchKernelGGL((dense_kernel<float, FOCAL>), dim3(grid, nl), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((dense_kernel<float, BCE>), dim3(grid, nl), dim3(256), 0, st, a);
+    }
     HDY_LAUNCH_CHECK("det_loss dense");
     hipLaunchKernelGGL(final_kernel, dim3(1), dim3(1), 0, st, a);
     HDY_LAUNCH_CHECK("det_loss final");
     return HDY_OK;
+}
+
+// the BCE form with one pos_weight for every class, the default objectness target rule
+int hdy_det_loss(const float* const* logits, int ldl, void* const* gdet, int ldg, int dtype, const int* ny, const int* nx, int nl, int B,
+                 int na, int nc, const float* anchors_grid, const float* balance, const float* gts, const float* tcls, int nt,
+                 const float* cls_cw, float cls_pw, float obj_pw, float anchor_t, float label_smoothing, float h_box, float h_obj, float h_cls,
+                 float* out, void* workspace, size_t ws_bytes, void* stream) {
+    float pw[MAXC];
+    for (int c = 0; c < MAXC; ++c) pw[c] = cls_pw;
+    return hdy_det_loss_ex(logits, ldl, gdet, ldg, dtype, ny, nx, nl, B, na, nc, anchors_grid, balance, gts, tcls, nt, cls_cw, pw, obj_pw,
+                           anchor_t, label_smoothing, h_box, h_obj, h_cls, 0.f, 0.25f, 1.f, 0, out, workspace, ws_bytes, stream);
 }
 
 int hdy_det_targets(const float* boxes, const float* img, const long long* labels, int nt, int nc, float* gts, float* tcls, void* stream) {

@@ -6,6 +6,8 @@ they consume the fp32 logits the HIP plan produces and seed its backward.  One d
 target scatter is made deterministic (last write wins, which is what the reference's CPU path does) instead of the
 GPU's unordered index_put.
 """
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -52,6 +54,34 @@ class FocalLoss(nn.Module):
         if self.reduction == 'mean':
             return loss.mean()
         return loss.sum() if self.reduction == 'sum' else loss
+
+
+def fused_criteria(det_loss, nc):
+    """The criteria of `det_loss` as csrc/loss.hip computes them, or None when it does not: decided from the criterion modules (what the
+    reference computes with), by type and shape only (no device reads, so it can run every step).  Accepted: BCEcls a
+    WeightReduceLoss(BCEWithLogitsLoss) and BCEobj a BCEWithLogitsLoss, both bare or both inside FocalLoss with equal gamma > 0 and alpha;
+    scalar or per-class class pos_weight and class weight, scalar objectness pos_weight.  Returns (cls WeightReduceLoss, cls BCE,
+    obj BCE, (gamma, alpha) or None)."""
+    def unwrap(m):
+        if type(m) is FocalLoss:
+            return m.loss_fcn, (float(m.gamma), float(m.alpha)), m.reduction
+        return m, None, getattr(m, 'reduction', None)
+
+    cls, f_cls, r_cls = unwrap(det_loss.BCEcls)
+    obj, f_obj, r_obj = unwrap(det_loss.BCEobj)
+    if type(cls) is not WeightReduceLoss or type(cls.loss_fn) is not nn.BCEWithLogitsLoss or type(obj) is not nn.BCEWithLogitsLoss:
+        return None
+    bce = cls.loss_fn
+    if r_cls not in ('mean', 'none') or r_obj != 'mean' or bce.reduction != 'none' or bce.weight is not None or obj.weight is not None:
+        return None
+    if f_cls != f_obj or (f_cls is not None and not (math.isfinite(f_cls[0]) and f_cls[0] > 0 and math.isfinite(f_cls[1]))):
+        return None
+
+    def fits(t, sizes):
+        return t is None or t.numel() in sizes
+    if not (fits(cls.weight, (1, nc)) and fits(bce.pos_weight, (1, nc)) and fits(obj.pos_weight, (1,))):
+        return None
+    return cls, bce, obj, f_cls
 
 
 def scatter_last(dst, index_tuple, values):

@@ -20,7 +20,7 @@ from .. import LOGGER
 from ... import engine as _engine
 from ... import ops as _ops
 from .layers import Conv
-from .loss import DetLoss, SegLoss
+from .loss import DetLoss, SegLoss, fused_criteria
 from .mask_rcnn import MaskRCNNHeads, MaskRCNNPredictor
 from .utils_general import nms_per_image, paired_box_iou, xywh2xyxy, xyxy2xywh
 from .utils_torch import one_hot_labels
@@ -279,11 +279,12 @@ class Detect(nn.Module):
 
     # ------------------------------------------------------------------ training side
     def fused_loss_ok(self):
-        """The single-launch-sequence loss (csrc/loss.hip) covers the default DetLoss: BCE (no focal), fixed balance."""
+        """The single-launch-sequence loss (csrc/loss.hip) covers DetLoss with BCE or focal criteria (loss.fused_criteria), any finite gr,
+        sort_obj_iou either way, fixed balance (no autobalance), up to 128 classes."""
         import os
         dl = self.det_loss
-        return (os.environ.get('HDY_FUSED_LOSS', '1') != '0' and not dl.autobalance and dl.hyp['fl_gamma'] == 0 and dl.gr == 1.0
-                and not dl.sort_obj_iou and self.nc <= 128)
+        return (os.environ.get('HDY_FUSED_LOSS', '1') != '0' and not dl.autobalance and self.nc <= 128 and math.isfinite(float(dl.gr))
+                and fused_criteria(dl, self.nc) is not None)
 
     def flatten_targets(self, targets, dev, fused=False):
         """Per-image ann dicts -> gts (nt,5) [img, cx, cy, w, h] and one-hot labels (nt, nc+1), built once per batch.

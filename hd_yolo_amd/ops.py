@@ -829,9 +829,11 @@ def cast_store(src_f32, dst, accumulate=False):
 
 # ------------------------------------------------------------------------------------------ fused detection loss
 class DetLossCall:
-    """Pre-marshalled hdy_det_loss call for one plan (pointers and geometry are static; only the targets change)."""
+    """Pre-marshalled hdy_det_loss_ex call for one plan (pointers, geometry and the criteria's weights are static; the targets change, and
+    the loss form and objectness target rule are read from det_loss on every call: gr, sort_obj_iou and a FocalLoss's gamma / alpha are
+    attributes a training script may set between steps)."""
 
-    def __init__(self, logits, gdets, na, nc, anchors_grid, balance, cls_cw, hyp, out, device):
+    def __init__(self, logits, gdets, na, nc, anchors_grid, balance, cls_cw, cls_pw, obj_pw, det_loss, out, device):
         nl = len(logits)
         self.nl, self.na, self.nc = nl, na, nc
         self.B = logits[0].shape[0]
@@ -845,7 +847,10 @@ class DetLossCall:
         self.anc = (ctypes.c_float * (nl * na * 2))(*[float(v) for v in anchors_grid])
         self.bal = (ctypes.c_float * nl)(*[float(v) for v in list(balance)[:nl]])    # nl = 4 takes the first 4 of the 5-level table (loss.py:201)
         self.cw = (ctypes.c_float * nc)(*[float(v) for v in cls_cw])
-        self.hyp = hyp
+        self.pw = (ctypes.c_float * nc)(*[float(v) for v in cls_pw])
+        self.obj_pw = float(obj_pw)
+        self.det_loss = det_loss
+        self.hyp = det_loss.hyp
         self.dtype = dcode(gdets[0].dtype)
         self.ws, self.ws_targets, self.device = None, -1, device       # sized by the number of targets, grown when a batch has more
         self.out = out
@@ -855,15 +860,17 @@ class DetLossCall:
         nt = int(gts.shape[0])
         assert gts.dtype == torch.float32 and gts.is_contiguous() and (nt == 0 or gts.shape[1] == 5)
         assert tcls.dtype == torch.float32 and tcls.is_contiguous() and (nt == 0 or tuple(tcls.shape) == (nt, self.nc))
-        h = self.hyp
+        h, dl = self.hyp, self.det_loss
+        gamma, alpha = (float(dl.BCEobj.gamma), float(dl.BCEobj.alpha)) if hasattr(dl.BCEobj, 'gamma') else (0.0, 0.25)
         if nt > self.ws_targets:
             self.ws_targets = max(64, nt + nt // 2)
             nbytes = _lib.query('hdy_det_loss_workspace_bytes', self.nl, self.ny, self.nx, self.B, self.na, self.nc, self.ws_targets)
             self.ws = torch.empty(nbytes // 4 + 4, dtype=torch.float32, device=self.device)
-        _lib.call('hdy_det_loss', self.lp, self.ldl, self.gp, self.ldg, self.dtype, self.ny, self.nx, self.nl, self.B, self.na, self.nc,
-                  self.anc, self.bal, gts.data_ptr() if nt else None, tcls.data_ptr() if nt else None, nt, self.cw,
-                  float(h['cls_pw']), float(h['obj_pw']), float(h['anchor_t']), float(h['label_smoothing']), float(h['box']),
-                  float(h['obj']), float(h['cls']), self.out.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 4, stream_ptr())
+        _lib.call('hdy_det_loss_ex', self.lp, self.ldl, self.gp, self.ldg, self.dtype, self.ny, self.nx, self.nl, self.B, self.na, self.nc,
+                  self.anc, self.bal, gts.data_ptr() if nt else None, tcls.data_ptr() if nt else None, nt, self.cw, self.pw,
+                  self.obj_pw, float(h['anchor_t']), float(h['label_smoothing']), float(h['box']), float(h['obj']), float(h['cls']),
+                  gamma, alpha, float(dl.gr), int(bool(dl.sort_obj_iou)), self.out.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 4,
+                  stream_ptr())
 
 
     def mask_select(self, gts, anchors_px, strides, min_iou=0.8):

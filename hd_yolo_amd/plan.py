@@ -909,11 +909,20 @@ class Plan:
     def fused_loss(self, head):
         """The hdy_det_loss call bound to this plan's logits / gradient buffers (built once)."""
         if self.loss_call is None:
+            from .metayolo.models.loss import fused_criteria
             anc = [float(v) for buf in head.anchors for v in buf.anchor.flatten().tolist()]
-            cw = head.det_loss.BCEcls.weight if hasattr(head.det_loss.BCEcls, 'weight') else None
-            cw = [1.0] * head.nc if cw is None else ([float(cw)] * head.nc if cw.numel() == 1 else [float(v) for v in cw.flatten().tolist()])
+            crit = fused_criteria(head.det_loss, head.nc)
+            assert crit is not None, 'the fused loss does not cover these criteria (Detect.fused_loss_ok)'
+            cls, bce, obj, _ = crit             # a FocalLoss wrapper is unwrapped: the class weights and pos_weights are its inner criterion's
+
+            def per_class(t, default):
+                if t is None:
+                    return [default] * head.nc
+                return [float(t)] * head.nc if t.numel() == 1 else [float(v) for v in t.flatten().tolist()]
+            cw, pw = per_class(cls.weight, 1.0), per_class(bce.pos_weight, 1.0)
+            obj_pw = 1.0 if obj.pos_weight is None else float(obj.pos_weight)
             self.loss_call = ops.DetLossCall([u.logits for u in self.det_units], [u.gdet for u in self.det_units], head.na, head.nc, anc,
-                                             head.det_loss.balance, cw, head.det_loss.hyp, self.loss_out, self.device)
+                                             head.det_loss.balance, cw, pw, obj_pw, head.det_loss, self.loss_out, self.device)
         return self.loss_call
 
     def tap_features(self):

@@ -292,7 +292,8 @@ int hdy_cast_store(const float* src, void* dst, int ldd, long long M, int C, int
  * logits[l]: fp32 [B][ny][nx][ldl], channel a*no+o;  gdet[l]: dtype [B][ny][nx][ldg] (ldl, ldg multiples of 4, 16-byte aligned
  * bases; channels >= na*no of gdet are written as zero);  anchors_grid: nl*na*2 HOST floats in grid
  * units; balance: nl HOST floats; gts: device [nt][5] (img, cx, cy, w, h normalised); tcls: device [nt][nc] class targets;
- * cls_cw: nc HOST floats.  out: device [4] = loss (x batch), box, obj, cls items.  Supported: fl_gamma = 0, no autobalance.
+ * cls_cw: nc HOST floats.  out: device [4] = loss (x batch), box, obj, cls items.  hdy_det_loss: BCE class / objectness terms with one
+ * class pos_weight, the reference's default objectness target (gr = 1, no sort_obj_iou); no autobalance.
  * workspace: hdy_det_loss_workspace_bytes(..., nt) bytes for calls with up to nt targets (sums, one list head per cell and anchor,
  * one record per possible match: nl * 5 * na * nt of them). */
 size_t hdy_det_loss_workspace_bytes(int nl, const int* ny, const int* nx, int B, int na, int nc, int nt);
@@ -300,6 +301,16 @@ int hdy_det_loss(const float* const* logits, int ldl, void* const* gdet, int ldg
                  int na, int nc, const float* anchors_grid, const float* balance, const float* gts, const float* tcls, int nt,
                  const float* cls_cw, float cls_pw, float obj_pw, float anchor_t, float label_smoothing, float h_box, float h_obj, float h_cls,
                  float* out, void* workspace, size_t ws_bytes, void* stream);
+/* hdy_det_loss with the other DetLoss forms (metayolo/models/loss.py:68-94 FocalLoss, :150 gr, :212-217 sort_obj_iou); hdy_det_loss is
+ * this call with the BCE form and gives the same bits.  cls_pw: nc HOST floats (per-class pos_weight).  fl_gamma > 0: both BCE terms
+ * wrapped in FocalLoss(gamma = fl_gamma, alpha = fl_alpha); fl_gamma == 0: BCE (fl_alpha unused).  gr < 1: a matched cell's objectness
+ * target is (1 - gr) + gr * iou; sort_obj_iou != 0: a cell matched several times keeps its largest iou instead of its last candidate's.
+ * HDY_EINVAL before any device work when fl_gamma is negative or not finite, or fl_alpha or gr is not finite. */
+int hdy_det_loss_ex(const float* const* logits, int ldl, void* const* gdet, int ldg, int dtype, const int* ny, const int* nx, int nl, int B,
+                    int na, int nc, const float* anchors_grid, const float* balance, const float* gts, const float* tcls, int nt,
+                    const float* cls_cw, const float* cls_pw, float obj_pw, float anchor_t, float label_smoothing, float h_box, float h_obj,
+                    float h_cls, float fl_gamma, float fl_alpha, float gr, int sort_obj_iou, float* out, void* workspace, size_t ws_bytes,
+                    void* stream);
 /* Which matched cell of each target feeds the mask branch (metayolo/models/yolo_head.py:231-262: per target the matched cell whose decoded
  * box has the best IoU with the truth — first in the reference's row order on ties — kept when that IoU >= min_iou = 0.8).  Same logits /
  * geometry / anchors_grid / gts / anchor_t as hdy_det_loss, anchors_px [nl][na][2] and strides [nl] as hdy_decode.  Device outputs:
