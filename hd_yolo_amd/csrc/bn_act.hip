@@ -454,6 +454,7 @@ __global__ __launch_bounds__(CL * TL) void bn_bwd_finalize_kernel(const float* _
 static void bn_bwd_finalize_launch(hipStream_t st, const float* partial, int nblocks, int K, double count, float* dgamma, float* dbeta, float* dgamma_b,
                                    float* dbeta_b, int Ka, int accumulate, float* c1, float* c2, const float* mean = nullptr,
                                    const float* invstd = nullptr) {
+    hdy_note_dispatch(nblocks >= 1024 ? "bn_bwd_finalize_wide" : "bn_bwd_finalize");
     if (nblocks >= 1024)
         hipLaunchKernelGGL((bn_bwd_finalize_kernel<8, 128>), dim3(cdiv(K, 8)), dim3(1024), 0, st, partial, nblocks, K, count, dgamma, dbeta, dgamma_b, dbeta_b, Ka,
                            accumulate, c1, c2, mean, invstd);
@@ -544,6 +545,7 @@ void bn_bwd_reduce_launch(dim3 grid, hipStream_t st, const Split& dz, const void
         // four channels per lane (see bn_act_bwd_reduce4_kernel): every BatchNorm of the path (K % 8 == 0, 8-element pitches); HDY_NO_BN_REDUCE4 keeps the
         // eight-channel form (A/B)
         if (y && !hdy_opt(HDY_OPT_NO_BN_REDUCE4) && dz.Ka % 4 == 0) {
+            hdy_note_dispatch("bn_bwd_reduce4");
             const dim3 g4(grid.x, cdiv(K / 4, 256));
             // rows in flight per lane: 4 (72 VGPRs) — 3 (60) and 2 (54) fit one more wave per SIMD beside the generic weight gradient and measured the same /
             // 0.1 ms slower in the step (11.94-11.96 | 11.92-11.99 | 12.06-12.08 ms; 8 channels per lane: 12.19-12.24).  A buffer-load form (one descriptor per
@@ -559,6 +561,7 @@ void bn_bwd_reduce_launch(dim3 grid, hipStream_t st, const Split& dz, const void
             return;
         }
     }
+    hdy_note_dispatch("bn_bwd_reduce");
     if (act == 1)
         hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<T, 2>), grid, dim3(256), 0, st, (const T*)dz.a, dz.lda, (const T*)dz.b, dz.ldb, dz.Ka, (const T*)y, ldy,
                            scale, shift, mean, invstd, M, K, act, rows, partial);
@@ -619,6 +622,7 @@ static int bn_finalize_impl(const float* stats, int stats_ld, int mtiles, int K,
     HDY_ARG(bn.Ka == K || (bn.Ka > 0 && bn.Ka < K && bn.gamma_b && bn.beta_b && (bn.rmean_b == nullptr) == (bn.rvar_b == nullptr)),
             "bn_finalize_pair: second module's parameters missing or split point outside (0, K)");
     hipStream_t st = (hipStream_t)stream;
+    hdy_note_dispatch(mtiles > 1024 && workspace ? "bn_finalize_2stage" : "bn_finalize");
     if (mtiles > 1024 && workspace) {
         // two stages: 32 groups of tiles reduced in parallel, then the usual final stage over 32 fp64 partials
         const int G = 32, tpg = cdiv(mtiles, G);

@@ -646,6 +646,7 @@ int hdy_wgrad_reduce_launch(const float* partial, int splits, size_t slab_stride
                             int accumulate, hipStream_t st) {
     const int n = K * Q;
     const bool vec = n % 4 == 0 && slab_stride % 4 == 0 && ((uintptr_t)partial & 15) == 0 && (!(mode == 0 && R == 1 && S == 1) || ((uintptr_t)grad & 15) == 0);
+    hdy_note_dispatch(vec ? "wgrad_reduce" : "wgrad_reduce_scalar");
     if (vec)
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(1024), 0, st, partial, splits, slab_stride, K, Q, mode, C, R, S, grad, accumulate);
     else
@@ -656,6 +657,7 @@ int hdy_wgrad_reduce_launch(const float* partial, int splits, size_t slab_stride
 }
 
 int hdy_pack_weight_launch(const hdy_pack_desc& d, hipStream_t st) {
+    hdy_note_dispatch(d.stem ? "pack_stem" : (d.transpose ? "pack_dgrad" : "pack_fwd"));
     hipLaunchKernelGGL(pack_weight_kernel, dim3(d.nblocks), dim3(256), 0, st, d);
     HDY_LAUNCH_CHECK("pack_weight");
     return HDY_OK;

@@ -776,6 +776,7 @@ int hdy_groupnorm_fwd(const void* x, int ldx, const float* gamma, const float* b
     const int VE = dtype == HDY_BF16 ? 8 : 4;
     HDY_ARG(x && gamma && beta && y && stat && ab && workspace && N > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, "groupnorm_fwd: bad args");
     HDY_ARG(C % VE == 0 && VEC_OK(x, ldx, VE) && VEC_OK(y, ldy, VE) && C <= 4096, "groupnorm_fwd: C/pitch/alignment must be multiples of one 16-byte vector");
+    hdy_note_dispatch("groupnorm_fwd");
     hipStream_t st = (hipStream_t)stream;
     dim3 rg(N, GN_SLICES);
     if (dtype == HDY_BF16)
@@ -806,6 +807,7 @@ int hdy_groupnorm_bwd(const void* dout, int lddo, const void* x, int ldx, const 
     HDY_ARG(N > 0 && C > 0 && ws_floats >= hdy_groupnorm_workspace_floats(N, C), "groupnorm_bwd: workspace of %zu floats is too small", ws_floats);
     HDY_ARG(dout && x && gamma && stat && ab && dx && dgamma && dbeta && coef && workspace && N > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0, "groupnorm_bwd: bad args");
     HDY_ARG(C % VE == 0 && VEC_OK(x, ldx, VE) && VEC_OK(dout, lddo, VE) && VEC_OK(dx, lddx, VE) && C <= 4096, "groupnorm_bwd: C/pitch/alignment must be multiples of one 16-byte vector");
+    hdy_note_dispatch("groupnorm_bwd");
     hipStream_t st = (hipStream_t)stream;
     float* pc = workspace + (size_t)N * GN_SLICES * 2 * C;
     dim3 rg(N, GN_SLICES);
@@ -893,6 +895,7 @@ size_t hdy_softdice_workspace_floats(int N, int nc) { return (size_t)N * DICE_SL
 int hdy_softdice(const float* logits, int ldl, const float* targets, const float* class_weight, int N, int HW, int nc, float* loss,
                  const float* upstream, float* dlogits, int lddl, float* workspace, size_t ws_floats, void* stream) {
     HDY_ARG(N > 0 && nc > 0 && ws_floats >= hdy_softdice_workspace_floats(N, nc), "softdice: workspace of %zu floats is too small", ws_floats);
+    hdy_note_dispatch("softdice");
     HDY_ARG(logits && targets && loss && workspace && N > 0 && HW > 0 && nc > 0 && nc <= DICE_MAXC && ldl >= nc && N * nc <= 65536, "softdice: bad args (nc <= %d)", DICE_MAXC);
     hipStream_t st = (hipStream_t)stream;
     float* coef = workspace + (size_t)N * DICE_SLICES * 2 * nc;

@@ -160,7 +160,7 @@ def conv_case(case, dtype):
     xd = to_dev_nhwc(x, dtype, ld=C + 16, off=8)
     Ho, Wo = ops.out_dim(H, R, stride, pad), ops.out_dim(W, R, stride, pad)
     wdev = w.to(DEV)
-    wp = ops.pack_alloc(K, C, R, R, stride, pad, ops.PACK_FWD, dtype, DEV)
+    wp = ops.pack_alloc(K, C, R, R, stride, pad, ops.PACK_FWD, dtype, DEV).fill_(float('nan'))      # the pack must write every element (padding too)
     ybuf = torch.full((N, Ho, Wo, K + 8), 5.0, dtype=dtype, device=DEV)
     y = ybuf[..., 8:]
     mt = ops.stat_slabs(N, H, W, C, K, R, R, stride, pad, dtype)
@@ -192,7 +192,7 @@ def conv_case(case, dtype):
     wr = wq.clone().requires_grad_(True)
     F.conv2d(xr, wr, None, stride, pad).backward(dy)
     dyd = to_dev_nhwc(dy, dtype, ld=K + 8, off=0)
-    wpd = ops.pack_alloc(K, C, R, R, stride, pad, ops.PACK_DGRAD, dtype, DEV)
+    wpd = ops.pack_alloc(K, C, R, R, stride, pad, ops.PACK_DGRAD, dtype, DEV).fill_(float('nan'))
     dx = torch.full((N, H, W, C), 1.0, dtype=dtype, device=DEV)
     ops.run([ops.rec_pack(wdev, None, stride, pad, ops.PACK_DGRAD, wpd)])
     _lib.dispatch_log(reset=True)
@@ -200,7 +200,7 @@ def conv_case(case, dtype):
     log_dgrad = _lib.dispatch_log(reset=True)
     assert_close(from_dev_nhwc(dx), xr.grad + 1.0, TOL[dtype] * 2, 'dgrad')
 
-    ws = torch.empty(ops.wgrad_ws_bytes(N, H, W, C, K, R, R, stride, pad, dtype) // 4 + 1, dtype=torch.float32, device=DEV)
+    ws = torch.full((ops.wgrad_ws_bytes(N, H, W, C, K, R, R, stride, pad, dtype) // 4 + 1,), float('nan'), dtype=torch.float32, device=DEV)   # read only where written
     ka = K // 2 if K >= 16 else K
     ga = torch.zeros((ka, C, R, R), dtype=torch.float32, device=DEV)
     gb = torch.full((K - ka, C, R, R), 2.0, dtype=torch.float32, device=DEV) if ka < K else None
