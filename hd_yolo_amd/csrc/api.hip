@@ -1,7 +1,7 @@
 // C-ABI entry points for the convolution family (see include/hdyolo.h).  Everything here is host code that
-// validates shapes, derives the tap-window geometry and launches the kernels in conv_igemm.hip / conv_wgrad.hip
-// on the caller's stream.  No allocation, no synchronisation; process state = the option table below (atomics, initialised once from the
-// environment), the per-kernel "LDS size attribute set" once-flags, and the thread-local error text / dispatch log.
+// validates shapes, derives the tap-window geometry and launches the kernels (forward / data gradient: through conv_dispatch.hip's
+// hdy_conv_launch; weight gradient: conv_wgrad*.hip) on the caller's stream.  No allocation, no synchronisation; process state = the
+// option table below (atomics, initialised once from the environment), the per-kernel "LDS size attribute set" once-flags, and the thread-local error text / dispatch log.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -97,6 +97,15 @@ inline Axis class_axis(int R, int pad, int a) {
     return ax;
 }
 
+// Stride-2 data gradient as ONE launch that walks the four parity classes per spatial tile: every class has the same Ho x Wo (even H and W)
+// and taps of its own.
+inline bool dgrad_class_walk(int H, int W, int R, int S, int pad) {
+    if (H % 2 || W % 2 || hdy_opt(HDY_OPT_NO_CLASS_WALK)) return false;
+    for (int a = 0; a < 2; ++a)
+        if (!class_axis(R, pad, a).taps || !class_axis(S, pad, a).taps) return false;
+    return true;
+}
+
 // rows (padded to the N-tile) x pitch of one packed block
 inline size_t block_elems(int rows, int kd, int dtype) {
     const int bn = hdy_conv_bn_tile(rows);
@@ -149,29 +158,9 @@ int hdy_fastdiv_magic(unsigned d, unsigned* magic, int* shift) {
     return HDY_OK;
 }
 
-int hdy_conv_out_dim(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
+int hdy_conv_out_dim(int in, int k, int stride, int pad) { return conv_out_dim(in, k, stride, pad); }
 
 int hdy_conv_mtiles(long long M) { return (int)((M + 127) / 128); }
-
-int hdy_conv_stat_slabs(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype) {
-    int own = hdy_conv3x3_c64_slabs(N, H, W, C, K, R, S, stride, pad, dtype);
-    if (own > 0) return own;
-    own = hdy_conv3x3_c128_slabs(N, H, W, C, K, R, S, stride, pad, dtype);
-    if (own > 0) return own;
-    own = hdy_conv3x3s2_c32_slabs(N, H, W, C, K, R, S, stride, pad, dtype);
-    if (own > 0) return own;
-    const bool stem = C == 3 && R == 6 && S == 6 && stride == 2 && pad == 2;
-    if (stem) {
-        own = hdy_conv_stem_slabs(N, H, W, K, dtype);
-        if (own > 0) return own;
-    }
-    const long long M = (long long)N * hdy_conv_out_dim(H, R, stride, pad) * hdy_conv_out_dim(W, S, stride, pad);
-    if (!stem) {
-        own = hdy_conv_deep_slabs(M, C, K, R * S, R == 1 && S == 1 && stride == 1 && pad == 0, dtype);
-        if (own > 0) return own;
-    }
-    return hdy_conv_igemm_slabs(M, K, stem ? 6 : R * S);
-}
 
 size_t hdy_conv_pack_elems(int K, int C, int R, int S, int stride, int pad, int kind, int dtype) {
     if (kind == KIND_FWD) return block_elems(K, R * S * C, dtype);
@@ -278,12 +267,12 @@ int hdy_conv_fwd(const void* x, int ldx, const void* w_packed, const float* scal
         a.Hin = H + 2 * pad; a.Win = W + 2 * pad; a.C = 24; a.ldx = 4; a.span_pixels = 1;
         a.ih_mul = 2; a.iw_mul = 2; a.dh0 = 0; a.dw0 = 0; a.TH = 6; a.TW = 1;
         a.Kdp = round_up(6 * 24, bke(dtype));
-        return hdy_conv_igemm_launch(a, dtype, out_f32, (hipStream_t)stream);
+        return hdy_conv_launch(a, dtype, out_f32, (hipStream_t)stream);
     }
     a.Hin = H; a.Win = W; a.C = C; a.ldx = ldx;
     a.ih_mul = stride; a.iw_mul = stride; a.dh0 = -pad; a.dw0 = -pad; a.TH = R; a.TW = S;
     a.Kdp = round_up(R * S * C, bke(dtype));
-    return hdy_conv_igemm_launch(a, dtype, out_f32, (hipStream_t)stream);
+    return hdy_conv_launch(a, dtype, out_f32, (hipStream_t)stream);
 }
 
 // dx (+)= conv_transpose(dy, w): dx is [N][H][W][lddx] (C channels), dy is [N][Ho][Wo][lddy] (K channels).
@@ -302,14 +291,17 @@ int hdy_conv_dgrad_stats(const void* dy, int lddy, const void* w_packed_dgrad, v
     return dgrad_impl(dy, lddy, w_packed_dgrad, dx, lddx, N, H, W, C, K, R, S, stride, pad, accumulate, dtype, stats, nstat, stream);
 }
 
-// workgroups of the data-gradient launch that would serve statistics: stride 1, or stride 2 as ONE class-walking launch (even H, W)
+// workgroups of the data-gradient launch that would serve statistics: stride 1, or stride 2 as ONE class-walking launch.  The statistics
+// instances are the generic kernel's with at most 64 output channels (the 128-wide ones have no registers to spare for the operands).
 int hdy_conv_dgrad_stat_slabs(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype) {
-    if (dtype != HDY_BF16 || C % 8 || (stride != 1 && stride != 2)) return 0;
-    if (stride == 1) return hdy_conv_igemm_stat_grid((long long)N * H * W, C, R * S, 1);
-    if (H % 2 || W % 2 || hdy_opt(HDY_OPT_NO_CLASS_WALK)) return 0;
-    for (int a = 0; a < 2; ++a)
-        if (!class_axis(R, pad, a).taps || !class_axis(S, pad, a).taps) return 0;
-    return hdy_conv_igemm_stat_grid((long long)N * (H / 2) * (W / 2), C, 1, 4);
+    if (dtype != HDY_BF16 || C % 8 || hdy_conv_bn_tile(C) > 64 || (stride != 1 && stride != 2)) return 0;
+    if (stride == 2 && !dgrad_class_walk(H, W, R, S, pad)) return 0;
+    ConvShape s = {};                       // the gradient as a convolution K -> C onto the H x W (stride 2: four classes of H/2 x W/2) grid
+    s.N = N; s.Ho = H / stride; s.Wo = W / stride; s.C = K; s.K = C; s.R = R; s.S = S; s.stride = 1; s.pad = -1; s.dtype = dtype;
+    s.dense = stride == 1; s.ncls = stride == 2 ? 4 : 1;
+    ConvPlan p;
+    hdy_conv_igemm_plan(s, &p);
+    return p.grid;
 }
 
 static int dgrad_impl(const void* dy, int lddy, const void* w_packed_dgrad, void* dx, int lddx, int N, int H, int W, int C, int K, int R,
@@ -330,39 +322,33 @@ static int dgrad_impl(const void* dy, int lddy, const void* w_packed_dgrad, void
         a.Ho = H; a.Wo = W; a.oh_mul = a.ow_mul = 1; a.dense_out = 1;
         a.dh0 = pad - (R - 1); a.dw0 = pad - (S - 1); a.TH = R; a.TW = S;
         a.Kdp = round_up(R * S * K, bke(dtype));
-        return hdy_conv_igemm_launch(a, dtype, 0, (hipStream_t)stream);
+        return hdy_conv_launch(a, dtype, 0, (hipStream_t)stream);
     }
     const int rows_total = round_up(C, hdy_conv_bn_tile(C));
     size_t off = 0;
     // One launch walking the four parity classes per spatial tile (conv_igemm.hip, `walk`): every class has the same Ho x Wo when H and W
     // are even.  As four launches each class wrote every other pixel of every other row (half cache lines, each line written by two
     // launches) and read dy from HBM again: 32<-64 @320x320 B=64 took 353 us against a 100 us bound.
-    const bool no_walk = hdy_opt(HDY_OPT_NO_CLASS_WALK) != 0;
-    if (H % 2 == 0 && W % 2 == 0 && !no_walk) {
+    if (dgrad_class_walk(H, W, R, S, pad)) {
         ConvArgs c = a;
         c.ncls = 4;
         c.Ho = H / 2; c.Wo = W / 2;
         c.oh_mul = c.ow_mul = 2; c.dense_out = 0;
-        bool ok = true;
-        for (int ca = 0; ca < 2 && ok; ++ca)
+        for (int ca = 0; ca < 2; ++ca)
             for (int cb = 0; cb < 2; ++cb) {
                 const Axis ah = class_axis(R, pad, ca), aw = class_axis(S, pad, cb);
-                if (!ah.taps || !aw.taps) { ok = false; break; }
                 const int i = ca * 2 + cb;
                 const int Kdp = round_up(ah.taps * aw.taps * K, bke(dtype));
                 c.c_dh[i] = ah.d0; c.c_dw[i] = aw.d0; c.c_TH[i] = ah.taps; c.c_TW[i] = aw.taps;
                 c.c_nkb[i] = Kdp / bke(dtype); c.c_oh[i] = ca; c.c_ow[i] = cb; c.c_w[i] = (long long)off;
                 off += (size_t)rows_total * Kdp;
             }
-        if (ok) {
-            c.w = w_packed_dgrad;
-            c.dh0 = c.c_dh[0]; c.dw0 = c.c_dw[0]; c.TH = c.c_TH[0]; c.TW = c.c_TW[0]; c.oh_off = c.ow_off = 0;
-            c.Kdp = c.c_nkb[0] * bke(dtype);
-            int rc2 = HDY_OK;
-            if (hdy_dgrad3x3s2_try(c, dtype, (hipStream_t)stream, &rc2)) return rc2;     // patch-resident kernel for the 32<-64 layer
-            return hdy_conv_igemm_launch(c, dtype, 0, (hipStream_t)stream);
-        }
-        off = 0;
+        c.w = w_packed_dgrad;
+        c.dh0 = c.c_dh[0]; c.dw0 = c.c_dw[0]; c.TH = c.c_TH[0]; c.TW = c.c_TW[0]; c.oh_off = c.ow_off = 0;
+        c.Kdp = c.c_nkb[0] * bke(dtype);
+        int rc2 = HDY_OK;
+        if (hdy_dgrad3x3s2_try(c, dtype, (hipStream_t)stream, &rc2)) return rc2;     // patch-resident kernel for the 32<-64 layer
+        return hdy_conv_launch(c, dtype, 0, (hipStream_t)stream);
     }
     for (int ca = 0; ca < 2; ++ca)
         for (int cb = 0; cb < 2; ++cb) {
@@ -378,7 +364,7 @@ static int dgrad_impl(const void* dy, int lddy, const void* w_packed_dgrad, void
             c.Kdp = round_up(ah.taps * aw.taps * K, bke(dtype));
             c.w = (const char*)w_packed_dgrad + off * esize(dtype);
             off += (size_t)rows_total * c.Kdp;
-            const int rc = hdy_conv_igemm_launch(c, dtype, 0, (hipStream_t)stream);
+            const int rc = hdy_conv_launch(c, dtype, 0, (hipStream_t)stream);
             if (rc) return rc;
         }
     return HDY_OK;

@@ -31,38 +31,7 @@ template <typename T> struct VT;
 template <> struct VT<float> { static constexpr int VE = 4; };
 template <> struct VT<bf16_t> { static constexpr int VE = 8; };
 
-template <typename T> __device__ __forceinline__ void unpack(const i32x4& v, float* f);
-template <> __device__ __forceinline__ void unpack<float>(const i32x4& v, float* f) {
-    V16 u; u.i = v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f[i] = u.f[i];
-}
-template <> __device__ __forceinline__ void unpack<bf16_t>(const i32x4& v, float* f) {
-    V16 u; u.i = v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = (float)u.h[i];
-}
-template <typename T> __device__ __forceinline__ i32x4 pack(const float* f);
-template <> __device__ __forceinline__ i32x4 pack<float>(const float* f) {
-    V16 u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) u.f[i] = f[i];
-    return u.i;
-}
-template <> __device__ __forceinline__ i32x4 pack<bf16_t>(const float* f) {
-    V16 u;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) u.h[i] = (bf16_t)f[i];
-    return u.i;
-}
-
-// v_exp_f32 + v_rcp_f32 (1 ulp): plenty for activations and far cheaper than the IEEE division sequence
-__device__ __forceinline__ float fast_sigmoid(float u) { return __builtin_amdgcn_rcpf(1.0f + __expf(-u)); }
 __device__ __forceinline__ float fast_silu(float u) { return u * fast_sigmoid(u); }
-__device__ __forceinline__ float dsilu_f(float u) {
-    const float s = fast_sigmoid(u);
-    return s * (1.0f + u * (1.0f - s));
-}
 
 // lane -> (channel vector, row lane) for a 256-thread block over rows of VCt vectors
 struct Lane {
@@ -605,7 +574,6 @@ void bn_act_fwd_dispatch(int grid, hipStream_t st, const void* y, int ldy, const
 
 }  // namespace
 
-#define VEC_OK(ptr, ld, VE) ((((uintptr_t)(ptr)) & 15) == 0 && (ld) % (VE) == 0)
 #define M_OK(M) ((M) > 0 && (M) < (1LL << 31))
 
 extern "C" {

@@ -133,4 +133,80 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
     const int q = n >> 3, r = n & 7, x = id & 7, s = id >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + s;
 }
+// ---- device helpers shared by several kernel files ------------------------------------------------------------------------------------------
+// n / d for n < 2^31 with the host-made reciprocal of hdy_magic(): mulhi(2n, mg) >> sh
+__device__ __forceinline__ unsigned fdiv(unsigned n, unsigned mg, int sh) { return __umulhi(n << 1, mg) >> sh; }
+
+// LDS-DMA straight from global memory: lane l's 16 bytes at g land at lds_wave_base + l*16
+__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
+                                     (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
+}
+
+// LDS-DMA through a buffer descriptor: lane l's 16 bytes at base + voff + soff land at lds + l*16; a lane whose offset fails the
+// descriptor's range check (>= num_records) gets zeros.
+__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, unsigned char* lds_wave_base) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (void __attribute__((address_space(3)))*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
+}
+
+// ... with the LDS destination as a byte address
+__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, unsigned lds_byte) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (void __attribute__((address_space(3)))*)(uintptr_t)lds_byte, 16, (int)voff, (int)soff, 0, 0);
+}
+
+// 32-byte-block (fsw) and 16-byte-chunk (fsw3) XOR swizzles of the [rows][128 B] LDS sub-tiles of the weight-gradient / fused 1x1 backward kernels
+__device__ __forceinline__ int fsw(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }
+__device__ __forceinline__ int fsw3(int row) { return (row & 6) ^ (((row >> 3) & 1) * 5); }
+
+// v_exp_f32 + v_rcp_f32 (1 ulp): plenty for activations and far cheaper than the IEEE division sequence
+__device__ __forceinline__ float fast_sigmoid(float u) { return __builtin_amdgcn_rcpf(1.0f + __expf(-u)); }
+__device__ __forceinline__ float dsilu_f(float u) {
+    const float s = fast_sigmoid(u);
+    return s * (1.0f + u * (1.0f - s));
+}
+
+// 16 bytes of T <-> fp32 values; VEC_OK: rows of `ld` elements at `ptr` can be moved in such vectors
+template <typename T> __device__ __forceinline__ void unpack(const i32x4& v, float* f);
+template <> __device__ __forceinline__ void unpack<float>(const i32x4& v, float* f) {
+    V16 u; u.i = v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = u.f[i];
+}
+template <> __device__ __forceinline__ void unpack<bf16_t>(const i32x4& v, float* f) {
+    V16 u; u.i = v;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = (float)u.h[i];
+}
+template <typename T> __device__ __forceinline__ i32x4 pack(const float* f);
+template <> __device__ __forceinline__ i32x4 pack<float>(const float* f) {
+    V16 u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) u.f[i] = f[i];
+    return u.i;
+}
+template <> __device__ __forceinline__ i32x4 pack<bf16_t>(const float* f) {
+    V16 u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) u.h[i] = (bf16_t)f[i];
+    return u.i;
+}
+
+#define VEC_OK(ptr, ld, VE) ((((uintptr_t)(ptr)) & 15) == 0 && (ld) % (VE) == 0)
+
+// LDS fragment reads and barriers of the patch-resident stride-2 kernels (conv3x3s2.hip, conv_dgrad_s2.hip; `HAND`, `smem`, `lds0` are the
+// kernel's): as inline asm with hand-counted waits where HAND, else compiler-visible
+#define S2_LDSR(dst, addr)                                                                             \
+    do {                                                                                               \
+        if constexpr (HAND) asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");    \
+        else dst = *(const i32x4*)(smem + ((addr) - lds0));                                            \
+    } while (0)
+#define S2_LGKM(n)                                                                                                       \
+    do {                                                                                                                 \
+        if constexpr (HAND) { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n) : "memory"); __builtin_amdgcn_sched_barrier(0); } \
+    } while (0)
+#define S2_BARRIER(lg)                                                                                                   \
+    do {                                                                                                                 \
+        if constexpr (HAND) { if (lg) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } \
+        else __syncthreads();                                                                                            \
+    } while (0)
 #endif

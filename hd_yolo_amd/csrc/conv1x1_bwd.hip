@@ -51,15 +51,8 @@ struct FusedArgs {
     StatReq stat[2];
 };
 
-__device__ __forceinline__ int fsw3(int row) { return (row & 6) ^ (((row >> 3) & 1) * 5); }
 // byte offset of 16-byte chunk `chunk` (0..7) of row `row` inside a [rows][128 B] sub-tile
 __device__ __forceinline__ int toff(int row, int chunk) { return row * 128 + ((chunk ^ fsw3(row)) << 4); }
-
-__device__ __forceinline__ float fast_sigmoid(float u) { return __builtin_amdgcn_rcpf(1.0f + __expf(-u)); }
-__device__ __forceinline__ float dsilu_f(float u) {
-    const float s = fast_sigmoid(u);
-    return s * (1.0f + u * (1.0f - s));
-}
 
 // The element-wise part of this kernel was its bound (PMC, 64<>64 @160x160: 6.2e7 VALU wave-instructions for 1.05e8 elements = 38 lane
 // instructions per element, ~180 us of VALU issue in a 258 us launch whose bytes take 167 us).  It now runs on PAIRS of channels with packed

@@ -54,7 +54,7 @@
 // MFMA k-step per tap, 36 filter VGPRs; for K == 32 two of the four waves carry zero filters.  64 x 160 x 160, 32->32: 75 us against
 // 134 us through the generic kernel (in the train step 70 + 58 us for forward + dgrad against 2 x ~103 us).
 //
-// Requirements (checked by the launcher, otherwise the generic kernel runs): bf16 in/out, C == 64 or 32, K <= 64, R = S = 3,
+// Requirements (hdy_conv3x3_c64_plan for the shape, hdy_conv3x3_c64_launch for the pointers; otherwise the next family of conv_fwd_plan runs): bf16 in/out, C == 64 or 32, K <= 64, R = S = 3,
 // stride 1, pad 1, H % 8 == 0, W % 16 == 0, 16-byte aligned rows.
 #include <stdlib.h>
 
@@ -66,11 +66,6 @@
 __device__ uint4 g_hdy_zero16_c3[4];   // zero page for out-of-image patch pixels
 
 namespace {
-
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
-                                     (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
-}
 
 // The split of `tiles` whole tiles over `grid` workgroups, computed identically on host and device.
 struct WorkSplit {
@@ -387,65 +382,27 @@ static void launch_c3(const ConvArgs& a, int grid, hipStream_t st) {
 }
 
 template <int C>
-static void launch_c3_c(const ConvArgs& a, int grid, int epi, hipStream_t st) {
-    if (a.stats) {
-        if (epi == 2) launch_c3<C, 2, true>(a, grid, st);
-        else if (epi == 1) launch_c3<C, 1, true>(a, grid, st);
-        else launch_c3<C, 0, true>(a, grid, st);
-    } else {
-        if (epi == 2) launch_c3<C, 2, false>(a, grid, st);
-        else if (epi == 1) launch_c3<C, 1, false>(a, grid, st);
-        else launch_c3<C, 0, false>(a, grid, st);
-    }
+static void launch_c3_c(const ConvArgs& a, int grid, hipStream_t st) {
+    with_stats_epi(a.stats != nullptr, epilogue_of(a), [&](auto stats, auto epi) { launch_c3<C, decltype(epi)::value, decltype(stats)::value>(a, grid, st); });
 }
 
 }  // namespace
 
-
-// Shape test shared by the launcher and the statistics-slab query (the two must agree on who writes the slabs).
-static bool conv3x3_shape_ok(int C, int K, int R, int S, int stride, int pad, int H, int W, int dtype) {
+// The shape is this kernel's (hdyolo_internal.h, ConvPlan): variant = input channels, one statistics slab per workgroup.
+bool hdy_conv3x3_c64_plan(const ConvShape& s, ConvPlan* p) {
     const bool disabled = hdy_opt(HDY_OPT_NO_CONV3X3) != 0;      // tests: force the generic kernel for A/B comparison
-    return !disabled && dtype == HDY_BF16 && R == 3 && S == 3 && stride == 1 && pad == 1 && (C == 64 || C == 32) && K <= 64 && K % 8 == 0 && H % TH == 0 &&
-           W % TW == 0;
+    if (disabled || s.dtype != HDY_BF16 || !conv_is(s, 3, 1, 1) || (s.C != 64 && s.C != 32) || s.K > 64 || s.K % 8 || s.H % TH || s.W % TW) return false;
+    const int tiles = s.N * (s.H / TH) * (s.W / TW), g = hdy_opt(HDY_OPT_C3_GRID);
+    const int cap = g ? g : (s.C == 32 ? 768 : 512);     // two 61 KB (C = 64) or three 39 KB (C = 32) 4-wave workgroups per CU
+    const int grid = tiles < cap ? tiles : cap;
+    *p = ConvPlan{CONV_3X3_C64, s.C, grid, grid, 0, 0};
+    return true;
 }
 
-static int conv3x3_grid(int tiles, int C) {
-    const int g = hdy_opt(HDY_OPT_C3_GRID);
-    const int cap = g ? g : (C == 32 ? 768 : 512);       // two 61 KB (C = 64) or three 39 KB (C = 32) 4-wave workgroups per CU
-    return tiles < cap ? tiles : cap;
-}
-
-// Number of statistic slabs the filter-resident kernel writes for this shape (one per workgroup), 0 = not eligible.
-int hdy_conv3x3_c64_slabs(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype) {
-    if (!conv3x3_shape_ok(C, K, R, S, stride, pad, H, W, dtype)) return 0;
-    return conv3x3_grid(N * (H / TH) * (W / TW), C);
-}
-
-// Returns 1 and launches when the shape qualifies; 0 = not eligible (caller falls back to the generic kernel); <0 / >0 = error.
-int hdy_conv3x3_c64_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc) {
-    if (dtype != HDY_BF16 || out_f32 || a.act > 1) return 0;
-    if (!(a.TH == 3 && a.TW == 3 && a.ih_mul == 1 && a.iw_mul == 1 && a.dh0 == -1 && a.dw0 == -1 && a.dense_out && !a.span_pixels)) return 0;
-    if (!(a.Hin == a.Ho && a.Win == a.Wo && conv3x3_shape_ok(a.C, a.K, 3, 3, 1, 1, a.Ho, a.Wo, dtype))) return 0;
-    const bool aligned = a.ldx % 8 == 0 && a.ldy % 8 == 0 && ((uintptr_t)a.y & 15) == 0 && ((uintptr_t)a.x & 15) == 0 &&
-                         (!a.res || (a.ldr % 8 == 0 && ((uintptr_t)a.res & 15) == 0));
-    if (!aligned) {
-        if (!a.stats) return 0;
-        // the caller sized the slab array with hdy_conv_stat_slabs for THIS kernel: falling back would write a different count
-        hdy_set_error("conv3x3_c64: statistics requested but x/y/res rows are not 16-byte aligned (ldx=%d ldy=%d)", a.ldx, a.ldy);
-        *rc = HDY_EINVAL;
-        return 1;
-    }
-    const int grid = conv3x3_grid(a.N * (a.Ho / TH) * (a.Wo / TW), a.C);
-    HDY_STAT_CAP(a, grid, "conv3x3_c64")
-    const int epi = a.act == 1 ? 2 : ((a.scale || a.shift) ? 1 : 0);
-    if (a.C == 32) launch_c3_c<32>(a, grid, epi, st);
-    else launch_c3_c<64>(a, grid, epi, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        hdy_set_error("conv3x3_c64: launch failed: %s", hipGetErrorString(e));
-        *rc = (int)e;
-        return 1;
-    }
-    *rc = HDY_OK;
-    return 1;
+int hdy_conv3x3_c64_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st) {
+    if (out_f32 || a.act > 1) return HDY_CONV_DECLINE;
+    if (const int rc = hdy_conv_take(a, p, rows_aligned(a, false), "conv3x3_c64")) return rc;
+    if (p.variant == 32) launch_c3_c<32>(a, p.grid, st);
+    else launch_c3_c<64>(a, p.grid, st);
+    return hdy_launch_status("conv3x3_c64");
 }

@@ -19,7 +19,7 @@
 // staging writes keyed by the row, 16-byte row stores of 128 contiguous bytes per pixel, residual / accumulate on the way out, BatchNorm sums in registers
 // across all of a workgroup's items, one slab per workgroup pair) is conv3x3.hip's.
 //
-// Requirements (checked by the launcher, otherwise the deep-pipelined / generic kernel runs): bf16 in / out, C == 128, K <= 128 and K % 8 == 0, R = S = 3,
+// Requirements (hdy_conv3x3_c128_plan for the shape, hdy_conv3x3_c128_launch for the pointers; otherwise the next family of conv_fwd_plan runs): bf16 in / out, C == 128, K <= 128 and K % 8 == 0, R = S = 3,
 // stride 1, pad 1, H % 8 == 0, W % 8 == 0, 16-byte aligned rows.
 //
 // Reference semantics replaced: nn.Conv2d(k = 3, s = 1, p = 1) inside metayolo/models/layers.py:92-93 (Bottleneck.cv2) and its autograd backward-data
@@ -34,11 +34,6 @@
 __device__ uint4 g_hdy_zero16_c128[4];   // zero page for out-of-image patch pixels
 
 namespace {
-
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
-                                     (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
-}
 
 constexpr int NTHR = 256;
 constexpr int C = 128, CB = C * 2, CPP = C / 8, KS = C / 32;          // 256-byte pixel rows, 16 chunks, 4 k-steps per tap
@@ -65,7 +60,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv3x3_c128_kernel(const ConvArgs p)
     const int tiles_total = p.N * per_img;
     const int nkh = (p.K + KH - 1) / KH;                                 // channel halves (1 or 2)
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
-    const int kh = wg % nkh, strm = wg / nkh, nstrm = (int)gridDim.x / nkh;     // grid % nkh == 0 (launcher)
+    const int kh = wg % nkh, strm = wg / nkh, nstrm = (int)gridDim.x / nkh;     // grid % nkh == 0 (hdy_conv3x3_c128_plan)
     const int k0 = kh * KH;
     const int nitems = strm < tiles_total ? (tiles_total - strm + nstrm - 1) / nstrm : 0;
 
@@ -290,58 +285,21 @@ static void launch_c128(const ConvArgs& a, int grid, hipStream_t st) {
 
 }  // namespace
 
-static bool c128_shape_ok(int Cin, int K, int R, int S, int stride, int pad, int H, int W, int dtype) {
-    return !hdy_opt(HDY_OPT_NO_CONV3X3_C128) && dtype == HDY_BF16 && R == 3 && S == 3 && stride == 1 && pad == 1 && Cin == C && K <= 2 * KH && K % 8 == 0 &&
-           H % TH == 0 && W % TW == 0;
-}
-
-// workgroups: two resident per CU; a multiple of the channel halves; never more than (tiles x halves)
-static int c128_grid(long long tiles, int K) {
-    const int nkh = (K + KH - 1) / KH;
+// The shape is this kernel's (hdyolo_internal.h, ConvPlan).  Workgroups: two resident per CU; a multiple of the channel halves; never more than
+// (tiles x halves).  One statistics slab per workgroup stream = grid / channel halves.
+bool hdy_conv3x3_c128_plan(const ConvShape& s, ConvPlan* p) {
+    if (hdy_opt(HDY_OPT_NO_CONV3X3_C128) || s.dtype != HDY_BF16 || !conv_is(s, 3, 1, 1) || s.C != C || s.K > 2 * KH || s.K % 8 || s.H % TH || s.W % TW) return false;
+    const int nkh = (s.K + KH - 1) / KH;
+    const long long tiles = (long long)s.N * (s.H / TH) * (s.W / TW);
     long long g = 512 / nkh * nkh;
     if (g > tiles * nkh) g = tiles * nkh;
-    return (int)g;
+    *p = ConvPlan{CONV_3X3_C128, 0, (int)g, (int)g / nkh, 0, 0};
+    return true;
 }
 
-// statistic slabs this kernel writes (one per workgroup stream = grid / channel halves); 0 = not its shape
-int hdy_conv3x3_c128_slabs(int N, int H, int W, int Cin, int K, int R, int S, int stride, int pad, int dtype) {
-    if (!c128_shape_ok(Cin, K, R, S, stride, pad, H, W, dtype)) return 0;
-    const int nkh = (K + KH - 1) / KH;
-    return c128_grid((long long)N * (H / TH) * (W / TW), K) / nkh;
-}
-
-// Returns 1 and launches when the shape qualifies; 0 = not eligible (the caller goes on to the deep-pipelined / generic kernel).
-int hdy_conv3x3_c128_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc) {
-    if (dtype != HDY_BF16 || out_f32 || a.act > 1) return 0;
-    if (!(a.TH == 3 && a.TW == 3 && a.ih_mul == 1 && a.iw_mul == 1 && a.dh0 == -1 && a.dw0 == -1 && a.dense_out && !a.span_pixels)) return 0;
-    if (!(a.Hin == a.Ho && a.Win == a.Wo && c128_shape_ok(a.C, a.K, 3, 3, 1, 1, a.Ho, a.Wo, dtype))) return 0;
-    const bool aligned = a.ldx % 8 == 0 && a.ldy % 8 == 0 && ((uintptr_t)a.y & 15) == 0 && ((uintptr_t)a.x & 15) == 0 &&
-                         (!a.res || (a.ldr % 8 == 0 && ((uintptr_t)a.res & 15) == 0));
-    if (!aligned) {
-        if (!a.stats) return 0;
-        hdy_set_error("conv3x3_c128: statistics requested but x/y/res rows are not 16-byte aligned (ldx=%d ldy=%d)", a.ldx, a.ldy);
-        *rc = HDY_EINVAL;
-        return 1;
-    }
-    const int nkh = (a.K + KH - 1) / KH;
-    const int grid = c128_grid((long long)a.N * (a.Ho / TH) * (a.Wo / TW), a.K);
-    HDY_STAT_CAP(a, grid / nkh, "conv3x3_c128")
-    const int epi = a.act == 1 ? 2 : ((a.scale || a.shift) ? 1 : 0);
-    if (a.stats) {
-        if (epi == 2) launch_c128<2, true>(a, grid, st);
-        else if (epi == 1) launch_c128<1, true>(a, grid, st);
-        else launch_c128<0, true>(a, grid, st);
-    } else {
-        if (epi == 2) launch_c128<2, false>(a, grid, st);
-        else if (epi == 1) launch_c128<1, false>(a, grid, st);
-        else launch_c128<0, false>(a, grid, st);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        hdy_set_error("conv3x3_c128: launch failed: %s", hipGetErrorString(e));
-        *rc = (int)e;
-        return 1;
-    }
-    *rc = HDY_OK;
-    return 1;
+int hdy_conv3x3_c128_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st) {
+    if (out_f32 || a.act > 1) return HDY_CONV_DECLINE;
+    if (const int rc = hdy_conv_take(a, p, rows_aligned(a, false), "conv3x3_c128")) return rc;
+    with_stats_epi(a.stats != nullptr, epilogue_of(a), [&](auto stats, auto epi) { launch_c128<decltype(epi)::value, decltype(stats)::value>(a, p.grid, st); });
+    return hdy_launch_status("conv3x3_c128");
 }

@@ -16,8 +16,8 @@
 //   * patch row q serves output row a = q / 2 with filter row 0 and a - 1 with filter row 2 (q even), or a = (q - 1) / 2 with filter row 1.
 // Epilogue, BatchNorm sums (one slab per workgroup) and the store phase are conv3x3.hip's.
 //
-// Requirements (checked by the launcher, otherwise the generic kernel runs): bf16 in / out, C == 32, K <= 64 and a multiple of 8, R = S = 3,
-// stride 2, pad 1, even H and W, Ho % 4 == 0, Wo % 16 == 0, 16-byte aligned rows.
+// Requirements (hdy_conv3x3s2_plan for the shape, hdy_conv3x3s2_launch for the pointers; otherwise the next family of conv_fwd_plan runs):
+// bf16 in / out, C == 32, K <= 64 and a multiple of 8, R = S = 3, stride 2, pad 1, even H and W, Ho % 4 == 0, Wo % 16 == 0, 16-byte aligned rows.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -46,31 +46,12 @@ template <int NP, int NWV> struct Geo {
     static_assert(NTHR / CPRW == 32, "32 staged rows per store pass");
 };
 
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g, (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
-}
-
 // EPI: 0 = raw convolution out (train-mode forward), 1 = scale/shift, 2 = scale/shift + SiLU;  STATS: BatchNorm partial sums (one slab per workgroup)
 // LDS fragment / staging reads as inline asm and raw barriers (round 5; see conv_dgrad_s2.hip): hipcc puts `s_waitcnt vmcnt(0)` in front of every
 // compiler-visible LDS read that may alias a pending LDS-DMA and into `__syncthreads()` — the next patch's DMA was waited for at the tile's first fragment
 // read and the tile's output stores at the barrier behind them.  The waits that are needed are counted by hand.
 // HAND (= NP == 2) selects that form; the one-plane instance keeps compiler-visible reads and `__syncthreads()`: three of its workgroups share a CU and
 // cover each other's waits, and the hand-counted form measured slower there (133 against 124 us).
-#define S2_LDSR(dst, addr)                                                                             \
-    do {                                                                                               \
-        if constexpr (HAND) asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");    \
-        else dst = *(const i32x4*)(smem + ((addr) - lds0));                                            \
-    } while (0)
-#define S2_LGKM(n)                                                                                                       \
-    do {                                                                                                                 \
-        if constexpr (HAND) { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n) : "memory"); __builtin_amdgcn_sched_barrier(0); } \
-    } while (0)
-#define S2_BARRIER(lg)                                                                                                   \
-    do {                                                                                                                 \
-        if constexpr (HAND) { if (lg) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } \
-        else __syncthreads();                                                                                            \
-    } while (0)
-
 template <int NP, int NWV, int EPI, bool STATS>
 __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 3 : 2) void conv3x3s2_kernel(const ConvArgs p) {
     using G = Geo<NP, NWV>;
@@ -292,68 +273,29 @@ static void launch_s2(const ConvArgs& a, int grid, hipStream_t st) {
 }
 
 template <int NP, int NWV>
-static void launch_s2_epi(const ConvArgs& a, int grid, int epi, hipStream_t st) {
-    if (a.stats) {
-        if (epi == 2) launch_s2<NP, NWV, 2, true>(a, grid, st);
-        else if (epi == 1) launch_s2<NP, NWV, 1, true>(a, grid, st);
-        else launch_s2<NP, NWV, 0, true>(a, grid, st);
-    } else {
-        if (epi == 2) launch_s2<NP, NWV, 2, false>(a, grid, st);
-        else if (epi == 1) launch_s2<NP, NWV, 1, false>(a, grid, st);
-        else launch_s2<NP, NWV, 0, false>(a, grid, st);
-    }
+static void launch_s2_epi(const ConvArgs& a, int grid, hipStream_t st) {
+    with_stats_epi(a.stats != nullptr, epilogue_of(a), [&](auto stats, auto epi) { launch_s2<NP, NWV, decltype(epi)::value, decltype(stats)::value>(a, grid, st); });
 }
 
 }  // namespace
 
-// planes of the instance that takes the shape: 1 = <1, 4> (32 -> <= 64), 2 = <2, 8> (64 -> 72..128), 0 = not eligible
-static int conv3x3s2_planes(int Cin, int K, int R, int S, int stride, int pad, int H, int W, int dtype) {
+// The shape is this kernel's (hdyolo_internal.h, ConvPlan): variant = planes of the instance, 1 = <1, 4> (32 -> <= 64), 2 = <2, 8> (64 -> 72..128).
+// One-plane form: three 46 KB, 4-wave workgroups per CU; two-plane form: one 93 KB, 8-wave workgroup.  One statistics slab per workgroup.
+bool hdy_conv3x3s2_plan(const ConvShape& s, ConvPlan* p) {
     const int disabled = hdy_opt(HDY_OPT_NO_CONV3X3S2);     // tests: 1 forces the generic kernel for A/B comparison, 2 only for the two-plane (64 -> 128) form
-    if (disabled == 1 || dtype != HDY_BF16 || R != 3 || S != 3 || stride != 2 || pad != 1 || K % 8 || H % 2 || W % 2 || (H / 2) % TH || (W / 2) % TW) return 0;
-    if (Cin == 32 && K <= 64) return 1;
-    if (Cin == 64 && K > 64 && K <= 128 && disabled != 2) return 2;
-    return 0;
+    if (disabled == 1 || s.dtype != HDY_BF16 || !conv_is(s, 3, 2, 1) || s.K % 8 || s.H % 2 || s.W % 2 || (s.H / 2) % TH || (s.W / 2) % TW) return false;
+    const int planes = (s.C == 32 && s.K <= 64) ? 1 : ((s.C == 64 && s.K > 64 && s.K <= 128 && disabled != 2) ? 2 : 0);
+    if (!planes) return false;
+    const int tiles = s.N * (s.H / 2 / TH) * (s.W / 2 / TW), cap = planes == 1 ? 768 : 256;
+    const int grid = tiles < cap ? tiles : cap;
+    *p = ConvPlan{CONV_3X3S2, planes, grid, grid, 0, 0};
+    return true;
 }
 
-// one-plane form: three 46 KB, 4-wave workgroups per CU; two-plane form: one 93 KB, 8-wave workgroup
-static int conv3x3s2_grid(int planes, int tiles) {
-    const int cap = planes == 1 ? 768 : 256;
-    return tiles < cap ? tiles : cap;
-}
-
-// Number of statistic slabs this kernel writes for the shape (one per workgroup), 0 = not eligible.
-int hdy_conv3x3s2_c32_slabs(int N, int H, int W, int Cin, int K, int R, int S, int stride, int pad, int dtype) {
-    const int planes = conv3x3s2_planes(Cin, K, R, S, stride, pad, H, W, dtype);
-    if (!planes) return 0;
-    return conv3x3s2_grid(planes, N * (H / 2 / TH) * (W / 2 / TW));
-}
-
-// Returns 1 and launches when the shape qualifies; 0 = not eligible (caller falls back to the generic kernel); <0 / >0 in *rc = error.
-int hdy_conv3x3s2_c32_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc) {
-    if (dtype != HDY_BF16 || out_f32 || a.act > 1) return 0;
-    if (!(a.TH == 3 && a.TW == 3 && a.ih_mul == 2 && a.iw_mul == 2 && a.dh0 == -1 && a.dw0 == -1 && a.dense_out && !a.span_pixels)) return 0;
-    const int planes = (a.Hin == 2 * a.Ho && a.Win == 2 * a.Wo) ? conv3x3s2_planes(a.C, a.K, 3, 3, 2, 1, a.Hin, a.Win, dtype) : 0;
-    if (!planes) return 0;
-    const bool aligned = a.ldx % 8 == 0 && a.ldy % 8 == 0 && ((uintptr_t)a.y & 15) == 0 && ((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0 &&
-                         a.Kdp % 8 == 0 && (!a.res || (a.ldr % 8 == 0 && ((uintptr_t)a.res & 15) == 0));
-    if (!aligned) {
-        if (!a.stats) return 0;
-        // the caller sized the slab array with hdy_conv_stat_slabs for THIS kernel: falling back would write a different count
-        hdy_set_error("conv3x3s2: statistics requested but x/y/res rows are not 16-byte aligned (ldx=%d ldy=%d)", a.ldx, a.ldy);
-        *rc = HDY_EINVAL;
-        return 1;
-    }
-    const int grid = conv3x3s2_grid(planes, a.N * (a.Ho / TH) * (a.Wo / TW));
-    HDY_STAT_CAP(a, grid, "conv3x3s2")
-    const int epi = a.act == 1 ? 2 : ((a.scale || a.shift) ? 1 : 0);
-    if (planes == 1) launch_s2_epi<1, 4>(a, grid, epi, st);
-    else launch_s2_epi<2, 8>(a, grid, epi, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        hdy_set_error("conv3x3s2: launch failed: %s", hipGetErrorString(e));
-        *rc = (int)e;
-        return 1;
-    }
-    *rc = HDY_OK;
-    return 1;
+int hdy_conv3x3s2_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st) {
+    if (out_f32 || a.act > 1) return HDY_CONV_DECLINE;
+    if (const int rc = hdy_conv_take(a, p, rows_aligned(a, true), "conv3x3s2")) return rc;
+    if (p.variant == 1) launch_s2_epi<1, 4>(a, p.grid, st);
+    else launch_s2_epi<2, 8>(a, p.grid, st);
+    return hdy_launch_status("conv3x3s2");
 }

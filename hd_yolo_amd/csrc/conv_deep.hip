@@ -60,12 +60,6 @@ namespace {
 constexpr int NTHR = 512;
 constexpr int UNIT = 16384;
 
-__device__ __forceinline__ unsigned fdiv(unsigned n, unsigned mg, int sh) { return __umulhi(n << 1, mg) >> sh; }
-
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, unsigned lds_byte) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (void __attribute__((address_space(3)))*)(uintptr_t)lds_byte, 16, (int)voff, (int)soff, 0, 0);
-}
-
 #define DP_READ(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
 #define DP_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 
@@ -661,21 +655,6 @@ int deep_launch_epi(const ConvArgs& a, int grid, hipStream_t st) {
     return deep_launch<BN, STATS, 0>(a, grid, st);
 }
 
-// shapes the deep kernel takes; bn_out: its column tile.  `stats`: the launch writes BatchNorm slabs (128-wide instances only).
-// First version (fragments read at the top of a phase): 1x1 layers 5-17 % faster than conv_igemm.hip, 3x3 layers 3-8 % slower.  With the
-// fragments read one segment ahead: yolov5s train step 12.37 -> 12.17 ms, yolov5l inference network 56.0 -> 49.6 ms with every eligible
-// layer here (HDY_DEEP_ALL = 0 keeps the multi-tap layers on the generic kernel).
-bool deep_shape_ok(long long M, int C, int K, int taps, bool pointwise, bool stats, int* bn_out, int classes = 1) {
-    if (hdy_opt(HDY_OPT_NO_DEEP)) return false;
-    if (!pointwise && !hdy_opt(HDY_OPT_DEEP_ALL)) return false;
-    if (C % 64 != 0 || K < 128 || K % 8 != 0) return false;
-    const int bn = stats ? 128 : deep_bn(M, K);
-    const long long tiles = (M + 255) / 256 * cdiv(K, bn) * classes;
-    if (tiles < hdy_opt(HDY_OPT_DEEP_MIN_TILES)) return false;     // too few 256-row tiles for 256 CUs: the 128-row kernel spreads wider
-    if (bn_out) *bn_out = bn;
-    return true;
-}
-
 }  // namespace
 
 // measurement only (not part of the C ABI header): copies the stamp table of the last HDY_DEEP_DEBUG & 32 launch to the host
@@ -689,34 +668,38 @@ extern "C" int hdy_deep_debug_read_segments(unsigned long long* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_deep_seg), sizeof(unsigned long long) * 256 * 16);
 }
 
-// statistic slabs a deep-kernel forward writes (one per workgroup position); 0: the shape is not the deep kernel's
-int hdy_conv_deep_slabs(long long M, int C, int K, int taps, int pointwise, int dtype) {
-    int bn = 0;
-    if (dtype != HDY_BF16 || !deep_shape_ok(M, C, K, taps, pointwise != 0, true, &bn)) return 0;
-    const int ntiles = cdiv(K, bn);
-    return deep_grid(M, ntiles) / ntiles;
-}
-
-// called by hdy_conv_igemm_launch after its own validation (a.M, a.Kdp, a.pointwise, union tap window, reciprocals are set)
-int hdy_conv_deep_try(const ConvArgs& a_in, int dtype, int out_f32, hipStream_t st, int* rc) {
-    const bool walk = a_in.ncls > 1;                               // the four-class stride-2 data gradient (validated by the caller)
-    if (dtype != HDY_BF16 || out_f32 || a_in.nstat > 0 || (!a_in.dense_out && !walk) || a_in.span_pixels || !a_in.vec_out || !a_in.utap) return 0;
+// The shape is this kernel's (hdyolo_internal.h, ConvPlan): bn = its column tile (a launch that writes BatchNorm slabs: the 128-wide instances
+// only), one statistics slab per workgroup position.  s.ncls == 4: the four-class stride-2 data gradient.
+// First version (fragments read at the top of a phase): 1x1 layers 5-17 % faster than conv_igemm.hip, 3x3 layers 3-8 % slower.  With the
+// fragments read one segment ahead: yolov5s train step 12.37 -> 12.17 ms, yolov5l inference network 56.0 -> 49.6 ms with every eligible
+// layer here (HDY_DEEP_ALL = 0 keeps the multi-tap layers on the generic kernel).
+bool hdy_conv_deep_plan(const ConvShape& s, ConvPlan* p) {
+    const bool walk = s.ncls > 1;
+    if (hdy_opt(HDY_OPT_NO_DEEP) || s.dtype != HDY_BF16 || s.stem || (!s.dense && !walk)) return false;
+    if (!conv_is(s, 1, 1, 0) && !hdy_opt(HDY_OPT_DEEP_ALL)) return false;
+    if (s.C % 64 != 0 || s.K < 128 || s.K % 8 != 0) return false;
     // measured at the yolov5s bench shapes (B = 64, scripts/probes/dgrad_walk.py): 105 / 80 / 62 / 48 us here against 94 / 86 / 59 / 51 us for
     // conv_igemm.hip's 128-row walk, and 12.37-12.45 against 12.30 ms in the train step.  Opt-in.
     // HDY_DEEP_WALK: 0 never, 1 always, 2 (default) where it measured faster: 256 or more gradient channels out (256<-512 @40x40 80.5 vs 85.9 us, 256<-256 47.5 vs 51.1)
-    if (walk && (hdy_opt(HDY_OPT_DEEP_WALK) == 0 || (hdy_opt(HDY_OPT_DEEP_WALK) == 2 && a_in.K < 256))) return 0;
-    int bn = 0;
-    if (!deep_shape_ok(a_in.M, a_in.C, a_in.K, a_in.TH * a_in.TW, a_in.pointwise != 0, a_in.stats != nullptr, &bn, walk ? 4 : 1)) return 0;
-    if (a_in.ldx % 8 != 0) return 0;
+    if (walk && (hdy_opt(HDY_OPT_DEEP_WALK) == 0 || (hdy_opt(HDY_OPT_DEEP_WALK) == 2 && s.K < 256))) return false;
+    const long long M = conv_pixels(s);
+    const int bn = s.stats ? 128 : deep_bn(M, s.K), ntiles = cdiv(s.K, bn);
+    if ((M + 255) / 256 * ntiles * (walk ? 4 : 1) < hdy_opt(HDY_OPT_DEEP_MIN_TILES)) return false;     // too few 256-row tiles for 256 CUs: the 128-row kernel spreads wider
+    const int grid = deep_grid(M, ntiles);
+    *p = ConvPlan{CONV_DEEP, walk, grid, grid / ntiles, bn, 0};
+    return true;
+}
+
+// called by hdy_conv_launch after its validation (a.M, a.Kdp, a.pointwise, union tap window, reciprocals are set)
+int hdy_conv_deep_launch(const ConvArgs& a_in, const ConvPlan& p, int out_f32, hipStream_t st) {
+    if (const int rc = hdy_conv_take(a_in, p, !out_f32 && a_in.vec_out && a_in.ldx % 8 == 0, "conv_deep")) return rc;
+    const bool walk = p.variant != 0;
     ConvArgs a = a_in;
     a.dbg = hdy_opt(HDY_OPT_DEEP_DEBUG);
-    a.ntiles = cdiv(a.K, bn);
+    a.ntiles = cdiv(a.K, p.bn);
     // a.bn stays the PACKING tile (rows of the packed filter block are padded to it)
-    const int grid = deep_grid(a.M, a.ntiles);
-    HDY_STAT_CAP(a, grid / a.ntiles, "conv_deep")
-    hdy_note_dispatch(bn == 256 ? (walk ? "deep_256x256_walk" : "deep_256x256") : (walk ? "deep_256x128_walk" : "deep_256x128"));
-    if (bn == 256) *rc = deep_launch_epi<256, false>(a, grid, st);
-    else if (a.stats) *rc = deep_launch_epi<128, true>(a, grid, st);
-    else *rc = deep_launch_epi<128, false>(a, grid, st);
-    return 1;
+    hdy_note_dispatch(p.bn == 256 ? (walk ? "deep_256x256_walk" : "deep_256x256") : (walk ? "deep_256x128_walk" : "deep_256x128"));
+    if (p.bn == 256) return deep_launch_epi<256, false>(a, p.grid, st);
+    if (a.stats) return deep_launch_epi<128, true>(a, p.grid, st);
+    return deep_launch_epi<128, false>(a, p.grid, st);
 }

@@ -54,31 +54,12 @@ template <int NP, int NCG, int TH> struct Geo {
     static_assert(SPASS == 8 && RPP % RPH == 0 && PPIX <= 153, "geometry");
 };
 
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g, (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
-}
-
 // LDS fragment reads as inline asm and raw barriers: hipcc puts `s_waitcnt vmcnt(0)` in front of every compiler-visible LDS read that may alias a pending
 // LDS-DMA, and `__syncthreads()` waits for vmcnt(0) too — the next patch's DMA (issued in front of the MFMAs) was waited for at the first fragment
 // read, and the tile's output stores at the barrier behind them: patch loads, MFMAs and stores ran back to back (18 + 44 + 30 = 92 us on the 64 <- 128
 // layer, profiles/r05_dgrad_s2_k128c64.txt).  The reads the compiler cannot see do not trigger the wait; the waits that ARE needed are counted by hand.
 // HAND (= NP == 2) selects that form; the one-plane instance keeps compiler-visible reads and `__syncthreads()`: with its smaller footprint two / three
 // workgroups share a CU and cover each other's waits, and the hand-counted form measured 3-8 % slower there (120-128 against 116-118 us).
-#define S2_LDSR(dst, addr)                                                                             \
-    do {                                                                                               \
-        if constexpr (HAND) asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");    \
-        else dst = *(const i32x4*)(smem + ((addr) - lds0));                                            \
-    } while (0)
-#define S2_LGKM(n)                                                                                                       \
-    do {                                                                                                                 \
-        if constexpr (HAND) { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(n) : "memory"); __builtin_amdgcn_sched_barrier(0); } \
-    } while (0)
-#define S2_BARRIER(lg)                                                                                                   \
-    do {                                                                                                                 \
-        if constexpr (HAND) { if (lg) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } \
-        else __syncthreads();                                                                                            \
-    } while (0)
-
 template <int NP, int NCG, int TH, int ABL = 0>      // ABL: timing ablations (results wrong): 1 no patch loads after the first, 4 no MFMAs, 8 no stores
 __global__ __launch_bounds__(64 * NCG * (TH / 4), 2) void dgrad3x3s2_kernel(const ConvArgs p) {
     using G = Geo<NP, NCG, TH>;

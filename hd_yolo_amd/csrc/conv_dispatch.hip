@@ -1,0 +1,119 @@
+// Kernel selection and launch of the convolution forward / data-gradient families (host code only).
+//
+// conv_fwd_plan() is the one ordered walk over the families: each family's <name>_plan (in its own file) says whether a ConvShape is
+// its own and, if so, with which instance, grid and statistic-slab count.  The sizing query (hdy_conv_stat_slabs) and the launch
+// (hdy_conv_launch) below both read that plan, so the slab array a caller sized is the one the kernel about to start writes.
+#include "common.h"
+#include "hdyolo_internal.h"
+#include "hdyolo.h"
+
+// the plan of the first family from `first` on that takes the shape
+static ConvPlan conv_fwd_plan(const ConvShape& s, int first = CONV_STEM) {
+    ConvPlan p = {};
+    if (first <= CONV_STEM && hdy_conv_stem_plan(s, &p)) return p;                // patch-resident 6x6/s2 stem
+    if (first <= CONV_3X3_C64 && hdy_conv3x3_c64_plan(s, &p)) return p;           // filter-resident 3x3, 32 / 64 input channels
+    if (first <= CONV_3X3_C128 && hdy_conv3x3_c128_plan(s, &p)) return p;         // ... its 128-input-channel form
+    if (first <= CONV_3X3S2 && hdy_conv3x3s2_plan(s, &p)) return p;               // patch-resident 3x3 / stride 2
+    if (first <= CONV_DEEP && hdy_conv_deep_plan(s, &p)) return p;                // deep-pipelined 256-row implicit GEMM (C % 64 == 0, K >= 128)
+    hdy_conv_igemm_plan(s, &p);                                                   // generic implicit GEMM: takes everything
+    return p;
+}
+
+extern "C" int hdy_conv_stat_slabs(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype) {
+    const int stem = C == 3 && R == 6 && S == 6 && stride == 2 && pad == 2;
+    return conv_fwd_plan(conv_shape(N, H, W, C, K, R, S, stride, pad, dtype, stem, 1)).slabs;
+}
+
+static int launch_planned(const ConvArgs& a, const ConvPlan& p, int dtype, int out_f32, hipStream_t st) {
+    switch (p.family) {
+        case CONV_STEM: return hdy_conv_stem_launch(a, p, out_f32, st);
+        case CONV_3X3_C64: return hdy_conv3x3_c64_launch(a, p, out_f32, st);
+        case CONV_3X3_C128: return hdy_conv3x3_c128_launch(a, p, out_f32, st);
+        case CONV_3X3S2: return hdy_conv3x3s2_launch(a, p, out_f32, st);
+        case CONV_DEEP: return hdy_conv_deep_launch(a, p, out_f32, st);
+        default: return hdy_conv_igemm_launch(a, p, dtype, out_f32, st);
+    }
+}
+
+// The layer a validated ConvArgs describes, derived in this one place.  A forward launch gives back what hdy_conv_fwd was called with; a
+// stride-1 data gradient is the convolution with C and K swapped and pad' = R - 1 - pad; a parity class of a stride-2 data gradient has no
+// such description (pad = -1) and only the implicit-GEMM families take it.
+static ConvShape shape_of(const ConvArgs& a, int dtype) {
+    ConvShape s = {};
+    s.N = a.N; s.H = a.Hin; s.W = a.Win; s.Ho = a.Ho; s.Wo = a.Wo; s.C = a.C; s.K = a.K; s.R = a.TH; s.S = a.TW; s.stride = a.ih_mul;
+    s.pad = -1; s.dense = a.dense_out; s.dtype = dtype; s.stats = a.stats != nullptr; s.ncls = a.ncls > 1 ? 4 : 1;
+    if (a.span_pixels) {                      // hdy_conv_fwd's stem: six row taps over the 24 pseudo channels of the padded 4-channel image
+        s.stem = 1; s.H = a.Hin - 4; s.W = a.Win - 4; s.C = 3; s.R = s.S = 6; s.stride = 2; s.pad = 2;
+    } else if (a.ncls <= 1 && a.dense_out && a.ih_mul == a.iw_mul && a.dh0 == a.dw0 && a.dh0 <= 0 && a.Ho == conv_out_dim(a.Hin, a.TH, a.ih_mul, -a.dh0) &&
+               a.Wo == conv_out_dim(a.Win, a.TW, a.iw_mul, -a.dw0)) {
+        s.pad = -a.dh0;
+    }
+    return s;
+}
+
+// Host-side validation + dispatch shared by the C-ABI entry points (api.hip).
+int hdy_conv_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st) {
+    const int VE = dtype == HDY_BF16 ? 8 : 4;
+    HDY_ARG(a.x && a.w && a.y, "conv: null pointer");
+    HDY_ARG(a.N > 0 && a.Hin > 0 && a.Win > 0 && a.Ho > 0 && a.Wo > 0 && a.K > 0 && a.C > 0, "conv: non-positive dim");
+    HDY_ARG(a.C % VE == 0, "conv: C=%d must be a multiple of %d for this dtype", a.C, VE);
+    HDY_ARG(a.ldx % (a.span_pixels ? 4 : VE) == 0 && (a.span_pixels || a.ldx >= a.C), "conv: ldx=%d must be >= C and a multiple of %d", a.ldx, VE);
+    HDY_ARG(a.ldy >= a.K, "conv: ldy=%d < K=%d", a.ldy, a.K);
+    HDY_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0, "conv: x/w must be 16-byte aligned");
+    HDY_ARG(a.TH > 0 && a.TW > 0, "conv: empty tap window");
+    HDY_ARG(a.Hin < 24000 && a.Win < 24000 && a.TH < 64 && a.TW < 64 && a.dh0 > -4000 && a.dw0 > -4000, "conv: image side beyond the loader's 16-bit coordinates");
+    HDY_ARG((long long)a.N * a.Hin * a.Win < (1LL << 31) && (long long)a.N * a.Ho * a.Wo < (1LL << 31), "conv: too many pixels");
+    a.Kd = a.TH * a.TW * a.C;
+    const int BKE = 8 * VE;
+    a.bn = hdy_conv_bn_tile(a.K);
+    HDY_ARG(a.Kdp == round_up(a.Kd, BKE), "conv: packed weight pitch %d != %d", a.Kdp, round_up(a.Kd, BKE));
+    a.M = a.N * a.Ho * a.Wo;
+    a.mtiles = cdiv(a.M, 128);
+    a.ntiles = cdiv(a.K, a.bn);
+    if (a.dense_out) HDY_ARG(a.oh_mul == 1 && a.ow_mul == 1 && a.oh_off == 0 && a.ow_off == 0 && a.Hout == a.Ho && a.Wout == a.Wo, "conv: dense_out geometry mismatch");
+    // 1x1 / stride 1 / no padding: input pixel == output pixel, no coordinate arithmetic in the loader
+    a.pointwise = (a.TH == 1 && a.TW == 1 && a.ih_mul == 1 && a.iw_mul == 1 && a.dh0 == 0 && a.dw0 == 0 && a.Hin == a.Ho && a.Win == a.Wo &&
+                   !a.span_pixels && a.ncls <= 1) ? 1 : 0;
+    if (a.ncls > 1) {
+        HDY_ARG(a.ncls == 4 && !a.dense_out && !a.stats, "conv: class walk is the four-class stride-2 dgrad");
+        for (int c = 0; c < 4; ++c) HDY_ARG(a.c_nkb[c] == round_up(a.c_TH[c] * a.c_TW[c] * a.C, BKE) / BKE, "conv: class %d k-blocks", c);
+    }
+    // coalesced 16-byte epilogue needs bf16 output, whole vectors and aligned rows
+    const bool bf16_out = dtype == HDY_BF16 && !out_f32;
+    a.vec_out = (bf16_out && a.K % 8 == 0 && a.ldy % 8 == 0 && ((uintptr_t)a.y & 15) == 0 &&
+                 (!a.res || (a.ldr % 8 == 0 && ((uintptr_t)a.res & 15) == 0))) ? 1 : 0;
+    if (a.nstat > 0) {
+        HDY_ARG(a.nstat <= 2 && a.vec_out && a.ntiles == 1 && a.bn <= 64 && !a.stats && !a.res, "conv: producer-side statistics need the bf16 vector epilogue and at most 64 output channels");
+        for (int r = 0; r < a.nstat; ++r) {
+            const StatReq& q = a.stat[r];
+            HDY_ARG(q.y && q.scale && q.shift && q.slabs && q.c0 >= 0 && q.c0 < q.c1 && q.c1 <= a.K && q.c0 % 8 == 0 && q.c1 % 8 == 0 &&
+                    q.ldy % 8 == 0 && (((uintptr_t)q.y | (uintptr_t)q.scale | (uintptr_t)q.shift) & 15) == 0,
+                    "conv: bad statistics request %d", r);
+        }
+    }
+    // loader geometry: union tap window over the classes, reciprocals for the row / chunk decompositions
+    a.uh0 = a.dh0; a.uw0 = a.dw0;
+    int uh1 = a.dh0 + a.TH, uw1 = a.dw0 + a.TW;
+    for (int c = 0; c < (a.ncls > 1 ? 4 : 0); ++c) {
+        a.uh0 = a.c_dh[c] < a.uh0 ? a.c_dh[c] : a.uh0; a.uw0 = a.c_dw[c] < a.uw0 ? a.c_dw[c] : a.uw0;
+        uh1 = a.c_dh[c] + a.c_TH[c] > uh1 ? a.c_dh[c] + a.c_TH[c] : uh1; uw1 = a.c_dw[c] + a.c_TW[c] > uw1 ? a.c_dw[c] + a.c_TW[c] : uw1;
+    }
+    a.UH = uh1 - a.uh0; a.UW = uw1 - a.uw0;
+    HDY_ARG(a.UH * a.UW <= 31, "conv: %d x %d tap window beyond the loader's 31 tap bits", a.UH, a.UW);
+    HDY_ARG(((long long)(a.UH + 1) * a.Win + a.UW) * a.ldx * (dtype == HDY_BF16 ? 2 : 4) < (1LL << 28), "conv: tap window spans too many bytes");
+    a.utap = a.C % BKE == 0 ? 1 : 0;
+    hdy_magic((unsigned)(a.Ho * a.Wo), &a.mg_howo, &a.sh_howo);
+    hdy_magic((unsigned)a.Wo, &a.mg_wo, &a.sh_wo);
+    hdy_magic((unsigned)a.C, &a.mg_c, &a.sh_c);
+    for (int c = 0; c < 4; ++c) hdy_magic((unsigned)(a.ncls > 1 ? a.c_TW[c] : a.TW), &a.mg_tw[c], &a.sh_tw[c]);
+    // Producer-side statistics (nstat) exist in the generic kernel only.  A family whose plan it is but whose kernel this call does not
+    // fit (hdy_conv_take) hands the launch to the families after it.
+    const ConvShape s = shape_of(a, dtype);
+    for (int first = a.nstat > 0 ? CONV_IGEMM : CONV_STEM;;) {
+        const ConvPlan p = conv_fwd_plan(s, first);
+        a.tile_interleave = p.interleave;
+        const int rc = launch_planned(a, p, dtype, out_f32, st);
+        if (rc != HDY_CONV_DECLINE) return rc;
+        first = p.family + 1;
+    }
+}

@@ -60,15 +60,6 @@ template <> __device__ __forceinline__ f32x4 mma16<float>(const V16& a, const V1
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
-// LDS-DMA through a buffer descriptor: lane l's 16 bytes at base + voff + soff land at lds + l*16; a lane whose offset fails the
-// descriptor's range check (>= num_records) gets zeros.
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (void __attribute__((address_space(3)))*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
-}
-
-// n / d for n < 2^31 with the host-made reciprocal of hdy_magic(): mulhi(2n, mg) >> sh
-__device__ __forceinline__ unsigned fdiv(unsigned n, unsigned mg, int sh) { return __umulhi(n << 1, mg) >> sh; }
-
 // BM x BN output tile, NTHR = 2*BM threads (BM/64 x 2 waves, each 64 x BN/2), NS-deep LDS ring of (A | B) stages.
 //   <128, *, 2>  4 waves, 2 stages: many small workgroups per CU (K <= 64, small problems)
 //   <256, *, 3>  8 waves (2 per SIMD), 3 stages with counted vmcnt: half the filter re-fetch per output, two k-blocks of
@@ -715,10 +706,6 @@ __global__ __launch_bounds__(2 * BM, (BM == 256 || BN == 128 || STAT) ? 2 : (BN 
     }
 }
 
-inline int igemm_interleave_mode() {      // bit 0: column tiles of one m-tile on neighbouring workgroups, bit 1: parity classes of the stride-2 dgrad too
-    return hdy_opt(HDY_OPT_TILE_INTERLEAVE);
-}
-
 // Persistent grid of a tile configuration: as many workgroups as stay resident (LDS-limited), never more than tiles.
 inline int igemm_grid(long long M, int ntiles, int BM, int BN, int NS) {
     const size_t smem = (size_t)NS * (BM * 128 + BN * 128) + (BN > 32 ? 2 * BN * sizeof(float) : 0);
@@ -739,22 +726,7 @@ inline bool igemm_big(long long M, int bn, int ntiles, int taps) {
 }
 
 template <typename T, typename OT, int BM, int BN, int NS, bool STAT = false>
-int launch(const ConvArgs& a, hipStream_t st) {
-    const int grid = igemm_grid(a.M, a.ntiles * (a.ncls > 1 ? 4 : 1), BM, BN, NS);
-    if (a.stats) {
-        // the kernel's own rule (wg_stats): one slab per workgroup position when the sums stay in registers across its tiles, else one per 128 rows
-        const bool wg = a.ntiles == 1 || ((a.tile_interleave & 1) && a.ncls <= 1 && grid % a.ntiles == 0);
-        long long writes = (a.M + 127) / 128;
-        if (wg && a.ntiles > 1) writes = grid / a.ntiles;
-        else if (wg) {
-            const long long tiles = (a.M + BM - 1) / BM, tpb = (tiles + grid - 1) / grid;
-            writes = (tiles + tpb - 1) / tpb;
-        }
-        HDY_ARG(a.stat_cap == writes, "conv: the statistics array holds %d slabs, this launch writes %lld (a kernel-selection option changed between "
-                "hdy_conv_stat_slabs and the launch?)", a.stat_cap, writes);
-    }
-    for (int r = 0; r < a.nstat; ++r)
-        HDY_ARG(a.stat[r].nslabs == grid, "conv: statistics request %d holds %d slabs, this launch writes %d", r, a.stat[r].nslabs, grid);
+int launch(const ConvArgs& a, int grid, hipStream_t st) {
     const size_t smem = (size_t)NS * (BM * 128 + BN * 128) + (BN > 32 ? 2 * BN * sizeof(float) : 0);
     static PerDeviceOnce attr_once;           // first launch of this instance on any thread
     attr_once.run([&] {
@@ -766,119 +738,51 @@ int launch(const ConvArgs& a, hipStream_t st) {
         hdy_note_dispatch(what);
     }
     hipLaunchKernelGGL((conv_igemm_kernel<T, OT, BM, BN, NS, STAT>), dim3(grid), dim3(2 * BM), smem, st, a);
-    HDY_LAUNCH_CHECK("conv_igemm");
-    return HDY_OK;
+    return hdy_launch_status("conv_igemm");
 }
 
 template <typename T, typename OT>
-int launch_bn(const ConvArgs& a, hipStream_t st) {
-    const bool big = a.ncls <= 1 && igemm_big(a.M, a.bn, a.ntiles, a.TH * a.TW);
+int launch_bn(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
     if constexpr (std::is_same<T, bf16_t>::value && std::is_same<OT, bf16_t>::value) {
         if (a.nstat > 0) {                         // producer-side BatchNorm-backward statistics (dgrad launches, <= 64 output channels)
-            if (a.bn == 32) return launch<T, OT, 128, 32, 2, true>(a, st);
-            return launch<T, OT, 128, 64, 2, true>(a, st);
+            if (p.bn == 32) return launch<T, OT, 128, 32, 2, true>(a, p.grid, st);
+            return launch<T, OT, 128, 64, 2, true>(a, p.grid, st);
         }
     }
-    switch (a.bn) {
-        case 32: return launch<T, OT, 128, 32, 2>(a, st);
-        case 64: return launch<T, OT, 128, 64, 2>(a, st);
-        default: return big ? launch<T, OT, 256, 128, 3>(a, st) : launch<T, OT, 128, 128, 2>(a, st);
+    switch (p.bn) {
+        case 32: return launch<T, OT, 128, 32, 2>(a, p.grid, st);
+        case 64: return launch<T, OT, 128, 64, 2>(a, p.grid, st);
+        default: return p.variant ? launch<T, OT, 256, 128, 3>(a, p.grid, st) : launch<T, OT, 128, 128, 2>(a, p.grid, st);
     }
 }
 
 }  // namespace
 
-int hdy_conv_bn_tile(int K) { return K <= 32 ? 32 : (K <= 64 ? 64 : 128); }
-
-// Statistic slabs the generic kernel writes for M output pixels, K channels, `taps` filter taps: one per workgroup position when the
-// sums stay in registers across the workgroup's tiles (a single column tile, or interleaved column tiles with grid % ntiles == 0: the
-// kernel's wg_stats), else one per 128 output rows.
-int hdy_conv_igemm_slabs(long long M, int K, int taps) {
-    const int bn = hdy_conv_bn_tile(K), ntiles = cdiv(K, bn);
-    const bool big = igemm_big(M, bn, ntiles, taps);
+// Every shape is this kernel's (hdyolo_internal.h, ConvPlan): variant = 1 the 256-row tile, bn = column tile.  Statistic slabs: one per workgroup
+// position when the sums stay in registers across the workgroup's tiles (a single column tile, or interleaved column tiles with
+// grid % ntiles == 0: the kernel's wg_stats), else one per 128 output rows.
+bool hdy_conv_igemm_plan(const ConvShape& s, ConvPlan* p) {
+    const long long M = conv_pixels(s);
+    const int bn = hdy_conv_bn_tile(s.K), ntiles = cdiv(s.K, bn), interleave = hdy_opt(HDY_OPT_TILE_INTERLEAVE);
+    const bool big = s.ncls <= 1 && igemm_big(M, bn, ntiles, conv_taps(s));
     const int BM = big ? 256 : 128;
-    const int grid = igemm_grid(M, ntiles, BM, bn, big ? 3 : 2);
-    if (ntiles > 1) return ((igemm_interleave_mode() & 1) && grid % ntiles == 0) ? grid / ntiles : (int)((M + 127) / 128);
-    const long long tiles = (M + BM - 1) / BM;
-    const long long tpb = (tiles + grid - 1) / grid;
-    return (int)((tiles + tpb - 1) / tpb);
+    const int grid = igemm_grid(M, ntiles * (s.ncls > 1 ? 4 : 1), BM, bn, big ? 3 : 2);
+    long long slabs = (M + 127) / 128;
+    if (ntiles > 1) {
+        if ((interleave & 1) && s.ncls <= 1 && grid % ntiles == 0) slabs = grid / ntiles;
+    } else {
+        const long long tiles = (M + BM - 1) / BM, tpb = (tiles + grid - 1) / grid;
+        slabs = (tiles + tpb - 1) / tpb;
+    }
+    *p = ConvPlan{CONV_IGEMM, big, grid, (int)slabs, bn, interleave};
+    return true;
 }
 
-// Workgroups (= statistics slabs) a dgrad launch with producer-side statistics uses; 0 when the shape cannot serve them.
-int hdy_conv_igemm_stat_grid(long long M, int K, int taps, int ncls) {
-    const int bn = hdy_conv_bn_tile(K);
-    if (bn > 64 || K % 8) return 0;               // the 128-wide instances have no registers to spare for the statistics operands
-    return igemm_grid(M, ncls > 1 ? 4 : 1, 128, bn, 2);
-}
-
-// Host-side validation + dispatch shared by the C-ABI entry points (api.hip).
-int hdy_conv_igemm_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st) {
-    const int VE = dtype == HDY_BF16 ? 8 : 4;
-    HDY_ARG(a.x && a.w && a.y, "conv: null pointer");
-    HDY_ARG(a.N > 0 && a.Hin > 0 && a.Win > 0 && a.Ho > 0 && a.Wo > 0 && a.K > 0 && a.C > 0, "conv: non-positive dim");
-    HDY_ARG(a.C % VE == 0, "conv: C=%d must be a multiple of %d for this dtype", a.C, VE);
-    HDY_ARG(a.ldx % (a.span_pixels ? 4 : VE) == 0 && (a.span_pixels || a.ldx >= a.C), "conv: ldx=%d must be >= C and a multiple of %d", a.ldx, VE);
-    HDY_ARG(a.ldy >= a.K, "conv: ldy=%d < K=%d", a.ldy, a.K);
-    HDY_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0, "conv: x/w must be 16-byte aligned");
-    HDY_ARG(a.TH > 0 && a.TW > 0, "conv: empty tap window");
-    HDY_ARG(a.Hin < 24000 && a.Win < 24000 && a.TH < 64 && a.TW < 64 && a.dh0 > -4000 && a.dw0 > -4000, "conv: image side beyond the loader's 16-bit coordinates");
-    HDY_ARG((long long)a.N * a.Hin * a.Win < (1LL << 31) && (long long)a.N * a.Ho * a.Wo < (1LL << 31), "conv: too many pixels");
-    a.Kd = a.TH * a.TW * a.C;
-    const int BKE = 8 * VE;
-    a.bn = hdy_conv_bn_tile(a.K);
-    HDY_ARG(a.Kdp == round_up(a.Kd, BKE), "conv: packed weight pitch %d != %d", a.Kdp, round_up(a.Kd, BKE));
-    a.M = a.N * a.Ho * a.Wo;
-    a.mtiles = cdiv(a.M, 128);
-    a.ntiles = cdiv(a.K, a.bn);
-    if (a.dense_out) HDY_ARG(a.oh_mul == 1 && a.ow_mul == 1 && a.oh_off == 0 && a.ow_off == 0 && a.Hout == a.Ho && a.Wout == a.Wo, "conv: dense_out geometry mismatch");
-    // 1x1 / stride 1 / no padding: input pixel == output pixel, no coordinate arithmetic in the loader
-    a.pointwise = (a.TH == 1 && a.TW == 1 && a.ih_mul == 1 && a.iw_mul == 1 && a.dh0 == 0 && a.dw0 == 0 && a.Hin == a.Ho && a.Win == a.Wo &&
-                   !a.span_pixels && a.ncls <= 1) ? 1 : 0;
-    if (a.ncls > 1) {
-        HDY_ARG(a.ncls == 4 && !a.dense_out && !a.stats, "conv: class walk is the four-class stride-2 dgrad");
-        for (int c = 0; c < 4; ++c) HDY_ARG(a.c_nkb[c] == round_up(a.c_TH[c] * a.c_TW[c] * a.C, BKE) / BKE, "conv: class %d k-blocks", c);
-    }
-    // coalesced 16-byte epilogue needs bf16 output, whole vectors and aligned rows
-    const bool bf16_out = dtype == HDY_BF16 && !out_f32;
-    a.vec_out = (bf16_out && a.K % 8 == 0 && a.ldy % 8 == 0 && ((uintptr_t)a.y & 15) == 0 &&
-                 (!a.res || (a.ldr % 8 == 0 && ((uintptr_t)a.res & 15) == 0))) ? 1 : 0;
-    if (a.nstat > 0) {
-        HDY_ARG(a.nstat <= 2 && a.vec_out && a.ntiles == 1 && a.bn <= 64 && !a.stats && !a.res, "conv: producer-side statistics need the bf16 vector epilogue and at most 64 output channels");
-        for (int r = 0; r < a.nstat; ++r) {
-            const StatReq& q = a.stat[r];
-            HDY_ARG(q.y && q.scale && q.shift && q.slabs && q.c0 >= 0 && q.c0 < q.c1 && q.c1 <= a.K && q.c0 % 8 == 0 && q.c1 % 8 == 0 &&
-                    q.ldy % 8 == 0 && (((uintptr_t)q.y | (uintptr_t)q.scale | (uintptr_t)q.shift) & 15) == 0,
-                    "conv: bad statistics request %d", r);
-        }
-    }
-    // loader geometry: union tap window over the classes, reciprocals for the row / chunk decompositions
-    a.uh0 = a.dh0; a.uw0 = a.dw0;
-    int uh1 = a.dh0 + a.TH, uw1 = a.dw0 + a.TW;
-    for (int c = 0; c < (a.ncls > 1 ? 4 : 0); ++c) {
-        a.uh0 = a.c_dh[c] < a.uh0 ? a.c_dh[c] : a.uh0; a.uw0 = a.c_dw[c] < a.uw0 ? a.c_dw[c] : a.uw0;
-        uh1 = a.c_dh[c] + a.c_TH[c] > uh1 ? a.c_dh[c] + a.c_TH[c] : uh1; uw1 = a.c_dw[c] + a.c_TW[c] > uw1 ? a.c_dw[c] + a.c_TW[c] : uw1;
-    }
-    a.UH = uh1 - a.uh0; a.UW = uw1 - a.uw0;
-    HDY_ARG(a.UH * a.UW <= 31, "conv: %d x %d tap window beyond the loader's 31 tap bits", a.UH, a.UW);
-    HDY_ARG(((long long)(a.UH + 1) * a.Win + a.UW) * a.ldx * (dtype == HDY_BF16 ? 2 : 4) < (1LL << 28), "conv: tap window spans too many bytes");
-    a.utap = a.C % BKE == 0 ? 1 : 0;
-    a.tile_interleave = igemm_interleave_mode();
-    hdy_magic((unsigned)(a.Ho * a.Wo), &a.mg_howo, &a.sh_howo);
-    hdy_magic((unsigned)a.Wo, &a.mg_wo, &a.sh_wo);
-    hdy_magic((unsigned)a.C, &a.mg_c, &a.sh_c);
-    for (int c = 0; c < 4; ++c) hdy_magic((unsigned)(a.ncls > 1 ? a.c_TW[c] : a.TW), &a.mg_tw[c], &a.sh_tw[c]);
-    int rc = 0;
-    if (a.ncls <= 1 && a.nstat == 0) {
-        if (hdy_conv_stem_try(a, dtype, out_f32, st, &rc)) return rc;         // patch-resident 6x6/s2 stem
-        if (hdy_conv3x3_c64_try(a, dtype, out_f32, st, &rc)) return rc;      // filter-resident 3x3 kernel when the shape qualifies
-        if (hdy_conv3x3_c128_try(a, dtype, out_f32, st, &rc)) return rc;     // ... its 128-input-channel form (round 6)
-        if (hdy_conv3x3s2_c32_try(a, dtype, out_f32, st, &rc)) return rc;    // patch-resident 3x3 / stride 2 kernel (32 input channels)
-        if (hdy_conv_deep_try(a, dtype, out_f32, st, &rc)) return rc;        // deep-pipelined 256-row kernel (C % 64 == 0, K >= 128)
-        // the slab count the caller sized its statistics buffer with must be the generic kernel's from here on
-        HDY_ARG(!a.stats || a.span_pixels || hdy_conv_deep_slabs(a.M, a.C, a.K, a.TH * a.TW, a.pointwise, dtype) == 0,
-                "conv: this shape's statistic slabs were sized for the deep-pipelined kernel, which declined the launch (alignment)");
-    }
-    if (a.ncls > 1 && a.nstat == 0 && hdy_conv_deep_try(a, dtype, out_f32, st, &rc)) return rc;      // stride-2 data gradient on the deep pipeline
-    if (dtype == HDY_BF16) return out_f32 ? launch_bn<bf16_t, float>(a, st) : launch_bn<bf16_t, bf16_t>(a, st);
-    return launch_bn<float, float>(a, st);
+// called by hdy_conv_launch after its validation; a.tile_interleave is the plan's
+int hdy_conv_igemm_launch(const ConvArgs& a, const ConvPlan& p, int dtype, int out_f32, hipStream_t st) {
+    if (const int rc = hdy_conv_take(a, p, true, "conv")) return rc;
+    for (int r = 0; r < a.nstat; ++r)
+        HDY_ARG(a.stat[r].nslabs == p.grid, "conv: statistics request %d holds %d slabs, this launch writes %d", r, a.stat[r].nslabs, p.grid);
+    if (dtype == HDY_BF16) return out_f32 ? launch_bn<bf16_t, float>(a, p, st) : launch_bn<bf16_t, bf16_t>(a, p, st);
+    return launch_bn<float, float>(a, p, st);
 }

@@ -29,11 +29,6 @@ constexpr int PATCH_B = PH * PROW;                      // 19584
 constexpr int PCHUNKS = PATCH_B / 16;                   // 1224 16-byte pieces
 constexpr int KSTEPS = 5;                               // 160 = 5 x 32 >= 144
 
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
-                                     (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
-}
-
 // NT = K / 16 (1..4); EPI: 0 raw, 1 scale/shift, 2 scale/shift + SiLU
 template <int NT, int EPI>
 __global__ __launch_bounds__(NTHR) void conv_stem_kernel(const ConvArgs p) {
@@ -54,7 +49,7 @@ __global__ __launch_bounds__(NTHR) void conv_stem_kernel(const ConvArgs p) {
     const int tpb = (tiles_total + (int)gridDim.x - 1) / (int)gridDim.x;
     const int wg = blockIdx.x;                           // statistics slab wg; tile ranges are contiguous in memory order
     const int tile_begin = wg * tpb, tile_end = min(tile_begin + tpb, tiles_total);
-    if (tile_begin >= tile_end) return;                  // (the launcher sizes the grid so that this never happens)
+    if (tile_begin >= tile_end) return;                  // (hdy_conv_stem_plan sizes the grid so that this never happens)
 
     const unsigned char* __restrict__ x = (const unsigned char*)p.x;
     const bf16_t* __restrict__ w = (const bf16_t*)p.w;
@@ -217,7 +212,7 @@ __global__ __launch_bounds__(NTHR) void conv_stem_kernel(const ConvArgs p) {
 template <int NT>
 int launch_nt(const ConvArgs& a, int grid, hipStream_t st) {
     const size_t smem = 2 * PATCH_B + (size_t)TOH * TOW * NT * 32 + (size_t)NT * 16 * 400;
-    const int epi = a.act == 1 ? 2 : ((a.scale || a.shift) ? 1 : 0);
+    const int epi = epilogue_of(a);
     static PerDeviceOnce attr_once;           // first launch of this instance on any thread
     attr_once.run([&] {
         (void)hipFuncSetAttribute((const void*)conv_stem_kernel<NT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -233,53 +228,31 @@ int launch_nt(const ConvArgs& a, int grid, hipStream_t st) {
 
 }  // namespace
 
-static bool stem_shape_ok(int K, int Ho, int Wo, int dtype) {
+// The shape is this kernel's (hdyolo_internal.h, ConvPlan): variant = 16-channel groups.  Every workgroup gets the same number of tiles where
+// possible (two 72 KB workgroups per CU at K = 32) and none is empty: each owns a statistics slab.
+bool hdy_conv_stem_plan(const ConvShape& s, ConvPlan* p) {
     const bool disabled = hdy_opt(HDY_OPT_NO_STEM_KERNEL) != 0;   // tests: force the generic kernel for A/B comparison
-    return !disabled && dtype == HDY_BF16 && K % 16 == 0 && K >= 16 && K <= 64 && Ho % TOH == 0 && Wo % TOW == 0;
-}
-
-// grid: every workgroup gets the same number of tiles where possible (two 72 KB workgroups per CU at K = 32)
-static int stem_grid(int tiles, int K) {
-    const int per_cu = (2 * PATCH_B + TOH * TOW * K * 2 + K * 400) * 2 <= 160 * 1024 ? 2 : 1;
+    if (disabled || !s.stem || s.dtype != HDY_BF16 || s.K % 16 || s.K < 16 || s.K > 64 || s.H % 2 || s.W % 2 || (s.H / 2) % TOH || (s.W / 2) % TOW) return false;
+    const int tiles = s.N * (s.H / 2 / TOH) * (s.W / 2 / TOW);
+    const int per_cu = (2 * PATCH_B + TOH * TOW * s.K * 2 + s.K * 400) * 2 <= 160 * 1024 ? 2 : 1;
     int grid = 256 * per_cu;
     if (grid > tiles) grid = tiles;
     const int tpb = (tiles + grid - 1) / grid;
-    return (tiles + tpb - 1) / tpb;                      // no empty workgroups: each owns a statistics slab
+    grid = (tiles + tpb - 1) / tpb;
+    *p = ConvPlan{CONV_STEM, s.K / 16, grid, grid, 0, 0};
+    return true;
 }
 
-// Statistic slabs the stem kernel writes for an H x W image batch (0 = not eligible).
-int hdy_conv_stem_slabs(int N, int H, int W, int K, int dtype) {
-    const int Ho = H / 2, Wo = W / 2;
-    if (H % 2 || W % 2 || !stem_shape_ok(K, Ho, Wo, dtype)) return 0;
-    return stem_grid(N * (Ho / TOH) * (Wo / TOW), K);
-}
-
-// Returns 1 and launches when the stem shape qualifies; 0 = not eligible (generic kernel runs).
-int hdy_conv_stem_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc) {
-    if (!a.span_pixels || out_f32 || a.res || a.accumulate || !a.dense_out || a.act > 1) return 0;
-    if (!(a.TH == 6 && a.TW == 1 && a.C == 24 && a.ldx == 4 && a.ih_mul == 2 && a.iw_mul == 2 && a.Kdp >= 160)) return 0;
-    if (!(a.Hin == 2 * a.Ho + 4 && a.Win == 2 * a.Wo + 4 && stem_shape_ok(a.K, a.Ho, a.Wo, dtype))) return 0;
-    const bool aligned = a.ldy % 8 == 0 && ((uintptr_t)a.y & 15) == 0 && ((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.w & 15) == 0;
-    if (!aligned) {
-        if (!a.stats) return 0;
-        hdy_set_error("conv_stem: statistics requested but y rows are not 16-byte aligned (ldy=%d)", a.ldy);
-        *rc = HDY_EINVAL;
-        return 1;
+int hdy_conv_stem_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st) {
+    if (out_f32 || a.res || a.accumulate || a.act > 1) return HDY_CONV_DECLINE;
+    // (not rows_aligned: the image rows are 4 channels wide)
+    const bool aligned = a.ldy % 8 == 0 && (((uintptr_t)a.y | (uintptr_t)a.x | (uintptr_t)a.w) & 15) == 0;
+    if (const int rc = hdy_conv_take(a, p, aligned, "conv_stem")) return rc;
+    switch (p.variant) {
+        case 1: launch_nt<1>(a, p.grid, st); break;
+        case 2: launch_nt<2>(a, p.grid, st); break;
+        case 3: launch_nt<3>(a, p.grid, st); break;
+        default: launch_nt<4>(a, p.grid, st); break;
     }
-    const int grid = stem_grid(a.N * (a.Ho / TOH) * (a.Wo / TOW), a.K);
-    HDY_STAT_CAP(a, grid, "conv_stem")
-    switch (a.K / 16) {
-        case 1: launch_nt<1>(a, grid, st); break;
-        case 2: launch_nt<2>(a, grid, st); break;
-        case 3: launch_nt<3>(a, grid, st); break;
-        default: launch_nt<4>(a, grid, st); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        hdy_set_error("conv_stem: launch failed: %s", hipGetErrorString(e));
-        *rc = (int)e;
-        return 1;
-    }
-    *rc = HDY_OK;
-    return 1;
+    return hdy_launch_status("conv_stem");
 }

@@ -26,8 +26,6 @@ __device__ uint4 g_hdy_zero16_w[4];   // zero page for masked 16-byte fetches
 
 namespace {
 
-__device__ __forceinline__ int fsw(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }
-
 template <typename T> struct WT;
 template <> struct WT<bf16_t> { static constexpr int VE = 8, TK = 64, WTL = 2; };   // channels per 128-byte sub-tile row, MFMA tiles per 32 ch
 template <> struct WT<float> { static constexpr int VE = 4, TK = 32, WTL = 1; };

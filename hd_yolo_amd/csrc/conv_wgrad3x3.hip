@@ -34,8 +34,6 @@ struct W3Args {
     int nkb, ncb, nsplit;
 };
 
-__device__ __forceinline__ int fsw3(int row) { return (row & 6) ^ (((row >> 3) & 1) * 5); }
-
 constexpr int W3_MAXTP = 256;        // output pixels per tile
 constexpr int W3_MAXPP = 352;        // patch pixels per tile
 

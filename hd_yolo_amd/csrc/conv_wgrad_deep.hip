@@ -44,13 +44,6 @@ struct WDArgs {
     int sh_tw;
 };
 
-__device__ __forceinline__ unsigned fdiv(unsigned n, unsigned mg, int sh) { return __umulhi(n << 1, mg) >> sh; }
-__device__ __forceinline__ int fsw(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }
-
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, unsigned lds_byte) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (void __attribute__((address_space(3)))*)(uintptr_t)lds_byte, 16, (int)voff, (int)soff, 0, 0);
-}
-
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 union F16 {          // one 16x16x32 operand = two transposed 8-byte reads (pixels +0..3, +4..7 of the lane group's 8)
     i32x2 d[2];

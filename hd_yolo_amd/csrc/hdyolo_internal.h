@@ -1,5 +1,7 @@
 // Internal (not part of the C ABI): argument blocks shared between api.hip and the kernel files.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 // BatchNorm-backward statistics requested from the kernel that produces a gradient tensor (its LAST contribution): for the output
@@ -22,9 +24,9 @@ struct ConvArgs {
     const float* scale;   // per-channel epilogue scale (or null = 1)
     const float* shift;   // per-channel epilogue shift / bias (or null = 0)
     float* stats;         // [stat_cap][2][K] BatchNorm partial sums (or null)
-    int stat_cap;         // slabs the caller's `stats` array holds (hdy_conv_fwd's stat_slabs): every launcher that writes statistics checks it
-                          // against the slab count of the kernel and grid it is about to start (HDY_STAT_CAP) — the sizing query and the launch
-                          // both read the process-wide option table, which another thread may change in between
+    int stat_cap;         // slabs the caller's `stats` array holds (hdy_conv_fwd's stat_slabs): checked against the slab count of the plan about to be
+                          // launched (hdy_conv_take) — the sizing query and the launch both read the process-wide option table, which another
+                          // thread may change in between
     const void* res;      // residual added after the activation, same pixel grid as y, pitch ldr (or null)
     int ldr;
     int N, Hin, Win, C, ldx;
@@ -45,7 +47,7 @@ struct ConvArgs {
     int ncls;
     int c_dh[4], c_dw[4], c_TH[4], c_TW[4], c_nkb[4], c_oh[4], c_ow[4];
     long long c_w[4];
-    // derived by hdy_conv_igemm_launch for the loader: union tap window over the classes (origin uh0 / uw0, UH x UW taps <= 31),
+    // derived by hdy_conv_launch for the loader: union tap window over the classes (origin uh0 / uw0, UH x UW taps <= 31),
     // utap = every 128-byte k-block lies inside one tap (C % BKE == 0), reciprocals (hdy_magic) of Ho*Wo, Wo, C and the tap-window width
     int uh0, uw0, UH, UW, utap;
     int tile_interleave;  // 1: tiles that share A rows (column tiles of one m-tile, parity classes) go to neighbouring workgroups instead of one
@@ -54,14 +56,101 @@ struct ConvArgs {
     int dbg;              // conv_deep.hip timing ablations (HDY_DEEP_DEBUG; results are wrong when set): 1 no A loads, 2 no B loads, 4 no MFMAs, 8 no epilogue, 16 no fragment reads
 };
 
-// `writes` = slabs the launch about to start writes; inside a *_try function (error through *rc, return 1 = handled)
-#define HDY_STAT_CAP(a, writes, who)                                                                                                      \
-    if ((a).stats && (a).stat_cap != (writes)) {                                                                                          \
-        hdy_set_error("%s: the statistics array holds %d slabs, this launch writes %d (a kernel-selection option changed between "        \
-                      "hdy_conv_stat_slabs and the launch?)", who, (a).stat_cap, (int)(writes));                                          \
-        *rc = HDY_EINVAL;                                                                                                                 \
-        return 1;                                                                                                                         \
-    }
+// ---- forward / data-gradient kernel selection -----------------------------------------------------------------------------------------
+// The layer as the selection sees it: what hdy_conv_stat_slabs is asked with, and what conv_dispatch.hip derives ONCE from a ConvArgs
+// (a stride-1 data gradient is the same convolution with C and K swapped and pad' = R - 1 - pad).
+struct ConvShape {
+    int N, H, W;          // input pixel grid (stem: the image, without its padding)
+    int Ho, Wo;           // output pixels per image the launch walks (ncls == 4: per parity class)
+    int C, K, R, S, stride;
+    int pad;              // < 0: the window is not padded alike on both axes, or the output grid is not the one (H, W, R, S, stride, pad) give
+    int dense;            // every output pixel is written (0: one parity class of a stride-2 data gradient)
+    int dtype;
+    int stem;             // the 6x6 / stride 2 / pad 2 stem on its 4-channel padded image (C == 3)
+    int stats;            // the launch writes BatchNorm slabs (the sizing query asks with 1)
+    int ncls;             // 4: the four-class walk of the stride-2 data gradient, else 1
+};
+// column tile of the generic kernel = row padding of a packed filter block
+inline int hdy_conv_bn_tile(int K) { return K <= 32 ? 32 : (K <= 64 ? 64 : 128); }
+inline int conv_out_dim(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
+// the layer hdy_conv_fwd / hdy_conv_stat_slabs are called with
+inline ConvShape conv_shape(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype, int stem, int stats) {
+    return ConvShape{N, H, W, conv_out_dim(H, R, stride, pad), conv_out_dim(W, S, stride, pad), C, K, R, S, stride, pad, 1, dtype, stem, stats, 1};
+}
+inline long long conv_pixels(const ConvShape& s) { return (long long)s.N * s.Ho * s.Wo; }
+inline int conv_taps(const ConvShape& s) { return s.stem ? 6 : s.R * s.S; }
+// a square window with these parameters (then Ho, Wo follow from H, W)
+inline bool conv_is(const ConvShape& s, int R, int stride, int pad) { return !s.stem && s.ncls <= 1 && s.R == R && s.S == R && s.stride == stride && s.pad == pad; }
+
+// The order of this list is the order the families are asked in (conv_fwd_plan, conv_dispatch.hip); the generic kernel takes everything.
+enum ConvFamily { CONV_NONE = 0, CONV_STEM, CONV_3X3_C64, CONV_3X3_C128, CONV_3X3S2, CONV_DEEP, CONV_IGEMM };
+
+// What one family answers for a shape: the sizing query reads `slabs`, the launch reads all of it.
+struct ConvPlan {
+    int family;           // ConvFamily
+    int variant;          // the family's instance (input channels, planes, 256-row tile, ...)
+    int grid;             // workgroups
+    int slabs;            // statistic slabs a launch with `stats` writes
+    int bn;               // column tile (deep-pipelined and generic kernel)
+    int interleave;       // generic kernel: the HDY_TILE_INTERLEAVE value `slabs` was counted with (becomes ConvArgs.tile_interleave)
+};
+
+// <family>_plan: true = the shape is this family's, *p filled.  Pure host functions of the shape and the option table.
+bool hdy_conv_stem_plan(const ConvShape& s, ConvPlan* p);
+bool hdy_conv3x3_c64_plan(const ConvShape& s, ConvPlan* p);
+bool hdy_conv3x3_c128_plan(const ConvShape& s, ConvPlan* p);
+bool hdy_conv3x3s2_plan(const ConvShape& s, ConvPlan* p);
+bool hdy_conv_deep_plan(const ConvShape& s, ConvPlan* p);
+bool hdy_conv_igemm_plan(const ConvShape& s, ConvPlan* p);
+
+// <family>_launch: starts the planned instance on the planned grid.  It decides nothing about the shape again; it checks what the shape
+// cannot know (alignment, fp32 output, residual, accumulate, activation) and answers HDY_CONV_DECLINE when this call cannot run on it.
+enum { HDY_CONV_DECLINE = -100 };
+int hdy_conv_stem_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
+int hdy_conv3x3_c64_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
+int hdy_conv3x3_c128_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
+int hdy_conv3x3s2_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
+int hdy_conv_deep_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
+int hdy_conv_igemm_launch(const ConvArgs& a, const ConvPlan& p, int dtype, int out_f32, hipStream_t st);
+
+// The one rule for a launch whose plan names a family.  `fits` = pointers, pitches and output type qualify for its kernel.  It does not
+// fit: without statistics the next family in the order takes the launch; with statistics the caller sized the slab array with
+// hdy_conv_stat_slabs for THIS family and any other kernel would write a different count, so that is an error.  It fits: the array must
+// hold exactly what the plan writes (HDY_OK = go on and launch).
+inline int hdy_conv_take(const ConvArgs& a, const ConvPlan& p, bool fits, const char* who) {
+    if (!fits && !a.stats) return HDY_CONV_DECLINE;
+    HDY_ARG(fits, "%s: statistics requested, but this call does not fit the kernel their slabs were sized for (bf16 output, 16-byte aligned x/y/res rows; "
+            "ldx=%d ldy=%d)", who, a.ldx, a.ldy);
+    HDY_ARG(!a.stats || a.stat_cap == p.slabs, "%s: the statistics array holds %d slabs, this launch writes %d (a kernel-selection option changed between "
+            "hdy_conv_stat_slabs and the launch?)", who, a.stat_cap, p.slabs);
+    return HDY_OK;
+}
+
+// x, y and the residual (need_w: the packed filter too) can be moved with 16-byte accesses
+inline bool rows_aligned(const ConvArgs& a, bool need_w) {
+    return a.ldx % 8 == 0 && a.ldy % 8 == 0 && (((uintptr_t)a.x | (uintptr_t)a.y) & 15) == 0 && (!need_w || (((uintptr_t)a.w & 15) == 0 && a.Kdp % 8 == 0)) &&
+           (!a.res || (a.ldr % 8 == 0 && ((uintptr_t)a.res & 15) == 0));
+}
+
+// epilogue instance of the patch- and filter-resident kernels: 0 store, 1 scale / shift, 2 scale / shift + SiLU
+inline int epilogue_of(const ConvArgs& a) { return a.act == 1 ? 2 : ((a.scale || a.shift) ? 1 : 0); }
+
+// run-time (stats, epilogue) -> template arguments: f(std::bool_constant<STATS>, std::integral_constant<int, EPI>)
+template <typename F> inline void with_stats_epi(bool stats, int epi, F&& f) {
+    auto with_epi = [&](auto s) {
+        if (epi == 2) f(s, std::integral_constant<int, 2>{});
+        else if (epi == 1) f(s, std::integral_constant<int, 1>{});
+        else f(s, std::integral_constant<int, 0>{});
+    };
+    if (stats) with_epi(std::true_type{});
+    else with_epi(std::false_type{});
+}
+
+// status of the launch just issued
+inline int hdy_launch_status(const char* who) {
+    HDY_LAUNCH_CHECK(who);
+    return HDY_OK;
+}
 
 // reciprocal for n / d, n < 2^31: q = mulhi(2n, *mg) >> *sh (conv_igemm.hip fdiv)
 inline void hdy_magic(unsigned d, unsigned* mg, int* sh) {
@@ -88,17 +177,8 @@ struct WgradArgs {
     const float *bn_scale, *bn_shift, *bn_mean, *bn_invstd, *bn_c1, *bn_c2;
 };
 
-int hdy_conv_bn_tile(int K);
 int hdy_wgrad_stem_grid(int N, int Ho, int Wo, int K, int dtype);
 int hdy_wgrad_stem_launch(const WgradArgs& a, int grid, hipStream_t st);
-int hdy_conv_igemm_slabs(long long M, int K, int taps);
-int hdy_conv3x3_c64_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc);
-int hdy_conv3x3_c64_slabs(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype);
-int hdy_conv3x3_c128_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc);
-int hdy_conv3x3_c128_slabs(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype);
-int hdy_conv_stem_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc);
-int hdy_conv_stem_slabs(int N, int H, int W, int K, int dtype);
-int hdy_conv_igemm_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st);
 int hdy_wgrad_launch(WgradArgs a, int dtype, hipStream_t st);
 int hdy_wgrad_plan(int K, int Q, long long P, int dtype, int* splits, int* pix_per_split);
 size_t hdy_wgrad3x3_workspace_bytes(int N, int Ho, int Wo, int C, int K, int stride, int dtype);
@@ -107,9 +187,5 @@ int hdy_wgrad3x3_try(const void* x, int ldx, const void* dy, int lddy, int N, in
 size_t hdy_wgrad_deep_workspace_bytes(int N, int Hin, int Win, int Ho, int Wo, int C, int K, int R, int S, int stride, int dtype);
 int hdy_wgrad_deep_try(const void* x, int ldx, const void* dy, int lddy, int N, int Hin, int Win, int Ho, int Wo, int C, int K, int R, int S, int stride,
                        int pad, float* partial, int dtype, hipStream_t st, int* splits, int* rc);
-int hdy_conv_igemm_stat_grid(long long M, int K, int taps, int ncls);
+int hdy_conv_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st);      // validation + plan + launch (conv_dispatch.hip, next to hdy_conv_stat_slabs)
 int hdy_dgrad3x3s2_try(const ConvArgs& a, int dtype, hipStream_t st, int* rc);
-int hdy_conv3x3s2_c32_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc);
-int hdy_conv_deep_try(const ConvArgs& a, int dtype, int out_f32, hipStream_t st, int* rc);
-int hdy_conv_deep_slabs(long long M, int C, int K, int taps, int pointwise, int dtype);
-int hdy_conv3x3s2_c32_slabs(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype);

@@ -14,30 +14,6 @@ template <typename T> struct VT;
 template <> struct VT<float> { static constexpr int VE = 4; };
 template <> struct VT<bf16_t> { static constexpr int VE = 8; };
 
-template <typename T> __device__ __forceinline__ void unpack(const i32x4& v, float* f);
-template <> __device__ __forceinline__ void unpack<float>(const i32x4& v, float* f) {
-    V16 u; u.i = v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f[i] = u.f[i];
-}
-template <> __device__ __forceinline__ void unpack<bf16_t>(const i32x4& v, float* f) {
-    V16 u; u.i = v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = (float)u.h[i];
-}
-template <typename T> __device__ __forceinline__ i32x4 pack(const float* f);
-template <> __device__ __forceinline__ i32x4 pack<float>(const float* f) {
-    V16 u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) u.f[i] = f[i];
-    return u.i;
-}
-template <> __device__ __forceinline__ i32x4 pack<bf16_t>(const float* f) {
-    V16 u;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) u.h[i] = (bf16_t)f[i];
-    return u.i;
-}
 
 constexpr int GN_SLICES = 32;       // pixel slices per image in the statistics passes (grid = N x GN_SLICES)
 
@@ -762,7 +738,6 @@ inline int grid_for(long long items) {
 
 }  // namespace
 
-#define VEC_OK(ptr, ld, VE) ((((uintptr_t)(ptr)) & 15) == 0 && (ld) % (VE) == 0)
 
 extern "C" {
 
