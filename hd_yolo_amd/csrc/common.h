@@ -137,6 +137,32 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
 // n / d for n < 2^31 with the host-made reciprocal of hdy_magic(): mulhi(2n, mg) >> sh
 __device__ __forceinline__ unsigned fdiv(unsigned n, unsigned mg, int sh) { return __umulhi(n << 1, mg) >> sh; }
 
+// ---- NMS arithmetic shared by detect.hip (one workgroup per box set) and nms_grid.hip (one set over the whole chip): the two must agree bit
+// for bit, so there is one copy.
+// IoU(a, b) > thr in IEEE fp32 with explicit round-to-nearest ops (no FMA contraction), the oracle's operation order; area = (x2 - x1) * (y2 - y1).
+__device__ __forceinline__ bool iou_gt(float ax1, float ay1, float ax2, float ay2, float aarea, float bx1, float by1, float bx2, float by2,
+                                       float barea, float thr) {
+    const float xx1 = ax1 > bx1 ? ax1 : bx1;
+    const float yy1 = ay1 > by1 ? ay1 : by1;
+    const float xx2 = ax2 < bx2 ? ax2 : bx2;
+    const float yy2 = ay2 < by2 ? ay2 : by2;
+    float w = __fsub_rn(xx2, xx1);
+    float h = __fsub_rn(yy2, yy1);
+    w = w < 0.f ? 0.f : w;
+    h = h < 0.f ? 0.f : h;
+    const float inter = __fmul_rn(w, h);
+    const float ovr = __fdiv_rn(inter, __fsub_rn(__fadd_rn(aarea, barea), inter));
+    return ovr > thr;
+}
+
+// 32-bit key whose ASCENDING unsigned order is DESCENDING score order for every float (negative scores included: explicit-box calls
+// carry caller scores of any sign; -0.0 ranks as +0.0).  For the positive scores of the thresholded paths this is ~bits, as before.
+__device__ __forceinline__ unsigned desc_key(float s) {
+    unsigned u = s == 0.0f ? 0u : __float_as_uint(s);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // ascending order-preserving map of the float line
+    return ~u;
+}
+
 // LDS-DMA straight from global memory: lane l's 16 bytes at g land at lds_wave_base + l*16
 __device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,

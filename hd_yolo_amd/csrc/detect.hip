@@ -166,30 +166,8 @@ struct NmsArgs {
     float* kept_area_g;
 };
 
-__device__ __forceinline__ bool iou_gt(float ax1, float ay1, float ax2, float ay2, float aarea, float bx1, float by1, float bx2, float by2,
-                                       float barea, float thr) {
-    const float xx1 = ax1 > bx1 ? ax1 : bx1;
-    const float yy1 = ay1 > by1 ? ay1 : by1;
-    const float xx2 = ax2 < bx2 ? ax2 : bx2;
-    const float yy2 = ay2 < by2 ? ay2 : by2;
-    float w = __fsub_rn(xx2, xx1);
-    float h = __fsub_rn(yy2, yy1);
-    w = w < 0.f ? 0.f : w;
-    h = h < 0.f ? 0.f : h;
-    const float inter = __fmul_rn(w, h);
-    const float ovr = __fdiv_rn(inter, __fsub_rn(__fadd_rn(aarea, barea), inter));
-    return ovr > thr;
-}
-
+// iou_gt and desc_key live in common.h (shared with nms_grid.hip)
 struct Cand { float x1, y1, x2, y2, area, score; int cls; };
-
-// 32-bit key whose ASCENDING unsigned order is DESCENDING score order for every float (negative scores included: explicit-box calls
-// carry caller scores of any sign; -0.0 ranks as +0.0).  For the positive scores of the thresholded paths this is ~bits, as before.
-__device__ __forceinline__ unsigned desc_key(float s) {
-    unsigned u = s == 0.0f ? 0u : __float_as_uint(s);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // ascending order-preserving map of the float line
-    return ~u;
-}
 
 __device__ __forceinline__ Cand make_cand(const float* p, int nc, int class_aware, int xyxy = 0) {
     Cand c;

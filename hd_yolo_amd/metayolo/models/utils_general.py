@@ -223,7 +223,8 @@ def paired_box_iou(boxes1, boxes2):
 # ---------------------------------------------------------------------------------------------- NMS
 def nms(boxes, scores, iou_threshold):
     """What the reference takes from torchvision.ops.nms (yolo.py:195): kept indices by descending score, IoU > threshold
-    suppressed, class-agnostic.  Runs on the MI355X (hdy_nms_boxes); at most 4096 boxes are kept."""
+    suppressed, class-agnostic; every survivor is returned.  Runs on the MI355X: the one-workgroup kernel (hdy_nms_boxes) for small sets, the
+    multi-workgroup path (hdy_nms_grid_*) from ops.NMS_GRID_MIN boxes on (whole-slide merges), same result bit for bit."""
     return _ops.nms(boxes, scores, iou_threshold)
 
 

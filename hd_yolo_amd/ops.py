@@ -778,15 +778,77 @@ def _nms_launch(boxes, scores, iou_thres, max_det):
     return keep[0, :int(n_keep.item())]
 
 
-def nms(boxes, scores, iou_thres, max_det=None):
-    """torchvision.ops.nms(boxes xyxy (N,4), scores (N,), iou) on the GPU: ALL kept indices (int64) in descending score order (ties:
-    lower index first), or the first `max_det` of them — one launch whatever the count (up to 4096 kept boxes the kernel's list lives in
-    LDS, beyond that in its workspace), so whole-slide merges of many tiles lose nothing (the reference's torchvision call returns
-    every survivor).  Rounds 2-5 continued the greedy pass in further launches with tensor expressions in between."""
+NMS_GRID_MIN = 32768            # nms(): sets of at least this many boxes take the multi-workgroup path (nms_grid); env HDY_NMS_GRID_MIN overrides,
+#                                 0 = never.  The smallest measured size from which the new path's slowest repeat beats the one-workgroup
+#                                 kernel's fastest at that and every larger measured size, over ALL three set families of
+#                                 profiles/nms_grid_ab.txt; slide-like sets alone cross at 2048, tile-density sets at 8192
+NMS_GRID_MAX = 1 << 24          # HDY_NMS_GRID_MAX_M (include/hdyolo.h)
+NMS_GRID_FIRST_ROUNDS = 12      # rounds enqueued before the first look at the undecided counter (random and slide-like sets need 4-10)
+
+
+def _nms_grid_min():
+    v = os.environ.get('HDY_NMS_GRID_MIN')
+    return NMS_GRID_MIN if v is None or v == '' else int(v)
+
+
+def _nms_grid_launch(boxes, scores, iou_thres, max_det, info=None):
+    """The three-piece multi-workgroup NMS (hdy_nms_grid_begin / _round / _finish) with the round loop here: rounds are enqueued in growing
+    batches, and the undecided counter is read (one synchronising copy, together with the kept count) after each batch.  Returns None when the
+    device flag says the spatial index cannot serve the set (a non-finite coordinate or side length): the caller falls back."""
+    N = boxes.shape[0]
+    dev = boxes.device
+    bs = torch.cat([boxes.float(), scores.float().reshape(N, 1)], 1).contiguous()
+    keep = torch.empty((max_det,), dtype=torch.int64, device=dev)
+    stat = torch.empty((4,), dtype=torch.int32, device=dev)          # n_keep, then status[3] = undecided, non-finite flag, rounds
+    wsb = _lib.query('hdy_nms_grid_workspace_bytes', N)
+    ws = torch.empty(((wsb + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    st = stream_ptr()
+    _lib.call('hdy_nms_grid_begin', bs.data_ptr(), N, ws.data_ptr(), ws.numel() * 8, st)
+    done, batch = 0, NMS_GRID_FIRST_ROUNDS
+    while True:
+        _lib.call('hdy_nms_grid_round', N, float(iou_thres), done, batch, ws.data_ptr(), ws.numel() * 8, st)
+        done += batch
+        _lib.call('hdy_nms_grid_finish', N, int(max_det), keep.data_ptr(), stat.data_ptr(), stat.data_ptr() + 4, ws.data_ptr(), ws.numel() * 8, st)
+        n_keep, undecided, nonfinite, rounds = stat.tolist()
+        if nonfinite:
+            return None
+        if undecided == 0:
+            break
+        batch = min(2 * batch, 1024)
+    if info is not None:
+        info.update(rounds=rounds, rounds_enqueued=done, workspace_bytes=wsb)
+    return keep[:n_keep]
+
+
+def nms_grid(boxes, scores, iou_thres, max_det=None, info=None):
+    """nms() through the multi-workgroup path whatever the size: the same kept indices in the same order, bit for bit, as the one-workgroup
+    kernel.  Sets the spatial index cannot serve (a non-finite coordinate, iou_thres outside [0, 1], more than NMS_GRID_MAX boxes) are
+    answered by the one-workgroup kernel, as before.  `info` (a dict) receives rounds / rounds_enqueued / workspace_bytes."""
     require_gpu(boxes)
     N = boxes.shape[0]
     if N == 0:
         return torch.empty((0,), dtype=torch.int64, device=boxes.device)
+    max_det = N if max_det is None else max(1, min(int(max_det), N))
+    iou = float(iou_thres)
+    if 0.0 <= iou <= 1.0 and N <= NMS_GRID_MAX:
+        keep = _nms_grid_launch(boxes, scores, iou, max_det, info)
+        if keep is not None:
+            return keep
+    return _nms_launch(boxes, scores, iou_thres, max_det)
+
+
+def nms(boxes, scores, iou_thres, max_det=None):
+    """torchvision.ops.nms(boxes xyxy (N,4), scores (N,), iou) on the GPU: ALL kept indices (int64) in descending score order (ties:
+    lower index first), or the first `max_det` of them, so whole-slide merges of many tiles lose nothing (the reference's torchvision call
+    returns every survivor).  Below NMS_GRID_MIN boxes: one launch of the one-workgroup kernel (up to 4096 kept boxes its list lives in LDS,
+    beyond that in its workspace).  From NMS_GRID_MIN on: the multi-workgroup path (nms_grid), same result bit for bit."""
+    require_gpu(boxes)
+    N = boxes.shape[0]
+    if N == 0:
+        return torch.empty((0,), dtype=torch.int64, device=boxes.device)
+    grid_min = _nms_grid_min()
+    if grid_min > 0 and N >= grid_min:
+        return nms_grid(boxes, scores, iou_thres, max_det)
     return _nms_launch(boxes, scores, iou_thres, N if max_det is None else max(1, min(int(max_det), N)))
 
 

@@ -312,3 +312,36 @@ def synth_nms_preds(batch, survivors, nc, size=1024, seed=2, pitch=12.0, extra=2
         perm = torch.randperm(n, generator=g)
         out[b] = rows[perm]
     return out
+
+
+def synth_slide_boxes(n_objects, side, seed=0, moat=None):
+    """Merged detections of a whole slide as the overlap strips of neighbouring tiles leave them: `n_objects` objects of 12-30 px spread
+    over a side x side region, each detected 1-3 times with 1.5 px jitter of the centre and +-10 % of the size, uniform scores.
+    Returns numpy (boxes xyxy fp32 (M, 4), scores fp32 (M,)), M ~ 2 * n_objects.  moat = (x0, y0, x1, y1, width): no box touches the band
+    of `width` px around that window, so the window's boxes interact with nothing outside it."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(0, side, (n_objects, 2))
+    wh = rng.uniform(12, 30, (n_objects, 2))
+    rep = rng.integers(1, 4, n_objects)
+    c = np.repeat(c, rep, 0) + rng.normal(0, 1.5, (int(rep.sum()), 2))
+    wh = np.repeat(wh, rep, 0) * rng.uniform(0.9, 1.1, (int(rep.sum()), 2))
+    boxes = np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32)
+    scores = rng.uniform(0, 1, len(boxes)).astype(np.float32)
+    if moat is not None:
+        x0, y0, x1, y1, width = moat
+        inside = (boxes[:, 0] > x0) & (boxes[:, 1] > y0) & (boxes[:, 2] < x1) & (boxes[:, 3] < y1)
+        outside = (boxes[:, 2] < x0 - width) | (boxes[:, 0] > x1 + width) | (boxes[:, 3] < y0 - width) | (boxes[:, 1] > y1 + width)
+        sel = inside | outside
+        boxes, scores = boxes[sel], scores[sel]
+    return boxes, scores
+
+
+def synth_dense_boxes(n, seed=0):
+    """One dense tile's candidates as explicit boxes: `n` boxes of 12-30 px at the density of 16 384 candidates per 640 x 640 tile."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    side = 640.0 * (n / 16384.0) ** 0.5
+    c = rng.uniform(0, side, (n, 2))
+    wh = rng.uniform(12, 30, (n, 2))
+    return np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32), rng.uniform(0, 1, n).astype(np.float32)

@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 6
+#define HDY_ABI_VERSION 7
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -270,6 +270,33 @@ int hdy_det_outputs(float* scores, const float* boxes, const int* n_keep, int B,
  * score order (stable), -1 padded; n_keep[B].  Same kernel and workspace rule as hdy_nms_batched (any max_det). */
 int hdy_nms_boxes(const float* boxes_scores, int B, int N, float iou, int max_det, long long* keep, int* n_keep, void* workspace,
                   size_t ws_bytes, void* stream);
+
+/* The same result as hdy_nms_boxes with B = 1 (same kept rows, same order, bit for bit) for ONE large set of explicit boxes, computed by
+ * the whole chip instead of one workgroup: the merge of a whole slide's tiles (evaluation.py inference_on_slide -> Detect.merge_outputs ->
+ * utils_general.nms), Ensemble.merge (metayolo/models/yolo.py:189-199) and the torchvision.ops.nms calls of utils_general.py's
+ * non_max_suppression option branches.  Pipeline (csrc/nms_grid.hip): 64-bit rank keys, multi-workgroup bitonic sort, a hierarchy of uniform
+ * grids over the box centres (one level per octave of box size; one table for all levels, hashed when the cells outnumber its entries),
+ * then rounds over an undecided / kept / suppressed state per box, one launch per round, until no box is undecided; kept flags are
+ * compacted in rank order.
+ * Split in three so that NO piece synchronises (all three can be listed for hdy_exec_run); the caller owns the loop:
+ *   hdy_nms_grid_begin   keys, sort, cell index.  boxes_scores [M][5] = (x1, y1, x2, y2, score) fp32.
+ *   hdy_nms_grid_round   n_rounds launches, numbered first_round, first_round + 1, ...: the caller continues the numbering in the next call.
+ *                        A round that finds nothing undecided does nothing.  iou in [0, 1].
+ *   hdy_nms_grid_finish  keep[max_det] (row indices in descending score order, ties by lower row, -1 padded), n_keep[1], and
+ *                        status[3] = {boxes still undecided, non-finite flag, rounds that had work (may vary by one or two between runs: a box may see a
+ *                        neighbour's decision of the same launch; the result cannot)}.  The result is valid when status[0] == 0
+ *                        and status[1] == 0; with status[0] > 0 run more rounds and finish again (finish may be repeated).  status[1] != 0:
+ *                        a coordinate or a side length is not finite, the index cannot serve the set, use hdy_nms_boxes.
+ * workspace (16-byte aligned): hdy_nms_grid_workspace_bytes(M), a function of M alone; the same buffer, untouched in between, for the
+ * three calls.  1 <= M <= HDY_NMS_GRID_MAX_M.  Cost: a box visits the cells its extent covers on every occupied level, so the work follows the
+ * number of overlapping pairs; a box that would visit more cells than there are higher-ranked boxes scans those instead (O(M) for that box
+ * per round).  A chain of n boxes each suppressing the next takes n rounds.  All boxes piled on one spot is the quadratic worst case, as
+ * for any NMS.  Results do not depend on the order in which atomics arrive: same input, same bits. */
+#define HDY_NMS_GRID_MAX_M (1 << 24)
+size_t hdy_nms_grid_workspace_bytes(int M);
+int hdy_nms_grid_begin(const float* boxes_scores, int M, void* workspace, size_t ws_bytes, void* stream);
+int hdy_nms_grid_round(int M, float iou, int first_round, int n_rounds, void* workspace, size_t ws_bytes, void* stream);
+int hdy_nms_grid_finish(int M, int max_det, long long* keep, int* n_keep, int* status, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- mask branch primitives ------------------------------------------------------------
  * hdy_roi_align_fwd/bwd replace torchvision.ops.roi_align as the reference calls it (metayolo/models/yolo_head.py:243 on ground
