@@ -5,7 +5,8 @@
     build_model(path | state | Model, ref_model=None, half=True, extra_configs={}) -> (model, deployed)
     attempt_load_model(path | [paths], ...)                                        -> single pair, or (Ensemble, Ensemble)
     inference_on_loader_yolov5(deployed, loader, device, input_size=640, compute_masks=False) -> (results, seconds per image)
-    inference_on_slide(deployed, slide (3, H, W), tile=640, overlap=64, ...)       -> one merged {'boxes','scores','labels'} per task
+    inference_on_slide(deployed, slide, tile=640, overlap=64, ...)                 -> one merged {'boxes','scores','labels'} per task
+                       (slide on the GPU: float (3, H, W) in 0..1, or 8-bit (H, W, 3 | 4) as slide readers deliver it)
 
 What differs from the reference, on purpose: `torch.jit.script(Deploy(model))` has no counterpart — the eval launch list of the
 wrapped Model is the deployed artefact (yolo.Deploy) —, checkpoints may hold state_dicts instead of pickled modules
@@ -13,7 +14,7 @@ wrapped Model is the deployed artefact (yolo.Deploy) —, checkpoints may hold s
 hot path.  Timing brackets exactly what the reference brackets (:98-105: resize + model call), with a device
 synchronisation on both sides because HIP launches are asynchronous.
 
-    python evaluation.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--weights w.pt] [--slide 2048]
+    python evaluation.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--weights w.pt] [--slide 2048 [--u8] [--min-tissue 0.05]]
 """
 import argparse
 import os
@@ -113,13 +114,59 @@ def slide_rois(height, width, tile, overlap):
     return [(x0, y0) for y0 in starts(height) for x0 in starts(width)]
 
 
+def slide_tile_table(height, width, tile, overlap, counts=None, min_tissue=0.0):
+    """Host side of the device tile table of an 8-bit slide: int32 array (n, 2) of (x0, y0) in the order of slide_rois.  With per-tile
+    tissue counts (ops.slide_tissue: pixels of the window that are not background) the rows with count < min_tissue * tile * tile are
+    dropped.  The rule is this project's own: the reference has no blank-tile skipping."""
+    import numpy as np
+    table = np.asarray(slide_rois(height, width, tile, overlap), dtype=np.int32).reshape(-1, 2)
+    if counts is not None and min_tissue > 0.0:
+        counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+        assert len(counts) == len(table), (len(counts), len(table))
+        table = table[counts >= float(min_tissue) * tile * tile]
+    return table
+
+
+def _check_slide(slide):
+    """what inference_on_slide accepts, said in one place (a clear error here instead of an assert deep inside a launch wrapper)"""
+    if not isinstance(slide, torch.Tensor):
+        raise TypeError(f'inference_on_slide: slide must be a torch tensor on the GPU, got {type(slide).__name__}')
+    if not slide.is_cuda:
+        raise ValueError('inference_on_slide: the slide must be on the GPU (slide.cuda()): a float (3, H, W) tensor in 0..1, or the 8-bit '
+                         '(H, W, 3) RGB / (H, W, 4) RGBA tensor a slide reader delivers')
+    if slide.dtype == torch.uint8:
+        ok = slide.dim() == 3 and slide.shape[2] in (3, 4) and slide.stride(2) == 1 and slide.stride(1) == slide.shape[2] \
+            and (slide.shape[0] <= 1 or slide.stride(0) >= slide.shape[1] * slide.shape[2]) and slide.numel() > 0
+        if not ok:
+            raise ValueError(f'inference_on_slide: an 8-bit slide must be (H, W, 3) RGB or (H, W, 4) RGBA with interleaved pixels and dense '
+                             f'rows (stride(2) == 1, stride(1) == C, any row stride); got shape {tuple(slide.shape)}, strides '
+                             f'{tuple(slide.stride())}.  A planar (3, H, W) uint8 tensor is not accepted: pass slide.permute(1, 2, 0).contiguous() '
+                             f'or a float (3, H, W) tensor')
+        return True
+    if not slide.is_floating_point() or slide.dim() != 3:
+        raise ValueError(f'inference_on_slide: a slide is a float (3, H, W) tensor in 0..1 or an 8-bit (H, W, 3 | 4) tensor, got {slide.dtype} '
+                         f'{tuple(slide.shape)}')
+    return False
+
+
 @torch.no_grad()
-def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=1.0, iou_thres=None, compute_masks=False):
+def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=1.0, iou_thres=None, compute_masks=False, min_tissue=0.0,
+                       background=220):
     """Whole-slide detection as the reference's ROI protocol composes it: tiles of one amplification are run in batches, each tile's
     detections carry their 'roi' offset, `Detect.merge_outputs` shifts and concatenates them (yolo_head.py:450-462), overlapping
     windows are de-duplicated by one class-agnostic NMS on the MI355X kernel (as Ensemble.merge does, yolo.py:189-199), and
-    `Detect.rescale_outputs` maps the boxes to another amplification (:464-471).  slide: (3, H, W) float in 0..1 on the GPU."""
-    assert slide.dim() == 3 and slide.is_cuda
+    `Detect.rescale_outputs` maps the boxes to another amplification (:464-471).
+
+    slide, on the GPU: (3, H, W) float in 0..1, or the slide as readers deliver it — uint8 (H, W, 3) RGB or (H, W, 4) RGBA (alpha ignored)
+    with interleaved pixels and any row stride, so a crop of a larger slide is a view.  The 8-bit slide is never converted as a whole:
+    tiles are gathered straight into the network's input buffer (pixel / 255, correctly rounded), and for single-label headers without
+    masks the detections stay on the device until the merge — one read of a device cursor per slide, none per batch.
+    min_tissue > 0 (8-bit slides only; not in the reference): tiles with fewer than min_tissue * tile * tile pixels that are not
+    background are skipped, a pixel being background when min(R, G, B) >= background.  0.0 keeps every tile and launches nothing."""
+    if _check_slide(slide):
+        return _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background)
+    if min_tissue:
+        raise ValueError('inference_on_slide: min_tissue applies to 8-bit slides (the background rule is defined on 8-bit RGB values)')
     inner = model._model if isinstance(model, Deploy) else model
     _, H, W = slide.shape
     rois = slide_rois(H, W, tile, overlap)
@@ -134,18 +181,70 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
         for (x0, y0), out in zip(chunk, outputs):
             for task_id, o in out.items():
                 per_task.setdefault(task_id, []).append(dict(o, roi=(float(x0), float(y0))))
-    merged = {}
-    for task_id, parts in per_task.items():
+    merged = {task_id: inner.headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres)
+
+
+def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres):
+    """everything after the merge: de-duplication of overlapping windows, clamp to the slide, rescale"""
+    out = {}
+    for task_id, r in merged.items():
         header = inner.headers[task_id]
-        r = header.merge_outputs(parts)
         thr = header.nms_params['iou_thres'] if iou_thres is None else iou_thres
         if len(r['boxes']) and overlap > 0:
             keep = nms(r['boxes'], r['scores'], thr)
             r = {k: v[keep] for k, v in r.items()}
         r['boxes'][:, [0, 2]] = r['boxes'][:, [0, 2]].clamp(0, W)
         r['boxes'][:, [1, 3]] = r['boxes'][:, [1, 3]].clamp(0, H)
-        merged[task_id] = header.rescale_outputs(r, scale)
-    return merged
+        out[task_id] = header.rescale_outputs(r, scale)
+    return out
+
+
+def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background):
+    from hd_yolo_amd import ops
+    if isinstance(model, Ensemble):
+        raise NotImplementedError('inference_on_slide: 8-bit slides run on one model (Model / Deploy); an Ensemble takes the float slide')
+    inner = model._model if isinstance(model, Deploy) else model
+    H, W, _ = slide.shape
+    dev = slide.device
+    table = slide_tile_table(H, W, tile, overlap)
+    origins = ops.slide_origins(table, dev)                              # one upload per slide
+    if min_tissue > 0.0:
+        counts = ops.slide_tissue(slide, origins, tile, tile, background).cpu().numpy()      # one read, before the first batch
+        table = slide_tile_table(H, W, tile, overlap, counts, min_tissue)
+        origins = ops.slide_origins(table, dev) if len(table) else None
+    n = len(table)
+    headers = inner.headers
+    on_device = not any(h.multi_label for h in headers.values()) and not (compute_masks and any(getattr(h, 'nc_masks', 0) > 0 for h in headers.values()))
+    if on_device:
+        # slide-wide arrays per task, tiles x max_det rows (an exact upper bound), and a device cursor: every batch appends behind it
+        acc = {}
+        for task_id, h in headers.items():
+            cap = max(n, 1) * int(h.nms_params['max_det'])
+            acc[task_id] = (torch.empty((cap, 4), dtype=torch.float32, device=dev), torch.empty((cap,), dtype=torch.float32, device=dev),
+                            torch.empty((cap,), dtype=torch.int64, device=dev), torch.zeros((2,), dtype=torch.int32, device=dev))
+        for i in range(0, n, batch_size):
+            count = min(batch_size, n - i)                               # the last, smaller chunk runs at its own size
+            _, outputs = model.forward_tiles(slide, origins, i, count, (tile, tile), compute_masks=False, device_outputs=True)
+            for task_id, (boxes, scores, labels, n_keep) in outputs.items():
+                ops.slide_append(boxes, scores, labels, n_keep, origins, i, *acc[task_id])
+        merged = {}
+        for task_id, (boxes, scores, labels, cursor) in acc.items():
+            rows, overflow = cursor.tolist()                             # the one device-to-host read of the slide (per task)
+            if overflow:
+                raise RuntimeError(f'inference_on_slide: the detections of task {task_id!r} passed the capacity of {len(scores)} rows')
+            merged[task_id] = {'boxes': boxes[:rows], 'labels': labels[:rows], 'scores': scores[:rows]}
+    else:
+        # multi-label rows and masks keep the Python merge; their tiles still come from the 8-bit slide
+        per_task = {}
+        for i in range(0, n, batch_size):
+            count = min(batch_size, n - i)
+            _, outputs = model.forward_tiles(slide, origins, i, count, (tile, tile), compute_masks=compute_masks)
+            for (x0, y0), out in zip(table[i:i + count].tolist(), outputs):
+                for task_id, o in out.items():
+                    per_task.setdefault(task_id, []).append(dict(o, roi=(float(x0), float(y0))))
+        merged = {task_id: headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres)
 
 
 def main():
@@ -158,6 +257,8 @@ def main():
     ap.add_argument('--batch-size', type=int, default=32)
     ap.add_argument('--batches', type=int, default=4)
     ap.add_argument('--slide', type=int, default=0, help='also run one synthetic SxS slide through inference_on_slide')
+    ap.add_argument('--u8', action='store_true', help='--slide: the synthetic slide as an 8-bit (H, W, 3) tensor (from the same seed), the way a slide reader delivers it')
+    ap.add_argument('--min-tissue', type=float, default=0.0, help='--slide --u8: skip tiles with less than this fraction of non-background pixels')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
     opt = ap.parse_args()
@@ -179,9 +280,11 @@ def main():
     print(f'{len(results)} tiles, {n} detections, {spi * 1e3:.3f} ms / tile ({1.0 / spi:.0f} tiles/s incl. host transfer of the results)')
     if opt.slide:
         slide = synth.synth_images(1, opt.slide, seed=5)[0].to(device)
+        if opt.u8:
+            slide = (slide * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous()
         torch.cuda.synchronize()
         t0 = time.time()
-        out = inference_on_slide(deployed.to(device), slide, tile=opt.imgsz, batch_size=opt.batch_size)
+        out = inference_on_slide(deployed.to(device), slide, tile=opt.imgsz, batch_size=opt.batch_size, min_tissue=opt.min_tissue)
         torch.cuda.synchronize()
         print(f'slide {opt.slide}x{opt.slide}: ' + ', '.join(f'{k}: {len(v["boxes"])} detections' for k, v in out.items()) + f' in {(time.time() - t0) * 1e3:.1f} ms')
 

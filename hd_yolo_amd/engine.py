@@ -277,20 +277,26 @@ class Engine:
 
     def plan_for(self, x, training, dtype):
         ops.require_gpu(x)
+        return self.plan_for_shape(tuple(x.shape), x.device, training, dtype)
+
+    def plan_for_shape(self, shape, device, training, dtype):
+        """the plan a tensor of `shape` on `device` runs (plan_for's key): a batch that never exists as such a tensor — tiles gathered from
+        an 8-bit slide — shares the plan of the float batch of the same shape"""
         _lib.load()
-        key = (tuple(x.shape), dtype, bool(training), x.device.index, self._check_and_sign(), bool(self.sync_bn) and bool(training))
+        shape = tuple(shape)
+        key = (shape, dtype, bool(training), device.index, self._check_and_sign(), bool(self.sync_bn) and bool(training))
         plan = self.plans.get(key)
         if plan is None:
             if training and self.store is None:
-                self.store = GradStore(self._params(), x.device)
-                self.hook = torch.zeros(1, device=x.device, requires_grad=True)
+                self.store = GradStore(self._params(), device)
+                self.hook = torch.zeros(1, device=device, requires_grad=True)
             if len(self.plans) >= self.max_plans:
                 self.plans.pop(next(iter(self.plans)))
             b, n, h = self.parts
             tap_params = []
             if self.extra is not None and training:
                 tap_params = [q for m in (self.extra if not isinstance(self.extra, nn.Module) else [self.extra]) for q in m.parameters()]
-            plan = Plan(b, n, h, tuple(x.shape), dtype, training, x.device, grad_store=self.store, taps=self.taps, tap_params=tap_params, sync=self.sync_bn)
+            plan = Plan(b, n, h, shape, dtype, training, device, grad_store=self.store, taps=self.taps, tap_params=tap_params, sync=self.sync_bn)
             plan.bucket_hook = self._bucket_ready
             self.plans[key] = plan
         self.last_plan = plan
@@ -331,6 +337,18 @@ class Engine:
             dets = plan.run_forward(x)
             if plan.tap_keys:
                 self.tap_outputs = plan.tap_features()
+        return plan, list(dets)
+
+    def forward_tiles(self, slide, origins, first, count, tile, dtype):
+        """Eval forward of `count` tiles of an 8-bit device slide (Plan.run_forward_tiles) on the plan of a (count, 3, th, tw) batch."""
+        ops.require_gpu(slide)
+        th, tw = tile
+        plan = self.plan_for_shape((int(count), 3, int(th), int(tw)), slide.device, False, dtype)
+        self.mask_token = None
+        self.tap_outputs = None
+        dets = plan.run_forward_tiles(slide, origins, first, count)
+        if plan.tap_keys:
+            self.tap_outputs = plan.tap_features()
         return plan, list(dets)
 
     def forward_fused_loss(self, x, dtype, head, gts, tcls):

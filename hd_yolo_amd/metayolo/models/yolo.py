@@ -78,6 +78,29 @@ class Model(nn.Module):
                 _, losses = header.fused_losses(self._eng(), x, dtype, gts, compute_masks=compute_masks)
                 return {task_id: losses}, self.post_processing([{task_id: o} for o in []])
         plan, dets = self._eng().forward(x, self.training, dtype)
+        return self._forward_headers(plan, dets, dtype, x.shape[0], x.device, targets, compute_masks)
+
+    @torch.no_grad()
+    def forward_tiles(self, slide, origins, first, count, tile, compute_masks=False, device_outputs=False):
+        """Eval forward of tiles [first, first + count) of an 8-bit slide that lives on the device (uint8 (H, W, 3 | 4), see ops.slide_u8;
+        origins: int32 [n][2] device table of (x0, y0), ops.slide_origins; tile = (th, tw)): the batch is gathered straight into the plan's
+        input buffer, on the SAME plan a float (count, 3, th, tw) tensor would run.  Returns what forward returns, or, with device_outputs,
+        (losses, {task: (boxes, scores, labels, n_keep)}) — the batch's compacted detections and the device `n_keep`, no synchronisation
+        (Detect.compute_outputs_device).  No reference counterpart: the reference's loaders hand float tiles to Model.forward."""
+        if self.training:
+            raise RuntimeError('Model.forward_tiles is eval-only: training batches come from a loader through Model.forward')
+        dtype = _engine.compute_dtype(self, slide)
+        plan, dets = self._eng().forward_tiles(slide, origins, first, count, tile, dtype)
+        if not device_outputs:
+            return self._forward_headers(plan, dets, dtype, count, slide.device, None, compute_masks)
+        outputs, at = {}, 0
+        for task_id, header in self.headers.items():
+            nl = len(header.m)
+            outputs[task_id] = header.compute_outputs_device(header.decode_all(dets[at:at + nl]))
+            at += nl
+        return {}, outputs
+
+    def _forward_headers(self, plan, dets, dtype, batch, device, targets, compute_masks):
         losses, outputs = {}, {}
         first = 0
         for task_id, header in self.headers.items():
@@ -93,8 +116,8 @@ class Model(nn.Module):
                     if task_id in t['anns']:
                         task_gts.extend(t['anns'][task_id])
                         keep.extend([idx] * len(t['anns'][task_id]))
-                if keep != list(range(x.shape[0])):
-                    sel = torch.tensor(keep, device=x.device, dtype=torch.long)
+                if keep != list(range(batch)):
+                    sel = torch.tensor(keep, device=device, dtype=torch.long)
                     task_dets = [d.index_select(0, sel) for d in all_dets]
             mask_ctx = (self._eng(), plan, dtype) if getattr(header, 'nc_masks', 0) > 0 and len(self.headers) == 1 else None
             losses[task_id], outputs[task_id] = header.forward_dets(task_dets, task_gts, compute_masks=compute_masks, mask_ctx=mask_ctx)
@@ -159,6 +182,12 @@ class Deploy(nn.Module):
 
     def post_processing(self, x: Any):
         return x
+
+    @torch.no_grad()
+    def forward_tiles(self, slide, origins, first, count, tile, compute_masks: bool = True, device_outputs: bool = False):
+        """Model.forward_tiles with Deploy.forward's return convention"""
+        _, outputs = self._model.forward_tiles(slide, origins, first, count, tile, compute_masks=compute_masks, device_outputs=device_outputs)
+        return None, (outputs if device_outputs else self.post_processing(outputs))
 
 
 class Ensemble(nn.ModuleList):

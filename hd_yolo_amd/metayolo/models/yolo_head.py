@@ -230,18 +230,10 @@ class Detect(nn.Module):
                               for i, p in enumerate(preds)], 1)
         else:
             flat = preds
-        conf = self.nms_params['conf_thres']
-        max_det = int(self.nms_params['max_det'])
-        # one NMS launch for the batch, then the score / label logic ONCE on the padded (bs * max_det, 1 + nc) rows (rows past an
-        # image's count are scratch and sliced away): the reference's per-image loop (yolo_head.py:313-353) costs ~10 tiny launches
-        # per tile, 17 ms of a 96 ms batch of 128 1024x1024 tiles
         bs = flat.shape[0]
         if bs == 0:
             return []
-        res = _ops.nms_batched(flat.float().contiguous(), self.nc, conf, self.nms_params['iou_thres'], max_det, min_wh=2.0, class_aware=False)
-        # hierarchical scores, best class / objectness fallback and labels for every kept box, compacted over the batch by ONE launch
-        # (hdy_det_outputs) issued before the sync; the host then splits three tensors instead of slicing 3 x bs padded ones
-        boxes_c, scores_c, labels_c = _ops.det_outputs(res, self.nc, conf, self._score_pairs(flat.device), self.multi_label)
+        res, boxes_c, scores_c, labels_c = self._outputs_device(flat)
         n_keep = res['n_keep'].tolist()                    # the one D2H sync of the batch
         total = sum(n_keep)
         results = [{'boxes': b, 'scores': s, 'labels': l} for b, s, l in
@@ -249,6 +241,25 @@ class Detect(nn.Module):
         if compute_masks and sum(n_keep) > 0 and not self.multi_label:
             self.attach_masks(results, res, n_keep, features)
         return results
+
+    def compute_outputs_device(self, flat):
+        """compute_outputs without its synchronisation: (boxes (bs * max_det, 4), scores, labels, n_keep int32 (bs,)) on the device, the
+        batch's detections compacted (image b's rows start at n_keep[0] + .. + n_keep[b - 1]; rows past the total are scratch).  For callers
+        that keep going on the device (the whole-slide append, ops.slide_append)."""
+        res, boxes_c, scores_c, labels_c = self._outputs_device(flat)
+        return boxes_c, scores_c, labels_c, res['n_keep']
+
+    def _outputs_device(self, flat):
+        conf = self.nms_params['conf_thres']
+        max_det = int(self.nms_params['max_det'])
+        # one NMS launch for the batch, then the score / label logic ONCE on the padded (bs * max_det, 1 + nc) rows (rows past an
+        # image's count are scratch and sliced away): the reference's per-image loop (yolo_head.py:313-353) costs ~10 tiny launches
+        # per tile, 17 ms of a 96 ms batch of 128 1024x1024 tiles
+        res = _ops.nms_batched(flat.float().contiguous(), self.nc, conf, self.nms_params['iou_thres'], max_det, min_wh=2.0, class_aware=False)
+        # hierarchical scores, best class / objectness fallback and labels for every kept box, compacted over the batch by ONE launch
+        # (hdy_det_outputs) issued before the sync; the host then splits three tensors instead of slicing 3 x bs padded ones
+        boxes_c, scores_c, labels_c = _ops.det_outputs(res, self.nc, conf, self._score_pairs(flat.device), self.multi_label)
+        return res, boxes_c, scores_c, labels_c
 
     def attach_masks(self, results, res, n_keep, mask_ctx):
         """multiscale_roi_align over the detections (each from the level that produced it) -> Mask R-CNN head -> sigmoid -> the

@@ -713,6 +713,83 @@ def rec_nchw_to_nhwc(src, dst):
     return _rec(locals(), 'hdy_nchw_to_nhwc', (src.data_ptr(), dp, ldd, N, C, H, W, dcode(dst.dtype)))
 
 
+# ------------------------------------------------------------------------------------------ whole-slide inference from an 8-bit slide
+def slide_u8(slide):
+    """(ptr, row pitch in bytes, pixel_bytes, H, W) of an 8-bit slide as readers deliver it: a CUDA uint8 tensor (H, W, 3) RGB or
+    (H, W, 4) RGBA with stride(2) == 1, stride(1) == C and any row stride (a crop of a larger slide is a view, not a copy)."""
+    if not isinstance(slide, torch.Tensor) or slide.dtype != torch.uint8:
+        raise _lib.HdyError(f'8-bit slide: a torch.uint8 tensor is expected, got {getattr(slide, "dtype", type(slide).__name__)}')
+    require_gpu(slide)
+    if slide.dim() != 3 or slide.shape[2] not in (3, 4):
+        raise _lib.HdyError(f'8-bit slide: shape (H, W, 3) RGB or (H, W, 4) RGBA is expected (pixels interleaved, as slide readers deliver '
+                            f'them), got {tuple(slide.shape)}')
+    H, W, C = slide.shape
+    if H == 0 or W == 0:
+        raise _lib.HdyError(f'8-bit slide: empty slide {tuple(slide.shape)}')
+    if slide.stride(2) != 1 or slide.stride(1) != C or (H > 1 and slide.stride(0) < W * C):
+        raise _lib.HdyError(f'8-bit slide: pixels must be interleaved and rows dense (stride(2) == 1, stride(1) == {C}, any row stride >= '
+                            f'{W * C}), got strides {tuple(slide.stride())}')
+    return slide.data_ptr(), int(slide.stride(0)) if H > 1 else W * C, C, H, W
+
+
+def slide_origins(origins, device):
+    """the device table of tile origins, int32 [n][2] = (x0, y0): uploaded once per slide"""
+    t = torch.as_tensor(origins, dtype=torch.int32).reshape(-1, 2).contiguous()
+    return t.to(device)
+
+
+def _origin_table(origins):
+    require_gpu(origins)
+    assert origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous(), 'origins: int32 [n][2]'
+    return origins.data_ptr(), origins.shape[0]
+
+
+def rec_slide_tiles(slide, origins, first, count, out, pad=2):
+    """Launch record (next to rec_stem_prep / rec_nchw_to_nhwc): tiles [first, first + count) of the 8-bit slide into `out`, either the
+    contiguous stem buffer (count, th + 2 pad, tw + 2 pad, 4) or a pitched NHWC view (count, th, tw, 3) of a wider buffer (pad = 0)."""
+    sp, pitch, pb, H, W = slide_u8(slide)
+    op_, n = _origin_table(origins)
+    require_gpu(out)
+    assert out.dim() == 4 and out.shape[0] == count, (tuple(out.shape), count)
+    if out.is_contiguous() and out.shape[3] == 4:
+        th, tw, ldd = out.shape[1] - 2 * pad, out.shape[2] - 2 * pad, 0
+        elems = out.numel()
+    else:
+        _, _, th, tw, C, ldd = nhwc(out)
+        assert C == 3 and pad == 0, 'a pitched NHWC input takes the 3 colour channels and no frame'
+        elems = count * th * tw * ldd
+    return _rec(locals(), 'hdy_slide_tiles_u8', (sp, pitch, pb, H, W, op_, n, int(first), int(count), out.data_ptr(), elems, th, tw, pad, ldd,
+                                                 dcode(out.dtype)))
+
+
+def slide_append(boxes, scores, labels, n_keep, origins, first, out_boxes, out_scores, out_labels, cursor):
+    """Append a batch's compacted single-label detections (det_outputs) to the slide-wide arrays at the device cursor (int32 [2]: rows,
+    overflow flag), each box shifted by its tile's origin (hdy_slide_append).  No synchronisation."""
+    op_, n = _origin_table(origins)
+    B = n_keep.shape[0]
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 2 and boxes.shape[1] == 4
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.dim() == 1 and labels.dtype == torch.int64 and labels.is_contiguous() \
+        and labels.dim() == 1, 'single-label detections only (multi-label rows keep the Python merge)'
+    assert scores.shape[0] == labels.shape[0] == boxes.shape[0] and n_keep.dtype == torch.int32 and n_keep.is_contiguous()
+    cap = out_boxes.shape[0]
+    assert out_boxes.dtype == torch.float32 and out_boxes.is_contiguous() and tuple(out_boxes.shape) == (cap, 4)
+    assert out_scores.dtype == torch.float32 and out_scores.is_contiguous() and tuple(out_scores.shape) == (cap,)
+    assert out_labels.dtype == torch.int64 and out_labels.is_contiguous() and tuple(out_labels.shape) == (cap,)
+    assert cursor.dtype == torch.int32 and cursor.is_contiguous() and cursor.numel() == 2
+    _call('hdy_slide_append', ptr(boxes), ptr(scores), ptr(labels), ptr(n_keep), B, boxes.shape[0], op_, n, int(first), ptr(out_boxes),
+          ptr(out_scores), ptr(out_labels), cap, ptr(cursor))
+
+
+def slide_tissue(slide, origins, th, tw, background=220):
+    """int32 [n] device tensor: per tile of the origin table, the pixels of its th x tw window (clipped to the slide) that are not
+    background — background: min(R, G, B) >= `background` (hdy_slide_tissue_u8; this rule is this project's, the reference has none)."""
+    sp, pitch, pb, H, W = slide_u8(slide)
+    op_, n = _origin_table(origins)
+    counts = torch.empty((n,), dtype=torch.int32, device=slide.device)
+    _call('hdy_slide_tissue_u8', sp, pitch, pb, H, W, op_, n, int(th), int(tw), int(background), counts.data_ptr(), n)
+    return counts
+
+
 # ------------------------------------------------------------------------------------------ detection head
 def decode_level(det, anchor_px, stride, out, row_offset, level_id):
     """det: fp32 logits viewed as (B, na, ny, nx, no) with o contiguous (any other strides)."""

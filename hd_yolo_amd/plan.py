@@ -561,6 +561,20 @@ class Plan:
             images = images.float().contiguous()
         assert tuple(images.shape) == (self.B, self.Cin, self.H, self.W), (images.shape, self.B, self.H, self.W)
         assert images.shape[1] == self.Cin
+        return self._run_forward(ops.rec_stem_prep(images, self.prep) if self.input is None else ops.rec_nchw_to_nhwc(images, self.input.t()))
+
+    def run_forward_tiles(self, slide, origins, first, count):
+        """run_forward with the batch taken from an 8-bit slide on the device: tiles [first, first + count) of the origin table (int32 [n][2]
+        device tensor of (x0, y0)) are gathered straight into the buffer the first convolution reads (hdy_slide_tiles_u8) — no float slide,
+        no NCHW batch, no stem_prep pass."""
+        if count != self.B or self.Cin != 3:
+            raise _lib.HdyError(f'run_forward_tiles: {count} tiles of 3 channels for a plan of batch {self.B} with {self.Cin} input channels')
+        if self.input is None:
+            return self._run_forward(ops.rec_slide_tiles(slide, origins, first, count, self.prep))
+        return self._run_forward(ops.rec_slide_tiles(slide, origins, first, count, self.input.t(), pad=0))
+
+    def _run_forward(self, input_rec):
+        """the forward list behind the record that fills the first convolution's input buffer"""
         pack_side = self.training and PACK_SIDE
         if pack_side:
             # the per-step weight re-pack (one launch, ~50 us of gathers at yolov5s) depends on the optimizer's update, not on the images: it runs on a
@@ -571,10 +585,7 @@ class Plan:
             self._pack_stream.wait_stream(main)
             with torch.cuda.stream(self._pack_stream):
                 self.packs.run(skip_unchanged=False)
-        if self.input is None:
-            ops.run([ops.rec_stem_prep(images, self.prep)])
-        else:
-            ops.run([ops.rec_nchw_to_nhwc(images, self.input.t())])
+        ops.run([input_rec])
         if pack_side:
             main.wait_stream(self._pack_stream)
         else:

@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 7
+#define HDY_ABI_VERSION 8
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -297,6 +297,39 @@ size_t hdy_nms_grid_workspace_bytes(int M);
 int hdy_nms_grid_begin(const float* boxes_scores, int M, void* workspace, size_t ws_bytes, void* stream);
 int hdy_nms_grid_round(int M, float iou, int first_round, int n_rounds, void* workspace, size_t ws_bytes, void* stream);
 int hdy_nms_grid_finish(int M, int max_det, long long* keep, int* n_keep, int* status, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- whole-slide inference from an 8-bit slide (csrc/slide.hip) ----------------------------------------------------------------
+ * The slide stays as slide readers deliver it: 8-bit pixels [H][pitch_bytes] on the device, pixel_bytes = 3 (RGB) or 4 (RGBA, alpha ignored),
+ * an explicit row pitch in BYTES (>= W * pixel_bytes: a cropped view of a larger slide needs no copy), addressed in 64 bits.  Tiles are named
+ * by a device table origins int32 [n_origins][2] = (x0, y0) of their top-left corners, uploaded once per slide; the kernels are memory-safe
+ * for any table content (a window or a part of it outside the slide reads as zero / counts nothing).
+ *
+ * hdy_slide_tiles_u8 replaces the reference's per-ROI crop + `/ 255` normalisation + NCHW batch in front of the model call (the ROI protocol
+ * around Detect.merge_outputs, metayolo/models/yolo_head.py:450-462; images are normalised with `/ 255` in val_nuclei.py:137) and this
+ * library's own hdy_stem_prep / hdy_nchw_to_nhwc behind it: tiles [first, first + count) of the table go straight into the buffer the first
+ * convolution reads.  ldd == 0: the hdy_stem_prep layout [count][th + 2 pad][tw + 2 pad][4] (zero frame, zero 4th channel), out 16-byte
+ * aligned; ldd >= 3 (pad must be 0): pitched NHWC [count][th][tw][ldd], channels 0..2 written, as hdy_nchw_to_nhwc writes a 3-channel image.
+ * Pixel value: float(v) / 255 correctly rounded to fp32 (a 256-entry table made on the host with IEEE division; NOT v * (1 / 255)), then
+ * converted to dtype as every other kernel converts.  out_elems = elements of dtype `out` holds: HDY_EINVAL unless it is exactly what the call
+ * writes.  Source bytes are read as whole aligned dwords: up to 3 bytes beside a row's pixels (never outside their page) may be read.
+ *
+ * hdy_slide_append replaces Detect.merge_outputs (yolo_head.py:450-462: per ROI `boxes + (x0, y0, x0, y0)`, then cat): the batch's compacted
+ * detections (hdy_det_outputs, single label: boxes [in_rows][4], scores [in_rows], labels int64 [in_rows], tile b's rows at
+ * n_keep[0] + .. + n_keep[b - 1]; B <= 1024 tiles = rows [first, first + B) of the table) are appended to slide-wide arrays of `capacity` rows at
+ * cursor[0], each box shifted by its tile's origin with one fp32 add per coordinate, in tile order then row order; cursor[0] moves by the rows
+ * written.  cursor int32 [2] lives on the device (zeroed by the caller before the first batch): rows that would pass `capacity` (or lie beyond
+ * in_rows) are dropped and cursor[1] is set to 1 — nothing is written past the end.  One workgroup, no atomics: repeats are bit-identical, and a
+ * slide needs no device-to-host copy per batch.
+ *
+ * hdy_slide_tissue_u8 (no reference counterpart: the reference has no blank-tile rule): counts[t] = pixels of tile t's th x tw window, clipped
+ * to the slide, that are NOT background, a pixel being background when min(R, G, B) >= background.  Exact integer counts, one workgroup per
+ * tile; n_counts must equal n_origins. */
+int hdy_slide_tiles_u8(const unsigned char* slide, long long pitch_bytes, int pixel_bytes, int H, int W, const int* origins, int n_origins,
+                       int first, int count, void* out, long long out_elems, int th, int tw, int pad, int ldd, int dtype, void* stream);
+int hdy_slide_append(const float* boxes, const float* scores, const long long* labels, const int* n_keep, int B, int in_rows, const int* origins,
+                     int n_origins, int first, float* out_boxes, float* out_scores, long long* out_labels, int capacity, int* cursor, void* stream);
+int hdy_slide_tissue_u8(const unsigned char* slide, long long pitch_bytes, int pixel_bytes, int H, int W, const int* origins, int n_origins, int th,
+                        int tw, int background, int* counts, int n_counts, void* stream);
 
 /* ---- mask branch primitives ------------------------------------------------------------
  * hdy_roi_align_fwd/bwd replace torchvision.ops.roi_align as the reference calls it (metayolo/models/yolo_head.py:243 on ground

@@ -2,7 +2,15 @@
 
     python scripts/bench_slide.py --ab [--out profiles/nms_grid_ab.txt]      one-workgroup kernel (ops._nms_launch) vs ops.nms_grid
     python scripts/bench_slide.py --slide 20000 [--grid-min 0]                synthetic slide -> evaluation.inference_on_slide
+    python scripts/bench_slide.py --slide 20000 --u8 [--min-tissue 0.05]      the same from a synthetic 8-bit (H, W, 3) slide (tile gather + device merge)
+    python scripts/bench_slide.py --slide-ab 8000 20000 [--out profiles/slide_u8_ab.txt]   float path vs 8-bit path on the same pixels
     python scripts/bench_slide.py --once 262144                               one nms_grid call (for a kernel trace of its own)
+
+--slide-ab: per size one random 8-bit slide on the device and three ways through evaluation.inference_on_slide, alternating, after a warm-up of
+each: "float" = the float path fed table[v] as float CHW already on the device (its best case), "convert + float" = the same with the
+conversion a caller of the float path needs (8-bit HWC -> float CHW on the device) inside the timed region, "8-bit" = the slide as it is.
+Wall time around each call between device synchronisations; merge NMS timed inside by two more synchronisations (all sides alike);
+peak device memory per side = the slide it reads + the call's own peak (torch.cuda.max_memory_allocated above the resident set).
 
 --ab: both paths on the same device tensors in one process, alternating, after a warm-up call of each; device events around each call (both
 end in a synchronising read of the kept count); median and min-max over --repeats.  Sets: slide (objects of 12-30 px detected 1-3 times,
@@ -89,7 +97,8 @@ def ab(opt):
     print(text)
 
 
-def slide(opt):
+def _slide_setup(opt):
+    """(evaluation module, deployed yolov5 on the device, merge-NMS stopwatch)"""
     import evaluation
     from metayolo.models.yolo import Model
     dev = torch.device('cuda', 0)
@@ -112,19 +121,99 @@ def slide(opt):
         return r
 
     evaluation.nms = timed_nms
+    return evaluation, deployed, merge, dev
+
+
+def u8_slide(S, dev, seed=5):
+    """synthetic 8-bit slide (S, S, 3) from a seed, made on the device"""
+    return torch.randint(0, 256, (S, S, 3), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(seed))
+
+
+def float_of(u8):
+    """table[v] as float CHW, table = arange(256) / 255 made on the CPU (the 8-bit path's pixel values, bit for bit), in row strips"""
+    table = (torch.arange(256).float() / 255).to(u8.device)
+    out = torch.empty((3,) + tuple(u8.shape[:2]), dtype=torch.float32, device=u8.device)
+    for r in range(0, u8.shape[0], 1024):
+        out[:, r:r + 1024] = table[u8[r:r + 1024, :, :3].long()].permute(2, 0, 1)
+    return out
+
+
+def slide_ab(opt):
+    evaluation, deployed, merge, dev = _slide_setup(opt)
+    kw = dict(tile=opt.tile, overlap=opt.overlap, batch_size=opt.batch_size)
+    lines = ['command: python ' + ' '.join(sys.argv),
+             f'device: {torch.cuda.get_device_name(0)}; yolov5{opt.variant}, tile {opt.tile}, overlap {opt.overlap}, batch {opt.batch_size}; times in ms, '
+             f'median [min .. max] over {opt.repeats} repeats, sides alternating; peak = the slide a side reads + what the call allocates on top (torch.cuda.max_memory_allocated), MB']
+    for S in opt.slide_ab:
+        u8 = u8_slide(S, dev)
+        flt = float_of(u8)
+        sides = {
+            'float CHW on device (old)': lambda: evaluation.inference_on_slide(deployed, flt, **kw),
+            'convert + float (old)': lambda: evaluation.inference_on_slide(deployed, u8.permute(2, 0, 1).float().div_(255), **kw),
+            '8-bit HWC (new)': lambda: evaluation.inference_on_slide(deployed, u8, **kw),
+        }
+        rec = {k: {'net': [], 'merge': [], 'total': [], 'peak': 0, 'kept': 0} for k in sides}
+        for fn in sides.values():
+            fn()                                                          # plans, allocator
+        for _ in range(opt.repeats):
+            for k, fn in sides.items():
+                merge.update(ms=0.0, boxes=0)
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                t0 = time.time()
+                out = fn()
+                torch.cuda.synchronize()
+                total = (time.time() - t0) * 1e3
+                r = rec[k]
+                r['net'].append(total - merge['ms'])
+                r['merge'].append(merge['ms'])
+                r['total'].append(total)
+                reads = flt if k.startswith('float') else u8             # both slides are resident throughout: count the one this side reads
+                r['peak'] = max(r['peak'], (torch.cuda.max_memory_allocated() - base + reads.numel() * reads.element_size()) >> 20)
+                r['kept'] = sum(len(v['boxes']) for v in out.values())
+                del out
+        tiles = len(evaluation.slide_rois(S, S, opt.tile, opt.overlap))
+        lines.append(f'slide {S} x {S}: {tiles} tiles')
+        lines.append(f'  {"side":28s} {"network + tiling":>34s}  {"merge NMS":>34s}  {"total":>34s}  {"peak MB":>8s}  {"kept":>8s}')
+        for k, r in rec.items():
+            lines.append(f'  {k:28s} {stats(r["net"]):>34s}  {stats(r["merge"]):>34s}  {stats(r["total"]):>34s}  {r["peak"]:8d}  {r["kept"]:8d}')
+        new, old, conv = rec['8-bit HWC (new)'], rec['float CHW on device (old)'], rec['convert + float (old)']
+        lines.append(f'  new slowest total < old fastest total: {"yes" if max(new["total"]) < min(old["total"]) else "no"}'
+                     f' (float on device), {"yes" if max(new["total"]) < min(conv["total"]) else "no"} (convert + float)')
+        print('\n'.join(lines[-6:]), flush=True)
+        del u8, flt, sides
+        torch.cuda.empty_cache()
+    text = '\n'.join(lines) + '\n'
+    if opt.out:
+        os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
+        with open(opt.out, 'w') as f:
+            f.write(text)
+    print(text)
+
+
+def slide(opt):
+    evaluation, deployed, merge, dev = _slide_setup(opt)
     S = opt.slide
-    img = torch.rand((3, S, S), device=dev, generator=torch.Generator(device=dev).manual_seed(5))
-    warm = img[:, :min(S, 1280), :min(S, 1280)].contiguous()
-    evaluation.inference_on_slide(deployed, warm, tile=opt.tile, overlap=opt.overlap, batch_size=opt.batch_size)        # plans, allocator
+    extra = {}
+    if opt.u8:
+        img = u8_slide(S, dev)
+        warm = img[:min(S, 1280), :min(S, 1280)].contiguous()
+        extra = dict(min_tissue=opt.min_tissue)
+    else:
+        img = torch.rand((3, S, S), device=dev, generator=torch.Generator(device=dev).manual_seed(5))
+        warm = img[:, :min(S, 1280), :min(S, 1280)].contiguous()
+    evaluation.inference_on_slide(deployed, warm, tile=opt.tile, overlap=opt.overlap, batch_size=opt.batch_size, **extra)        # plans, allocator
     merge.update(ms=0.0, boxes=0)
     torch.cuda.synchronize()
     t0 = time.time()
-    out = evaluation.inference_on_slide(deployed, img, tile=opt.tile, overlap=opt.overlap, batch_size=opt.batch_size)
+    torch.cuda.reset_peak_memory_stats()
+    out = evaluation.inference_on_slide(deployed, img, tile=opt.tile, overlap=opt.overlap, batch_size=opt.batch_size, **extra)
     torch.cuda.synchronize()
     total = (time.time() - t0) * 1e3
     tiles = len(evaluation.slide_rois(S, S, opt.tile, opt.overlap))
     kept = sum(len(v['boxes']) for v in out.values())
-    print(f'slide {S}x{S}: {tiles} tiles, HDY_NMS_GRID_MIN={os.environ.get("HDY_NMS_GRID_MIN", "default " + str(ops.NMS_GRID_MIN))}, '
+    print(f'slide {S}x{S}{" 8-bit" if opt.u8 else ""}: {tiles} tiles, peak {torch.cuda.max_memory_allocated() >> 20} MB, HDY_NMS_GRID_MIN={os.environ.get("HDY_NMS_GRID_MIN", "default " + str(ops.NMS_GRID_MIN))}, '
           f'{merge["boxes"]} merged boxes -> {kept} kept; network + tiling {total - merge["ms"]:.1f} ms, merge NMS {merge["ms"]:.1f} ms, total {total:.1f} ms')
 
 
@@ -142,6 +231,9 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--ab', action='store_true')
     ap.add_argument('--slide', type=int, default=0)
+    ap.add_argument('--u8', action='store_true', help='--slide: a synthetic 8-bit (S, S, 3) slide from the seed, through the tile gather and the device merge')
+    ap.add_argument('--min-tissue', type=float, default=0.0, help='--slide --u8: skip tiles with less than this fraction of non-background pixels')
+    ap.add_argument('--slide-ab', type=int, nargs='*', default=[], help='sizes for the float path vs 8-bit path comparison')
     ap.add_argument('--once', type=int, default=0)
     ap.add_argument('--repeats', type=int, default=9)
     ap.add_argument('--old-max', type=int, default=140000, help='largest set the one-workgroup kernel is timed on repeatedly')
@@ -157,6 +249,8 @@ if __name__ == '__main__':
     opt = ap.parse_args()
     if opt.ab:
         ab(opt)
+    if opt.slide_ab:
+        slide_ab(opt)
     if opt.slide:
         slide(opt)
     if opt.once:
