@@ -29,3 +29,99 @@ class SyntheticTiles:
             if self.device is not None:
                 x = x.to(self.device, non_blocking=True)
             yield tuple(x.unbind(0)), t
+
+
+class DeviceTiles:
+    """Training batches augmented on the device from an 8-bit tile bank (hd_yolo_amd.augment.TileBank): the reference's training branch
+    (metayolo/datasets.py TorchDataset.__getitem__ with train_proc: HSV, random projective, flips, k x k mosaic, random crop, small-object
+    filter, normalised boxes) as two launches per batch (csrc/augment.hip).  Iterable like SyntheticTiles; yields (imgs, targets): imgs a
+    tuple of (3, S, S) views of one (B, 3, S, S) `dtype` tensor in 0..1, targets the per-image dicts of the reference's schema with device
+    tensors (views of the batch's compact arrays).
+
+    `hyp` carries the reference's keys (degrees translate scale shear perspective hsv_h hsv_s hsv_v fliplr flipud transpose cval k_mosaic
+    patch_size img_size); a missing one raises KeyError.  `cval` is the border value as the reference hands it to cv2 on an 8-bit image
+    (rounded half to even and clamped to 0..255).  Mask targets, keep_res > 0, color_aug other than 'hsv' and albumentations are refused.
+
+    The loader works on its own stream, one batch ahead: batch i + 1 is issued before batch i is handed out, and the per-image row counts —
+    the only device-to-host copy, one per batch — are waited for through an event recorded a whole step earlier.  Two buffer sets
+    alternate: a batch is valid until the next one is handed out.  Every (seed, rank, epoch, step) has its own numpy Generator, mixed as
+    SyntheticTiles mixes them."""
+
+    def __init__(self, bank, hyp, batch_size, steps, rank=0, seed=0, device='cuda', dtype=torch.bfloat16, task='det', cap=None):
+        from hd_yolo_amd import augment
+        self.k, self.patch, self.imgsz, self.cval = augment.check_hyp(hyp)
+        if getattr(bank, 'masks', None) is not None:
+            raise ValueError('DeviceTiles: mask targets are not supported')
+        self.hyp, self.bank, self.batch_size, self.steps, self.rank, self.seed, self.task = dict(hyp), bank, batch_size, steps, rank, seed, task
+        self.device, self.dtype = torch.device(device), dtype
+        if self.device.type != 'cuda':
+            raise ValueError('DeviceTiles augments on the GPU: there is no CPU path (use SyntheticTiles without one)')
+        n_cells = batch_size * self.k * self.k
+        if n_cells > augment.MAX_CELLS:
+            raise ValueError(f'DeviceTiles: batch_size * k_mosaic^2 = {n_cells} cells in a batch (at most {augment.MAX_CELLS})')
+        if bank.device != self.device:
+            bank.to(self.device)
+        self.epoch = 0
+        self.d2h_copies = 0                    # device-to-host copies this loader made (one per batch: the row counts)
+        self.cap = int(cap) if cap is not None else max(n_cells * max(bank.max_per_tile, 1), 1)
+        self.stream = torch.cuda.Stream(device=self.device)
+        nbytes = n_cells * augment.CELL_BYTES + batch_size * 8
+        B, S, dev = batch_size, self.imgsz, self.device
+        self.slots = []
+        for _ in range(2):
+            self.slots.append({
+                'host': torch.empty(nbytes, dtype=torch.uint8).pin_memory(), 'table': torch.empty(nbytes, dtype=torch.uint8, device=dev),
+                'imgs': torch.empty((B, 3, S, S), dtype=dtype, device=dev), 'boxes': torch.empty((self.cap, 4), dtype=torch.float32, device=dev),
+                'labels': torch.empty((self.cap,), dtype=torch.int64, device=dev), 'img': torch.empty((self.cap,), dtype=torch.float32, device=dev),
+                'counts': torch.empty((B + 1,), dtype=torch.int32, device=dev), 'counts_host': torch.empty((B + 1,), dtype=torch.int32).pin_memory(),
+                'event': torch.cuda.Event()})
+        self._size = torch.tensor([S, S], dtype=torch.int64)
+        self._ids = [torch.tensor([i], dtype=torch.int64) for i in range(B)]
+
+    def set_epoch(self, epoch):
+        self.epoch = epoch
+
+    def __len__(self):
+        return self.steps
+
+    def _issue(self, step, slot):
+        """draw, pack, upload and launch batch `step` into `slot` on the loader's stream"""
+        from hd_yolo_amd import augment, ops
+        rng = augment.step_rng(self.seed, self.rank, self.epoch, step)
+        pars = augment.draw_params(rng, self.hyp, self.batch_size, self.bank.n)
+        augment.cell_tables(pars, (self.bank.H, self.bank.W), out=slot['host'].numpy())
+        n_cells = self.batch_size * self.k * self.k
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))      # the consumer is done with this slot's previous batch
+        with torch.cuda.stream(self.stream):
+            slot['table'].copy_(slot['host'], non_blocking=True)
+            cells = slot['table'][:n_cells * augment.CELL_BYTES].view(n_cells, augment.CELL_BYTES)
+            crop = slot['table'][n_cells * augment.CELL_BYTES:].view(torch.int32).view(self.batch_size, 2)
+            ops.augment_tiles(self.bank.d_tiles, cells, crop, slot['imgs'], self.patch, self.k, self.cval)
+            ops.augment_boxes(self.bank.d_boxes, self.bank.d_labels, self.bank.d_offsets, len(self.bank.boxes), cells, crop, self.patch, self.k,
+                              self.imgsz, slot['boxes'], slot['labels'], slot['img'], slot['counts'][:self.batch_size],
+                              slot['counts'][self.batch_size:])
+            slot['counts_host'].copy_(slot['counts'], non_blocking=True)
+            self.d2h_copies += 1
+            slot['event'].record(self.stream)
+
+    def _hand_out(self, slot):
+        slot['event'].synchronize()
+        torch.cuda.current_stream(self.device).wait_event(slot['event'])
+        counts = slot['counts_host'].tolist()
+        if counts[-1]:
+            raise RuntimeError(f'DeviceTiles: a batch kept {sum(counts[:-1])} boxes, more than the capacity of {self.cap} rows: raise `cap`')
+        counts = counts[:-1]
+        total = sum(counts)
+        boxes, labels = slot['boxes'][:total].split(counts), slot['labels'][:total].split(counts)
+        targets = tuple({'image_id': self._ids[i], 'size': self._size,
+                         'anns': {self.task: [{'size': self._size, 'boxes': boxes[i], 'labels': labels[i]}]}} for i in range(self.batch_size))
+        return tuple(slot['imgs'].unbind(0)), targets
+
+    def __iter__(self):
+        if self.steps <= 0:
+            return
+        self._issue(0, self.slots[0])
+        for i in range(self.steps):
+            if i + 1 < self.steps:
+                self._issue(i + 1, self.slots[(i + 1) % 2])
+            yield self._hand_out(self.slots[i % 2])

@@ -790,6 +790,63 @@ def slide_tissue(slide, origins, th, tw, background=220):
     return counts
 
 
+# ------------------------------------------------------------------------------------------ training augmentation from an 8-bit tile bank
+AUG_CELL_BYTES = 864
+
+
+def _tile_bank_u8(tiles):
+    """(ptr, tile stride, row pitch (bytes), pixel_bytes, n, H, W) of a bank: a CUDA uint8 tensor (n, H, W, 3 | 4) with interleaved pixels,
+    dense rows and any row / tile stride (a crop of a larger bank is a view, not a copy)."""
+    if not isinstance(tiles, torch.Tensor) or tiles.dtype != torch.uint8:
+        raise _lib.HdyError(f'tile bank: a torch.uint8 tensor is expected, got {getattr(tiles, "dtype", type(tiles).__name__)}')
+    require_gpu(tiles)
+    if tiles.dim() != 4 or tiles.shape[3] not in (3, 4) or 0 in tiles.shape:
+        raise _lib.HdyError(f'tile bank: shape (n, H, W, 3) RGB or (n, H, W, 4) RGBA is expected, got {tuple(tiles.shape)}')
+    n, H, W, C = tiles.shape
+    pitch = int(tiles.stride(1)) if H > 1 else W * C
+    stride = int(tiles.stride(0)) if n > 1 else (H - 1) * pitch + W * C
+    if tiles.stride(3) != 1 or tiles.stride(2) != C or pitch < W * C or stride < (H - 1) * pitch + W * C:
+        raise _lib.HdyError(f'tile bank: pixels must be interleaved and rows dense, got strides {tuple(tiles.stride())}')
+    return tiles.data_ptr(), stride, pitch, C, n, H, W
+
+
+def _cell_table(cells, crop, k):
+    require_gpu(cells)
+    assert cells.dtype == torch.uint8 and cells.dim() == 2 and cells.shape[1] == AUG_CELL_BYTES and cells.is_contiguous(), \
+        f'cell table: uint8 [B * k * k][{AUG_CELL_BYTES}]'
+    assert crop.dtype == torch.int32 and crop.dim() == 2 and crop.shape[1] == 2 and crop.is_contiguous() and crop.is_cuda, 'crop: int32 [B][2]'
+    return cells.data_ptr(), cells.shape[0], crop.data_ptr(), crop.shape[0]
+
+
+def augment_tiles(tiles, cells, crop, out, patch, k, cval):
+    """The augmented batch (hdy_augment_tiles_u8): `out` (B, 3, S, S) fp32 / bf16 contiguous, from the bank `tiles`, the device cell table
+    uint8 (B * k * k, 864) and crop offsets int32 (B, 2) that hd_yolo_amd.augment.cell_tables packs.  No synchronisation."""
+    bp, stride, pitch, pb, n, H, W = _tile_bank_u8(tiles)
+    cp, n_cells, rp, B = _cell_table(cells, crop, k)
+    require_gpu(out)
+    assert out.dim() == 4 and out.shape[0] == B and out.shape[1] == 3 and out.shape[2] == out.shape[3] and out.is_contiguous(), tuple(out.shape)
+    _call('hdy_augment_tiles_u8', bp, stride, pitch, pb, n, H, W, cp, n_cells, rp, B, int(patch), int(k), int(out.shape[2]), int(cval),
+          out.data_ptr(), out.numel(), dcode(out.dtype))
+    return out
+
+
+def augment_boxes(bank_boxes, bank_labels, offsets, n_boxes, cells, crop, patch, k, img_size, out_boxes, out_labels, out_img, counts, overflow):
+    """The batch's transformed targets (hdy_augment_boxes): compact normalised xyxy rows in (image, cell, source) order into out_boxes
+    (cap, 4) / out_labels int64 (cap,) / out_img fp32 (cap,), rows per image into counts int32 (B,), overflow int32 (1,) = 1 when more than
+    cap rows were kept.  n_boxes: rows of the bank's box array that are annotations.  No synchronisation."""
+    cp, n_cells, rp, B = _cell_table(cells, crop, k)
+    cap = out_boxes.shape[0]
+    assert bank_boxes.dtype == torch.float32 and bank_boxes.is_contiguous() and bank_boxes.dim() == 2 and bank_boxes.shape[1] == 4
+    assert bank_labels.dtype == torch.int64 and bank_labels.is_contiguous() and offsets.dtype == torch.int64 and offsets.is_contiguous()
+    assert 0 <= n_boxes <= bank_boxes.shape[0] and bank_labels.shape[0] >= n_boxes
+    assert out_boxes.dtype == torch.float32 and out_boxes.is_contiguous() and tuple(out_boxes.shape) == (cap, 4)
+    assert out_labels.dtype == torch.int64 and out_labels.is_contiguous() and tuple(out_labels.shape) == (cap,)
+    assert out_img.dtype == torch.float32 and out_img.is_contiguous() and tuple(out_img.shape) == (cap,)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and overflow.dtype == torch.int32 and overflow.numel() >= 1
+    _call('hdy_augment_boxes', ptr(bank_boxes), ptr(bank_labels), ptr(offsets), offsets.shape[0] - 1, int(n_boxes), cp, n_cells, rp, B,
+          int(patch), int(k), int(img_size), ptr(out_boxes), ptr(out_labels), ptr(out_img), cap, ptr(counts), counts.numel(), ptr(overflow))
+
+
 # ------------------------------------------------------------------------------------------ detection head
 def decode_level(det, anchor_px, stride, out, row_offset, level_id):
     """det: fp32 logits viewed as (B, na, ny, nx, no) with o contiguous (any other strides)."""

@@ -345,3 +345,35 @@ def synth_dense_boxes(n, seed=0):
     c = rng.uniform(0, side, (n, 2))
     wh = rng.uniform(12, 30, (n, 2))
     return np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32), rng.uniform(0, 1, n).astype(np.float32)
+
+
+def synth_tile_bank(n, size, nc, seed=0, nmin=20, nmax=60):
+    """A seeded 8-bit tile bank (hd_yolo_amd.augment.TileBank) for the device augmentation, because no real histology tiles ship with the
+    project: `n` RGB tiles of size x size, an eosin-pink noisy background with `nmin`..`nmax` haematoxylin-blue elliptical nuclei of 14-34 px
+    per tile, one xyxy box in pixels and a label in 1..nc per nucleus."""
+    import numpy as np
+    from hd_yolo_amd.augment import TileBank
+    rng = np.random.default_rng(5000 + seed)
+    tiles = np.empty((n, size, size, 3), np.uint8)
+    boxes, labels, offsets = [], [], [0]
+    for t in range(n):
+        img = np.array([228.0, 182.0, 208.0]) + rng.normal(0, 9, (size, size, 3))
+        m = int(rng.integers(nmin, nmax + 1))
+        c = rng.uniform(0.03 * size, 0.97 * size, (m, 2))
+        wh = rng.uniform(14, 34, (m, 2))
+        lab = rng.integers(1, nc + 1, m)
+        b = np.clip(np.concatenate([c - wh / 2, c + wh / 2], 1), 0, size)
+        for (x1, y1, x2, y2), l in zip(b, lab):
+            xs, ys = np.arange(int(x1), int(np.ceil(x2))), np.arange(int(y1), int(np.ceil(y2)))
+            if not len(xs) or not len(ys):
+                continue
+            e = ((xs[None] + 0.5 - (x1 + x2) / 2) / max((x2 - x1) / 2, 1)) ** 2 + ((ys[:, None] + 0.5 - (y1 + y2) / 2) / max((y2 - y1) / 2, 1)) ** 2
+            colour = np.array([70.0 + 12 * l, 50.0 + 6 * l, 140.0 - 4 * l])
+            sel = e <= 1.0
+            patch = img[ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1]
+            patch[sel] = colour + rng.normal(0, 6, (int(sel.sum()), 3))
+        tiles[t] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+        boxes.append(b.astype(np.float32))
+        labels.append(lab.astype(np.int64))
+        offsets.append(offsets[-1] + m)
+    return TileBank(tiles, np.concatenate(boxes), np.concatenate(labels), np.asarray(offsets, np.int64))

@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 8
+#define HDY_ABI_VERSION 9
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -330,6 +330,68 @@ int hdy_slide_append(const float* boxes, const float* scores, const long long* l
                      int n_origins, int first, float* out_boxes, float* out_scores, long long* out_labels, int capacity, int* cursor, void* stream);
 int hdy_slide_tissue_u8(const unsigned char* slide, long long pitch_bytes, int pixel_bytes, int H, int W, const int* origins, int n_origins, int th,
                         int tw, int background, int* counts, int n_counts, void* stream);
+
+/* ---- training augmentation from an 8-bit tile bank (csrc/augment.hip) ---------------------------------------------------------------
+ * Replaces the training branch of the reference's loader (metayolo/datasets.py TorchDataset.__getitem__ on the keep_res <= 0 path, detection
+ * annotations without masks): per output image a k x k mosaic of cells, each cell one source tile through train_proc (random_hsv ->
+ * random_projective into a patch x patch canvas with border value cval -> random_flip: hflip, vflip, transpose), then a random img_size crop,
+ * the crop's and the final remove_invalid_objects, and target_to_tensors' normalisation.  The parameters are drawn and the matrices composed
+ * on the host in float64 (hd_yolo_amd/augment.py); the two kernels apply them.  The pixel arithmetic is this library's own (the reference
+ * calls cv2 and pins no version) and is stated here in full, so that tests/augment_ref.py reproduces both kernels bit for bit.
+ *
+ * Bank: n tiles of H x W 8-bit pixels, tile t's row y at bank + t * tile_stride_bytes + y * pitch_bytes, pixel_bytes = 3 (RGB) or 4 (RGBA,
+ * alpha ignored); a cropped view of a larger bank needs no copy.  Boxes of the bank: bank_boxes fp32 [M][4] xyxy in source pixels (16-byte
+ * aligned), bank_labels int64 [M], offsets int64 [n + 1] (tile t owns rows [offsets[t], offsets[t + 1])).
+ *
+ * Cell table: B * k * k records of HDY_AUG_CELL_BYTES, image-major, then cell row r, then cell column c.  A record is 24 little-endian words
+ *   [0] source tile (int32)   [1..9] inverse matrix Mi (canvas -> source, fp32 row-major)   [10] flags: 1 hflip, 2 vflip, 4 transpose, 8 HSV,
+ *   16 perspective divide   [11..19] forward matrix M (source -> canvas)   [20] scale   [21..23] zero
+ * followed by three 256-byte tables (hue, saturation, value).  crop: int32 [B][2] = (x, y) of the crop window in the mosaic.  Both kernels are
+ * memory-safe for any table content: a source index outside [0, n) reads as cval and owns no boxes; a crop offset outside
+ * [0, k * patch - img_size] gives an image of cval and no boxes; offsets rows that are negative, decreasing or beyond M own no boxes.
+ *
+ * hdy_augment_tiles_u8 writes out (B, 3, img_size, img_size) NCHW of dtype; out_elems must be exactly that many elements (else HDY_EINVAL);
+ * out 16-byte aligned; k <= 8; 4 <= patch <= 32768; img_size <= k * patch.  Output pixel (ox, oy) of image b:
+ *   X = ox + crop_x, Y = oy + crop_y;  c = X / patch, r = Y / patch (cell);  u = X - c patch, v = Y - r patch
+ *   transpose: swap(u, v);  vflip: v = patch - 1 - v;  hflip: u = patch - 1 - u          (the three flips undone, last one first)
+ *   sx = (Mi0 u + Mi1 v) + Mi2, sy = (Mi3 u + Mi4 v) + Mi5 in fp32, every product and sum rounded on its own (no FMA); with the perspective
+ *   flag sw = (Mi6 u + Mi7 v) + Mi8, sx = sx / sw, sy = sy / sw
+ *   qx = rint(32 sx), qy = rint(32 sy) (ties to even; 1/32 pixel, the convention of 8-bit warpAffine); |32 s| > 2^24 or NaN: the pixel is cval
+ *   x0 = qx >> 5, fx = qx & 31, y0 = qy >> 5, fy = qy & 31;  texels t00 = (x0, y0), t01 = (x0 + 1, y0), t10 = (x0, y0 + 1), t11: a position
+ *   outside the tile reads (cval, cval, cval); one inside goes through the HSV round trip when the flag is set (before interpolation)
+ *   per channel  p = (t00 (32 - fx)(32 - fy) + t01 fx (32 - fy) + t10 (32 - fx) fy + t11 fx fy + 512) >> 10
+ *   out = table[p], the correctly rounded p / 255 of hdy_slide_tiles_u8, converted to dtype.
+ * HSV round trip of a pixel (r, g, b), all integers, `/` truncating on non-negative operands:
+ *   V = max, d = V - min, S = V ? (255 d + (V >> 1)) / V : 0
+ *   H = 0 when d == 0, else off + (60 (num + d) + d) / (2 d) - 30 with (num, off) = (g - b, 0) if V == r, else (b - r, 60) if V == g, else
+ *   (r - g, 120); H += 180 when negative                                                   (H in 0 .. 179)
+ *   H' = hue[H] (minus 180 when >= 180), S' = sat[S], V' = val[V];  sec = H' / 30, f = H' - 30 sec
+ *   p = (V' (255 - S') + 127) / 255,  q = (V' (7650 - S' f) + 3825) / 7650,  t = (V' (7650 - S' (30 - f)) + 3825) / 7650
+ *   (r, g, b) = (V', t, p), (q, V', p), (p, V', t), (p, q, V'), (t, p, V'), (V', p, q) for sec = 0 .. 5.
+ * Source bytes are read as whole aligned dwords: up to 3 bytes beside a pixel (never outside its page) may be read.
+ *
+ * hdy_augment_boxes ("Targets") writes the kept boxes of the batch compactly: out_boxes fp32 [cap][4] (xyxy / img_size, 16-byte aligned),
+ * out_labels int64 [cap], out_img fp32 [cap] (image index: the form hdy_det_targets takes), counts int32 [n_counts = B] rows per image, and
+ * overflow[0] = 1 when more than cap rows were kept (else 0): the first cap rows are written, nothing beyond.  Order: image, then cell in
+ * (r, c) order, then source order.  One workgroup, prefix sums, no atomics: repeats are bit-identical.  B * k * k <= 4096; of a tile's boxes
+ * the first 65536 are read.  Per source box (x1, y1, x2, y2) of cell (r, c), fp32, every operation rounded on its own, in this order:
+ *   corners (x1, y1), (x1, y2), (x2, y2), (x2, y1):  X = (x M0 + y M1) + M2, Y = (x M3 + y M4) + M5; with the perspective flag
+ *   Wd = (x M6 + y M7) + M8, X = X / Wd, Y = Y / Wd;  X = min(max(X, 0), patch), Y alike                       (warp_coords, Mask(clip=True))
+ *   box = (min X, min Y, max X, max Y), or zeros when all four X are zero                                       (Mask.box)
+ *   w1 = x2 scale - x1 scale, h1 alike; w2, h2 of box; kept when w2 > 2, h2 > 2, (w2 h2) / (w1 h1 + 1e-16) > 0.1 and
+ *   max(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16)) < 100                                                             (box_candidates)
+ *   hflip: (|x2 - patch|, |y1|, |x1 - patch|, |y2|);  vflip: (|x1|, |y2 - patch|, |x2|, |y1 - patch|);  transpose: (y1, x1, y2, x2)
+ *   x += (c patch - crop_x), y += (r patch - crop_y)      (the integer difference is exact in fp32)             (pad_annotation, crop_annotation)
+ *   dropped unless x1 < x2 and y1 < y2 (remove_invalid_objects after the crop evaluates its filter on the UNCLIPPED box: it removes nothing)
+ *   clipped to [0, img_size]; dropped unless x1 < x2 - 10 and y1 < y2 - 10                                      (the final filter)
+ *   out = box / img_size. */
+#define HDY_AUG_CELL_BYTES 864
+int hdy_augment_tiles_u8(const unsigned char* bank, long long tile_stride_bytes, long long pitch_bytes, int pixel_bytes, int n, int H, int W,
+                         const void* cells, int n_cells, const int* crop, int B, int patch, int k, int img_size, int cval, void* out,
+                         long long out_elems, int dtype, void* stream);
+int hdy_augment_boxes(const float* bank_boxes, const long long* bank_labels, const long long* offsets, int n, int M, const void* cells, int n_cells,
+                      const int* crop, int B, int patch, int k, int img_size, float* out_boxes, long long* out_labels, float* out_img, int cap,
+                      int* counts, int n_counts, int* overflow, void* stream);
 
 /* ---- mask branch primitives ------------------------------------------------------------
  * hdy_roi_align_fwd/bwd replace torchvision.ops.roi_align as the reference calls it (metayolo/models/yolo_head.py:243 on ground

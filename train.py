@@ -43,7 +43,7 @@ from hd_yolo_amd import synth  # noqa: E402
 from hd_yolo_amd.parallel import DataParallel  # noqa: E402
 from metayolo import LOGGER  # noqa: E402
 from metayolo.common import ModelEMA, de_parallel  # noqa: E402
-from metayolo.datasets import SyntheticTiles  # noqa: E402
+from metayolo.datasets import DeviceTiles, SyntheticTiles  # noqa: E402
 from metayolo.engines.general import checkpoint_state, convert_yolo_weights, increment_path, init_seeds, intersect_dicts, one_cycle  # noqa: E402
 from metayolo.engines.torch_utils import select_device  # noqa: E402
 from metayolo.models.utils_general import check_img_size  # noqa: E402
@@ -161,7 +161,17 @@ def train(hyp, opt, device):
     mk = dict(task=task0, masks=with_masks)
     if with_masks:
         mk.update(nmin=4, nmax=24)                                     # every object carries a 28x28 mask target
-    loader = SyntheticTiles(batch_size, imgsz, nc, opt.steps_per_epoch, rank=max(RANK, 0), seed=opt.seed, device=device, **mk)
+    if opt.tile_bank:                                                  # 8-bit tiles + boxes, augmented on the device (metayolo/datasets.py DeviceTiles)
+        assert not with_masks, '--tile-bank carries detection boxes only: mask targets are not supported by the device augmentation'
+        from hd_yolo_amd.augment import TileBank
+        bank = TileBank.load(opt.tile_bank)
+        assert bank.nc <= nc, f'--tile-bank holds labels up to {bank.nc}, the model has nc={nc}'
+        aug = {k: getattr(opt, k) for k in ('degrees', 'translate', 'scale', 'shear', 'perspective', 'hsv_h', 'hsv_s', 'hsv_v', 'fliplr', 'flipud',
+                                            'transpose', 'cval')}
+        aug.update(k_mosaic=opt.k_mosaic, patch_size=opt.patch_size or imgsz, img_size=imgsz)
+        loader = DeviceTiles(bank, aug, batch_size, opt.steps_per_epoch, rank=max(RANK, 0), seed=opt.seed, device=device, task=task0)
+    else:
+        loader = SyntheticTiles(batch_size, imgsz, nc, opt.steps_per_epoch, rank=max(RANK, 0), seed=opt.seed, device=device, **mk)
     val_loader = SyntheticTiles(batch_size, imgsz, nc, opt.val_batches, rank=0, seed=opt.seed + 99, device=device, task=task0)
     nb = len(loader)
     nw = max(round(hyp['warmup_epochs'] * nb), 100)
@@ -270,6 +280,25 @@ def argument_parser():
     p.add_argument('--cos-lr', action='store_true')
     p.add_argument('--patience', type=int, default=100)
     p.add_argument('--seed', type=int, default=0)
+    # device augmentation from an 8-bit tile bank.  The keys are the reference's hyper-parameter names (metayolo/datasets.py train_proc); the
+    # reference ships no default for them (they come from its hyp yaml), so the defaults below are this project's: the YOLOv5 scratch values
+    # where one exists, a 2 x 2 mosaic of img-size cells, a mid-grey border.
+    p.add_argument('--tile-bank', default='', help='.npz tile bank (tiles uint8 (n,H,W,3), boxes float32 xyxy px, labels int64 1..nc, offsets int64 '
+                                                   '(n+1)): train on it with device-side augmentation instead of synthetic tiles')
+    p.add_argument('--k-mosaic', type=int, default=2, help='mosaic side k: every image is a random crop of k x k augmented cells')
+    p.add_argument('--patch-size', type=int, default=0, help='side of a mosaic cell in pixels (0: img-size)')
+    p.add_argument('--degrees', type=float, default=0.0)
+    p.add_argument('--translate', type=float, default=0.1)
+    p.add_argument('--scale', type=float, default=0.5)
+    p.add_argument('--shear', type=float, default=0.0)
+    p.add_argument('--perspective', type=float, default=0.0)
+    p.add_argument('--hsv-h', dest='hsv_h', type=float, default=0.015)
+    p.add_argument('--hsv-s', dest='hsv_s', type=float, default=0.7)
+    p.add_argument('--hsv-v', dest='hsv_v', type=float, default=0.4)
+    p.add_argument('--fliplr', type=float, default=0.5)
+    p.add_argument('--flipud', type=float, default=0.5)
+    p.add_argument('--transpose', type=float, default=0.5)
+    p.add_argument('--cval', type=float, default=114.0, help='border value of the projective warp, in 8-bit units')
     p.add_argument('--log-every', type=int, default=10)
     p.add_argument('--project', default=os.path.join(ROOT, 'runs', 'train'))
     p.add_argument('--name', default='exp')
