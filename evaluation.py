@@ -14,7 +14,7 @@ wrapped Model is the deployed artefact (yolo.Deploy) —, checkpoints may hold s
 hot path.  Timing brackets exactly what the reference brackets (:98-105: resize + model call), with a device
 synchronisation on both sides because HIP launches are asynchronous.
 
-    python evaluation.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--weights w.pt] [--slide 2048 [--u8] [--min-tissue 0.05]]
+    python evaluation.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--weights w.pt] [--slide 2048 [--u8] [--min-tissue 0.05] [--score]]
 """
 import argparse
 import os
@@ -247,6 +247,63 @@ def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_t
     return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres)
 
 
+SCORE_CELL_SIDES = 4.0          # score_slide: side of an ordering cell, in mean box sides (a block of 256 rows then spans a few cells)
+
+
+def _cell_order(boxes, x0, y0, cell, nx):
+    """rows in row-major order of the cells their centres fall into (ties: lower row), by one torch.sort on the device"""
+    cx = ((boxes[:, 0] + boxes[:, 2]) * 0.5 - x0).div(cell).floor().nan_to_num(0.0, 0.0, 0.0).clamp(0, nx - 1).to(torch.int64)
+    cy = ((boxes[:, 1] + boxes[:, 3]) * 0.5 - y0).div(cell).floor().nan_to_num(0.0, 0.0, 0.0).clamp(0, nx - 1).to(torch.int64)
+    return torch.sort(cy * nx + cx, stable=True)[1]
+
+
+def slide_orders(pred_boxes, true_boxes):
+    """the two permutations score_slide applies: both sets in the row-major order of the same coarse cells"""
+    both = torch.cat([pred_boxes, true_boxes])
+    finite = both[torch.isfinite(both).all(1)]
+    if not len(finite):
+        return torch.arange(len(pred_boxes), device=both.device), torch.arange(len(true_boxes), device=both.device)
+    x0, y0 = finite[:, 0].min(), finite[:, 1].min()
+    extent = torch.maximum(finite[:, 2].max() - x0, finite[:, 3].max() - y0).clamp_min(1e-6)
+    mean_side = ((finite[:, 2] - finite[:, 0]).abs().mean() + (finite[:, 3] - finite[:, 1]).abs().mean()) * 0.5
+    cell = torch.maximum(mean_side * SCORE_CELL_SIDES, extent / 4096.0)         # at most 4096 x 4096 cells
+    return _cell_order(pred_boxes, x0, y0, cell, 4096), _cell_order(true_boxes, x0, y0, cell, 4096)
+
+
+@torch.no_grad()
+def score_slide(result, truth, iouv=None, ignore=(-100, -1), info=None):
+    """Scores one task's whole-slide result ({'boxes', 'scores', 'labels'}, as inference_on_slide returns it) against the slide's annotations
+    ({'boxes', 'labels'}), all device tensors, as ONE image of 10^5-10^6 rows: the matching of APMeter without a dense IoU matrix
+    (ops.ap_match).  Both sets are put in the row-major order of coarse cells (a few box sides wide) by a device sort, so that a block of
+    predictions meets only the truth chunks around it; the original rows travel as pred_row / true_row, so ties resolve as in the given
+    order, and the results are un-permuted.  Returns APMeter.ap_per_class's stats dict plus 'match' (int32 per detection: the row of its
+    truth, or -1), 'match_iou' (fp32), 'hit' (threshold bits) and 'live', device tensors in the given order.  `info` receives chunks_visited / chunks_total / workspace_bytes."""
+    from hd_yolo_amd import ops
+    from metayolo.models.metrics import ap_curves
+    import numpy as np
+    iouv = torch.linspace(0.5, 0.95, 10) if iouv is None else iouv
+    if result['labels'].dim() != 1 or truth['labels'].dim() != 1:
+        raise ValueError('score_slide: multi-label results must be flattened first (val_nuclei.flatten_onehot_objects)')
+    pb, ps, pl = result['boxes'].detach().float().reshape(-1, 4), result['scores'].detach().float().reshape(-1), result['labels'].detach()
+    tb, tl = truth['boxes'].detach().float().reshape(-1, 4).to(pb.device), truth['labels'].detach().to(pb.device)
+    dev, n, m = pb.device, len(pb), len(tb)
+    op, ot = slide_orders(pb, tb)
+    off = lambda k: torch.tensor([0, k], dtype=torch.int32, device=dev)   # noqa: E731
+    hit, live, match, miou = ops.ap_match(pb[op], ps[op], pl[op], off(n), tb[ot], tl[ot], off(m), iouv, ignore=ignore,
+                                          pred_row=op.to(torch.int32), true_row=ot.to(torch.int32), info=info)
+    inv = torch.empty_like(op)
+    inv[op] = torch.arange(n, device=dev)
+    hit, live, match, miou = hit[inv], live[inv], match[inv], miou[inv]
+    match = torch.where(match >= 0, ot[match.clamp_min(0).to(torch.int64)].to(torch.int32), match) if m else match
+    thr = np.asarray(iouv.tolist() if hasattr(iouv, 'tolist') else list(iouv), dtype=np.float32)
+    bits, keep = hit.cpu().numpy().view(np.uint16), live.cpu().numpy().astype(bool)
+    flags = ((bits[:, None] >> np.arange(len(thr), dtype=np.uint16)[None]) & 1).astype(bool)
+    stats = ap_curves(flags[keep], ps.cpu().numpy()[keep], pl.cpu().numpy().astype(np.int64)[keep], tl.cpu().numpy().astype(np.int64), thr,
+                      [int(v) for v in (ignore or ())])
+    stats.update(match=match, match_iou=miou, hit=hit, live=live)
+    return stats
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--weights', nargs='*', default=[], help='checkpoint(s); several = Ensemble; none = synthetic weights')
@@ -259,6 +316,7 @@ def main():
     ap.add_argument('--slide', type=int, default=0, help='also run one synthetic SxS slide through inference_on_slide')
     ap.add_argument('--u8', action='store_true', help='--slide: the synthetic slide as an 8-bit (H, W, 3) tensor (from the same seed), the way a slide reader delivers it')
     ap.add_argument('--min-tissue', type=float, default=0.0, help='--slide --u8: skip tiles with less than this fraction of non-background pixels')
+    ap.add_argument('--score', action='store_true', help='--slide: also score a synthetic set of slide detections against a synthetic truth (score_slide)')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
     opt = ap.parse_args()
@@ -287,6 +345,18 @@ def main():
         out = inference_on_slide(deployed.to(device), slide, tile=opt.imgsz, batch_size=opt.batch_size, min_tissue=opt.min_tissue)
         torch.cuda.synchronize()
         print(f'slide {opt.slide}x{opt.slide}: ' + ', '.join(f'{k}: {len(v["boxes"])} detections' for k, v in out.items()) + f' in {(time.time() - t0) * 1e3:.1f} ms')
+        if opt.score:
+            # synthetic weights detect nothing meaningful, so the scored detections are synthetic too: annotations at nucleus density and
+            # detections made from them (synth.synth_slide_truth)
+            n_obj = max(1, int((opt.slide / 40.0) ** 2))
+            tb, tl, pb, ps, pl = (torch.from_numpy(a).to(device) for a in synth.synth_slide_truth(n_obj, opt.slide, opt.nc, seed=5))
+            info = {}
+            torch.cuda.synchronize()
+            t0 = time.time()
+            st = score_slide({'boxes': pb, 'scores': ps, 'labels': pl}, {'boxes': tb, 'labels': tl}, info=info)
+            torch.cuda.synchronize()
+            print(f'score: {len(ps)} detections x {len(tl)} truths, mAP@.5 {float(st["ap"][:, 0].mean()):.4f}, chunk pairs visited / total '
+                  f'{info["chunks_visited"]} / {info["chunks_total"]} ({info["chunks_visited"] / max(info["chunks_total"], 1):.4f}) in {(time.time() - t0) * 1e3:.1f} ms')
 
 
 if __name__ == '__main__':

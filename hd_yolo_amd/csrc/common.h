@@ -45,6 +45,8 @@ enum HdyOption {
     HDY_OPT_WGRAD_DEEP_KMIN,   // HDY_WGRAD_DEEP_KMIN: fewest output channels (a multiple of 64) the deep-pipelined multi-tap weight gradient takes (default 192; 256 = rounds 3-5)
     HDY_OPT_NO_CONV3X3_C128,   // HDY_NO_CONV3X3_C128: filter-resident 3x3 kernel for 128 input channels off (deep-pipelined / generic kernel instead)
     HDY_OPT_NO_F1X1_96,        // HDY_NO_F1X1_96: fused 1x1 backward instance for 96 channels off (three launches instead; A/B)
+    HDY_OPT_AP_CHUNK,          // HDY_AP_CHUNK: truths the AP match pass stages in LDS at a time (0 = default 256; 64, 128, 256): results do not depend on it
+    HDY_OPT_AP_NO_PRUNE,       // HDY_AP_NO_PRUNE: the AP match pass visits every truth chunk (A/B, tests: results do not depend on it)
     HDY_OPT_COUNT
 };
 int hdy_opt(int id);

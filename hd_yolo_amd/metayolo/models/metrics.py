@@ -1,6 +1,7 @@
 """Detection metrics for the validation entry point (reference: metayolo/models/metrics.py:19-84 ap_per_class,
-:86-110 compute_ap, :251-408 APMeter).  Host-side numpy on at most max_det rows per tile: not a kernel target
-(SURVEY.md §2 row 5g); APMeter keeps the reference's matching rules and stats dictionary (pinned by tests/golden/apmeter.npz)."""
+:86-110 compute_ap, :251-408 APMeter).  APMeter is host-side numpy and keeps the reference's matching rules and stats dictionary
+(pinned by tests/golden/apmeter.npz); DeviceAPMeter does the same matching on the device (csrc/score.hip) for batches and whole
+slides, and shares the curve arithmetic (ap_curves)."""
 import numpy as np
 import torch
 
@@ -95,6 +96,45 @@ def summarize_precision_recall(stats_list, labels_text):
     return out
 
 
+def ap_curves(hit, scores, y_pred, y_true, iouv, ignore, eps=1e-16):
+    """Precision / recall / AP curves from per-prediction hit flags: the second half of APMeter.ap_per_class, shared with DeviceAPMeter.
+    hit (n, n_iou) bool, scores / y_pred (n,) of the predictions that stay in the curves, y_true (n_true,), ignore a list of labels."""
+    order = np.argsort(-scores, kind='stable')
+    hit, scores, y_pred = hit[order], scores[order], y_pred[order]
+
+    px = np.linspace(0, 1, 1000)
+    out = {'labels': [], 'counts': [], 'px': px}
+    py, ap, p, r = [], [], [], []
+    for c, n_true in zip(*np.unique(y_true, return_counts=True)):
+        if c in ignore:
+            continue
+        out['labels'].append(c)
+        out['counts'].append(n_true)
+        sel = y_pred == c
+        if sel.sum() == 0 or n_true == 0:
+            ap.append(np.zeros(len(iouv)))
+            for curve in (r, p, py):
+                curve.append(np.zeros(len(px)))
+            continue
+        tpc, fpc = hit[sel].cumsum(0), (~hit[sel]).cumsum(0)
+        # fp32 curves, as the reference's torch arithmetic produces them: with fp64 a recall of exactly k/n can land ON a
+        # knot of compute_ap's 101-point grid where the fp32 value falls just beside it, and the AP moves in the 4th digit
+        tp32 = tpc.astype(np.float32)
+        recall, precision = tp32 / np.float32(n_true + eps), tp32 / (tpc + fpc).astype(np.float32)
+        r.append(np.interp(-px, -scores[sel], recall[:, 0], left=0))
+        p.append(np.interp(-px, -scores[sel], precision[:, 0], left=1))
+        row = np.zeros(len(iouv))
+        for j in range(len(iouv)):
+            row[j], mpre, mrec = compute_ap(recall[:, j], precision[:, j])
+            if j == 0:
+                py.append(np.interp(px, mrec, mpre))
+        ap.append(row)
+    stack = lambda rows, w: np.stack(rows) if rows else np.zeros((0, w))   # noqa: E731
+    out.update(py=stack(py, len(px)), ap=stack(ap, len(iouv)), p=stack(p, len(px)), r=stack(r, len(px)))
+    out['f1'] = 2 * out['p'] * out['r'] / (out['p'] + out['r'] + eps)
+    return out
+
+
 class APMeter:
     """Dataset-level detection AP with the reference's accumulation and matching rules (metayolo/models/metrics.py:251-375).
 
@@ -105,7 +145,9 @@ class APMeter:
     prediction is a true positive at threshold t when its pair's IoU >= t.  Predictions whose only pairs were with ignored
     truths are removed from the precision/recall curves.  Returns the reference's stats dict:
     'labels', 'counts', 'px', 'py' (n_cls, 1000), 'ap' (n_cls, n_iou), 'p', 'r', 'f1' (n_cls, 1000).
-    Host-side numpy on <= max_det rows per tile (not a kernel target)."""
+    Host-side numpy with a dense IoU matrix per image: for tiles.  DeviceAPMeter computes the same on the device.
+    Tie rule: equal scores inside one image are ranked by torch.sort, whose order among ties is unspecified; DeviceAPMeter ranks the lower
+    row first.  This is the one place the two meters may differ."""
 
     def __init__(self, labels_text={}):
         self.iouv = np.linspace(0.5, 0.95, 10)
@@ -177,37 +219,121 @@ class APMeter:
             live = np.ones(self.n_pred, dtype=bool)
             live[np.setdiff1d(m_pred[ignored], k_pred)] = False
             hit, scores, y_pred = hit[live], scores[live], y_pred[live]
-        order = np.argsort(-scores, kind='stable')
-        hit, scores, y_pred = hit[order], scores[order], y_pred[order]
+        return ap_curves(hit, scores, y_pred, y_true, iouv, ignore, eps)
 
-        px = np.linspace(0, 1, 1000)
-        out = {'labels': [], 'counts': [], 'px': px}
-        py, ap, p, r = [], [], [], []
-        for c, n_true in zip(*np.unique(y_true, return_counts=True)):
-            if c in ignore:
-                continue
-            out['labels'].append(c)
-            out['counts'].append(n_true)
-            sel = y_pred == c
-            if sel.sum() == 0 or n_true == 0:
-                ap.append(np.zeros(len(iouv)))
-                for curve in (r, p, py):
-                    curve.append(np.zeros(len(px)))
-                continue
-            tpc, fpc = hit[sel].cumsum(0), (~hit[sel]).cumsum(0)
-            # fp32 curves, as the reference's torch arithmetic produces them: with fp64 a recall of exactly k/n can land ON a
-            # knot of compute_ap's 101-point grid where the fp32 value falls just beside it, and the AP moves in the 4th digit
-            tp32 = tpc.astype(np.float32)
-            recall, precision = tp32 / np.float32(n_true + eps), tp32 / (tpc + fpc).astype(np.float32)
-            r.append(np.interp(-px, -scores[sel], recall[:, 0], left=0))
-            p.append(np.interp(-px, -scores[sel], precision[:, 0], left=1))
-            row = np.zeros(len(iouv))
-            for j in range(len(iouv)):
-                row[j], mpre, mrec = compute_ap(recall[:, j], precision[:, j])
-                if j == 0:
-                    py.append(np.interp(px, mrec, mpre))
-            ap.append(row)
-        stack = lambda rows, w: np.stack(rows) if rows else np.zeros((0, w))   # noqa: E731
-        out.update(py=stack(py, len(px)), ap=stack(ap, len(iouv)), p=stack(p, len(px)), r=stack(r, len(px)))
-        out['f1'] = 2 * out['p'] * out['r'] / (out['p'] + out['r'] + eps)
-        return out
+
+class DeviceAPMeter:
+    """APMeter with the matching on the device (ops.ap_match, csrc/score.hip): no pair list, no sort, no dense IoU matrix on the host.
+
+    add_batch(outputs, targets): `outputs` is what Model.forward delivers for one task of a batch, a list of per-image dicts
+    {'boxes', 'scores', 'labels'} of device tensors, or the compacted (boxes, scores, labels, n_keep) tuple of device_outputs=True;
+    `targets` a list of per-image dicts {'boxes', 'labels'}.  The batch is concatenated on the device, matched in one call, and its result
+    tensors stay on the device: no device-to-host read per image or per batch.  add(output, target) is a batch of one.
+    ap_per_class() copies the compact arrays (scores, labels, hit bits, live flags) to the host once and returns APMeter's stats dict through
+    the same curve arithmetic (ap_curves).  iouv (at most 16 thresholds) and ignore (at most 4 labels) are fixed at construction, because the
+    hit bits are made at add time: passing different ones to ap_per_class raises ValueError.  Multi-label (2-D) outputs are flattened by the
+    caller (val_nuclei.flatten_onehot_objects).
+    Tie rule: equal scores inside one image are ranked lower row first; APMeter ranks them by torch.sort, whose order among ties is
+    unspecified.  This is the one place the two meters may differ.  The properties list predictions per image in descending score order, as
+    APMeter's do."""
+
+    def __init__(self, labels_text={}, iouv=torch.linspace(0.5, 0.95, 10), ignore=(-100, -1)):
+        self.iouv = np.asarray(iouv.tolist() if hasattr(iouv, 'tolist') else list(iouv), dtype=np.float32)
+        self.ignore = tuple(int(v) for v in (ignore or ()))
+        if not 1 <= len(self.iouv) <= 16 or len(self.ignore) > 4:
+            raise ValueError('DeviceAPMeter: 1 to 16 IoU thresholds and at most 4 ignored labels')
+        self.labels_text = labels_text
+        self.reset()
+
+    def reset(self):
+        self._batches = []          # per batch: device tensors (scores, labels, hit, live, pred_off, true_labels, true_off)
+        self._host_cache = None
+
+    def add(self, output, target, iou_type='boxes'):
+        if iou_type == 'masks' and 'masks' in output and 'masks' in target:
+            raise NotImplementedError('mask IoU: the reference calls get_mask_ious here (metrics.py:275), a function its metrics module neither defines nor imports')
+        self.add_batch([output], [target])
+
+    def add_batch(self, outputs, targets, info=None):
+        from ... import ops
+        i32 = lambda counts, dev: torch.tensor(np.concatenate(([0], np.cumsum(counts))), dtype=torch.int32, device=dev)   # noqa: E731
+        if isinstance(outputs, tuple):
+            boxes, scores, labels, n_keep = outputs
+            dev = boxes.device
+            pred_off = torch.zeros((n_keep.numel() + 1,), dtype=torch.int32, device=dev)
+            pred_off[1:] = torch.cumsum(n_keep.to(torch.int32), 0)
+        else:
+            if not len(outputs):
+                return
+            if outputs[0]['labels'].dim() != 1:
+                raise ValueError('DeviceAPMeter: multi-label outputs must be flattened by the caller (val_nuclei.flatten_onehot_objects)')
+            dev = outputs[0]['boxes'].device
+            boxes = torch.cat([o['boxes'].detach().float().reshape(-1, 4) for o in outputs])
+            scores = torch.cat([o['scores'].detach().float().reshape(-1) for o in outputs])
+            labels = torch.cat([o['labels'].detach().reshape(-1).to(torch.int64) for o in outputs])
+            pred_off = i32([len(o['scores']) for o in outputs], dev)       # shapes are host values: an upload, no read
+        if len(targets) != pred_off.numel() - 1:
+            raise ValueError(f'DeviceAPMeter: {pred_off.numel() - 1} images of predictions, {len(targets)} of truths')
+        tboxes = torch.cat([t['boxes'].detach().float().reshape(-1, 4) for t in targets]).to(dev)
+        tlabels = torch.cat([t['labels'].detach().reshape(-1).to(torch.int64) for t in targets]).to(dev)
+        true_off = i32([len(t['labels']) for t in targets], dev)
+        hit, live, _, _ = ops.ap_match(boxes, scores, labels, pred_off, tboxes, tlabels, true_off, self.iouv, ignore=self.ignore, info=info)
+        self._batches.append((scores.detach().float().reshape(-1), labels.detach().reshape(-1).to(torch.int64), hit, live, pred_off, tlabels, true_off))
+        self._host_cache = None
+
+    def _host(self):
+        """the compact arrays on the host (one copy per array), rows outside every image's span dropped, and the image of every prediction"""
+        if self._host_cache is None:
+            z = lambda dt: np.zeros(0, dt)   # noqa: E731
+            if not self._batches:
+                self._host_cache = (z(np.float32), z(np.int64), z(np.uint16), z(bool), z(np.int64), z(np.int64))
+                return self._host_cache
+            cat = lambda k: torch.cat([b[k] for b in self._batches]).cpu().numpy()   # noqa: E731
+            scores, y_pred, hit, live, y_true = cat(0), cat(1), cat(2).view(np.uint16), cat(3).astype(bool), cat(5)
+            poffs, toffs = [b[4].cpu().numpy().astype(np.int64) for b in self._batches], [b[6].cpu().numpy().astype(np.int64) for b in self._batches]
+            keep_p, keep_t, image, base_p, base_t, n_img = [], [], [], 0, 0, 0
+            for b, po, to in zip(self._batches, poffs, toffs):
+                keep_p.append(base_p + np.arange(po[0], po[-1]))
+                keep_t.append(base_t + np.arange(to[0], to[-1]))
+                image.append(n_img + np.repeat(np.arange(len(po) - 1), np.diff(po)))
+                base_p, base_t, n_img = base_p + len(b[0]), base_t + len(b[5]), n_img + len(po) - 1
+            kp, kt = np.concatenate(keep_p), np.concatenate(keep_t)
+            self._host_cache = (scores[kp], y_pred[kp], hit[kp], live[kp], y_true[kt], np.concatenate(image))
+        return self._host_cache
+
+    def _ranked(self):
+        scores, _, _, _, _, image = self._host()
+        return np.lexsort((np.arange(len(scores)), -scores, image))      # per image, descending score, lower row first
+
+    @property
+    def n_pred(self):
+        return len(self._host()[0])
+
+    @property
+    def n_true(self):
+        return len(self._host()[4])
+
+    @property
+    def scores(self):
+        return self._host()[0][self._ranked()]
+
+    @property
+    def y_pred(self):
+        return self._host()[1][self._ranked()]
+
+    @property
+    def y_true(self):
+        return self._host()[4]
+
+    def ap_per_class(self, iouv=None, ignore=None, eps=1e-16):
+        if iouv is not None:
+            given = np.asarray(iouv.tolist() if hasattr(iouv, 'tolist') else list(iouv), dtype=np.float32)
+            if given.shape != self.iouv.shape or not np.array_equal(given, self.iouv):
+                raise ValueError('DeviceAPMeter: the IoU thresholds are fixed at construction (the hit bits are made at add time)')
+        if ignore is not None and sorted(int(v) for v in ignore) != sorted(self.ignore):
+            raise ValueError('DeviceAPMeter: the ignored labels are fixed at construction (the matching is made at add time)')
+        scores, y_pred, bits, live, y_true, _ = self._host()
+        hit = ((bits[:, None] >> np.arange(len(self.iouv), dtype=np.uint16)[None]) & 1).astype(bool)
+        if not live.all():
+            hit, scores, y_pred = hit[live], scores[live], y_pred[live]
+        return ap_curves(hit, scores, y_pred, y_true, self.iouv, list(self.ignore), eps)

@@ -986,6 +986,66 @@ def nms(boxes, scores, iou_thres, max_det=None):
     return _nms_launch(boxes, scores, iou_thres, N if max_det is None else max(1, min(int(max_det), N)))
 
 
+# ------------------------------------------------------------------------------------------ detection scoring (csrc/score.hip)
+AP_PRED_BLOCK, AP_TRUE_CHUNK = 256, 256      # HDY_AP_PRED_BLOCK / HDY_AP_TRUE_CHUNK (include/hdyolo.h): predictions per workgroup, truths per chunk
+AP_MAX_IOU, AP_MAX_IGNORE = 16, 4
+
+
+def _i32(t, name):
+    if t is None:
+        return None
+    require_gpu(t)
+    if t.dtype != torch.int32:
+        raise _lib.HdyError(f'ap_match: {name} must be int32, got {t.dtype}')
+    return t.contiguous()
+
+
+def ap_match(pred_boxes, pred_scores, pred_labels, pred_off, true_boxes, true_labels, true_off, iouv, ignore=(-100, -1), pair_iou=0.5,
+             pred_row=None, true_row=None, info=None):
+    """The matching of APMeter (metayolo/models/metrics.py) for a ragged batch, on the device (hdy_ap_match): image i owns prediction rows
+    [pred_off[i], pred_off[i + 1]) and truth rows [true_off[i], true_off[i + 1]) (int32 device tensors of B + 1 entries).  Returns device tensors
+    hit (16 bits in an int16: bit j = matched with IoU >= iouv[j]), live (uint8: 0 = touched an ignored label and unmatched), match
+    (int32 truth row or -1) and match_iou (fp32), one entry per prediction row.  Equal scores inside an image rank lower row first; pred_row /
+    true_row (int32) replace the position in both tie rules, so permuted inputs give the permuted results.  No host synchronisation; `info` (a
+    dict) receives chunks_visited / chunks_total / workspace_bytes at the price of one read."""
+    require_gpu(pred_boxes)
+    dev = pred_boxes.device
+    pb = pred_boxes.detach().float().reshape(-1, 4).contiguous()
+    ps = pred_scores.detach().float().reshape(-1).contiguous()
+    pl = pred_labels.detach().reshape(-1).to(torch.int64).contiguous()
+    tb = true_boxes.detach().float().reshape(-1, 4).contiguous()
+    tl = true_labels.detach().reshape(-1).to(torch.int64).contiguous()
+    NP, NT = pb.shape[0], tb.shape[0]
+    if not (ps.numel() == NP == pl.numel() and tl.numel() == NT):
+        raise _lib.HdyError('ap_match: boxes, scores and labels disagree in length')
+    pred_off, true_off = _i32(pred_off, 'pred_off'), _i32(true_off, 'true_off')
+    B = pred_off.numel() - 1
+    if B < 0 or true_off.numel() != B + 1:
+        raise _lib.HdyError('ap_match: pred_off and true_off must both hold B + 1 entries')
+    pred_row, true_row = _i32(pred_row, 'pred_row'), _i32(true_row, 'true_row')
+    if (pred_row is not None and pred_row.numel() != NP) or (true_row is not None and true_row.numel() != NT):
+        raise _lib.HdyError('ap_match: pred_row / true_row must have one entry per row')
+    thr = [float(v) for v in (iouv.tolist() if hasattr(iouv, 'tolist') else iouv)]
+    ign = [int(v) for v in (ignore or ())]
+    c_thr = (ctypes.c_float * max(1, len(thr)))(*thr)
+    c_ign = (ctypes.c_longlong * max(1, len(ign)))(*ign)
+    hit = torch.empty((NP,), dtype=torch.int16, device=dev)          # 16 threshold bits (torch has no unsigned 16-bit arithmetic)
+    live = torch.empty((NP,), dtype=torch.uint8, device=dev)
+    match = torch.empty((NP,), dtype=torch.int32, device=dev)
+    miou = torch.empty((NP,), dtype=torch.float32, device=dev)
+    wsb = _lib.query('hdy_ap_match_workspace_bytes', B, NP, NT)
+    if wsb == 0:
+        raise _lib.HdyError(f'ap_match: counts out of range (B={B}, predictions={NP}, truths={NT})')
+    ws = torch.empty(((wsb + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    _lib.call('hdy_ap_match', pb.data_ptr(), ps.data_ptr(), pl.data_ptr(), pred_off.data_ptr(), ptr(pred_row), NP, tb.data_ptr(), tl.data_ptr(),
+              true_off.data_ptr(), ptr(true_row), NT, B, c_thr, len(thr), float(pair_iou), c_ign, len(ign), hit.data_ptr(), live.data_ptr(),
+              match.data_ptr(), miou.data_ptr(), ws.data_ptr(), ws.numel() * 8, stream_ptr())
+    if info is not None:
+        visited, total = ws[:2].tolist()
+        info.update(chunks_visited=visited, chunks_total=total, workspace_bytes=wsb)
+    return hit, live, match, miou
+
+
 # ------------------------------------------------------------------------------------------ mask branch primitives (row f2)
 def roi_align(feat, rois, spatial_scale, P, sampling_ratio=2, aligned=False):
     """feat NHWC (B, H, W, C) (possibly a pitched view), rois (R, 5) fp32 [image, x1, y1, x2, y2] -> (R, P, P, C) NHWC."""

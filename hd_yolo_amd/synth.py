@@ -337,6 +337,36 @@ def synth_slide_boxes(n_objects, side, seed=0, moat=None):
     return boxes, scores
 
 
+def synth_slide_truth(n_objects, side, nc, seed=0):
+    """Annotations of a whole slide and detections that go with them, for scoring (evaluation.score_slide): `n_objects` truths of 12-30 px
+    spread over a side x side region with labels 1..nc, about 3 % of them carrying the ignored label -100.  Detections: 88 % of the truths are
+    detected, 15 % of those twice (jittered duplicates: 1.5 px on the centre, +-10 % on the size), 8 % of the detections carry another label,
+    and 10 % more detections hit nothing; uniform scores, shuffled rows.
+    Returns numpy (true_boxes fp32 (M, 4), true_labels int64 (M,), boxes fp32 (N, 4), scores fp32 (N,), labels int64 (N,)), N ~ 1.1 M."""
+    import numpy as np
+    rng = np.random.default_rng(9000 + seed)
+    c = rng.uniform(0, side, (n_objects, 2))
+    wh = rng.uniform(12, 30, (n_objects, 2))
+    true_boxes = np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32)
+    true_labels = rng.integers(1, nc + 1, n_objects).astype(np.int64)
+    true_labels[rng.uniform(0, 1, n_objects) < 0.03] = -100
+    rep = (rng.uniform(0, 1, n_objects) < 0.88).astype(np.int64)
+    rep += (rep > 0) & (rng.uniform(0, 1, n_objects) < 0.15)
+    n_det = int(rep.sum())
+    dc = np.repeat(c, rep, 0) + rng.normal(0, 1.5, (n_det, 2))
+    dwh = np.repeat(wh, rep, 0) * rng.uniform(0.9, 1.1, (n_det, 2))
+    labels = np.repeat(np.where(true_labels > 0, true_labels, 1), rep)
+    wrong = rng.uniform(0, 1, n_det) < 0.08
+    labels = np.where(wrong, labels % nc + 1, labels)
+    n_false = n_objects // 10
+    fc, fwh = rng.uniform(0, side, (n_false, 2)), rng.uniform(12, 30, (n_false, 2))
+    boxes = np.concatenate([np.concatenate([dc - dwh / 2, dc + dwh / 2], 1), np.concatenate([fc - fwh / 2, fc + fwh / 2], 1)]).astype(np.float32)
+    labels = np.concatenate([labels, rng.integers(1, nc + 1, n_false)]).astype(np.int64)
+    scores = rng.uniform(0, 1, len(boxes)).astype(np.float32)
+    order = rng.permutation(len(boxes))
+    return true_boxes, true_labels, boxes[order], scores[order], labels[order]
+
+
 def synth_dense_boxes(n, seed=0):
     """One dense tile's candidates as explicit boxes: `n` boxes of 12-30 px at the density of 16 384 candidates per 640 x 640 tile."""
     import numpy as np

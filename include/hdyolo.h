@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 9
+#define HDY_ABI_VERSION 10
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -392,6 +392,39 @@ int hdy_augment_tiles_u8(const unsigned char* bank, long long tile_stride_bytes,
 int hdy_augment_boxes(const float* bank_boxes, const long long* bank_labels, const long long* offsets, int n, int M, const void* cells, int n_cells,
                       const int* crop, int B, int patch, int k, int img_size, float* out_boxes, long long* out_labels, float* out_img, int cap,
                       int* counts, int n_counts, int* overflow, void* stream);
+
+/* ---- detection scoring: AP matching for ragged batches and whole slides (csrc/score.hip) --------------------------------------------
+ * Replaces the per-image work of APMeter.add and the matching half of APMeter.ap_per_class (metayolo/models/metrics.py:251-375: five
+ * device-to-host copies, a CPU sort, a dense box_iou matrix, np.nonzero, an argsort over the pairs, two np.unique passes).  B images; image i
+ * owns prediction rows [pred_off[i], pred_off[i + 1]) and truth rows [true_off[i], true_off[i + 1]) of the concatenated arrays (offsets int32
+ * [B + 1] ON THE DEVICE, so a caller needs no read to launch; they are clamped into [0, capacity] on the device: any content is memory-safe;
+ * rows outside every span are neither read nor written).  pred_boxes / true_boxes fp32 [capacity][4] xyxy, 16-byte aligned; pred_scores fp32;
+ * labels int64.  Per image:
+ *   1. IoU exactly as utils_general.box_iou on CPU fp32 (inter = max(min(x2, X2) - max(x1, X1), 0) * max(min(y2, Y2) - max(y1, Y1), 0),
+ *      iou = inter / ((a + A) - inter), every operation rounded on its own).  A pair with IoU < pair_iou, or a NaN IoU, is no pair; a pair
+ *      whose prediction or truth label is in `ignore` only marks the prediction as touched;
+ *   2. otherwise the prediction keeps the truth of highest IoU (tie: lowest truth row);
+ *   3. every truth is claimed by the prediction of highest score among those that kept it (tie: lower prediction row);
+ *   4. a prediction is matched iff it won its claim and the two labels agree: hit[p] bit j = (its IoU >= iouv[j]), match[p] = the truth's row in
+ *      the concatenated truth array, match_iou[p] = its IoU; unmatched: 0, -1, 0;
+ *   5. live[p] = 0 iff the prediction was touched and is not matched (such predictions leave the precision / recall curves), else 1.
+ * "row" in the two tie rules is the position in the concatenated arrays, or pred_row[p] / true_row[t] (int32, non-negative, distinct inside an
+ * image; may be NULL) when given: a caller may then permute its inputs without changing any result.
+ * iouv (n_iou in [1, 16] thresholds), pair_iou in (0, 1] and ignore (n_ignore in [0, 4] labels) are HOST values, read before the call returns.
+ * Truths are walked in chunks of HDY_AP_TRUE_CHUNK by workgroups of HDY_AP_PRED_BLOCK predictions; a workgroup skips every chunk whose bounding
+ * box does not overlap its own predictions' box (boxes with a non-finite coordinate are in neither box and always visited), which cannot change
+ * a result.  workspace (16-byte aligned, hdy_ap_match_workspace_bytes, 0 = counts out of range; travels with its size): after the call its
+ * first two uint64 hold the chunk pairs visited and the chunk pairs in total.  No allocation, no synchronisation, everything on `stream`; the
+ * outputs are a pure function of the inputs (no dependence on atomic arrival order, HDY_AP_CHUNK or HDY_AP_NO_PRUNE).  All argument checks are made
+ * before any launch. */
+#define HDY_AP_PRED_BLOCK 256
+#define HDY_AP_TRUE_CHUNK 256
+#define HDY_AP_MAX_ROWS (1 << 28)
+size_t hdy_ap_match_workspace_bytes(int n_img, int pred_capacity, int true_capacity);
+int hdy_ap_match(const float* pred_boxes, const float* pred_scores, const long long* pred_labels, const int* pred_off, const int* pred_row,
+                 int pred_capacity, const float* true_boxes, const long long* true_labels, const int* true_off, const int* true_row,
+                 int true_capacity, int n_img, const float* iouv, int n_iou, float pair_iou, const long long* ignore, int n_ignore,
+                 unsigned short* hit, unsigned char* live, int* match, float* match_iou, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- mask branch primitives ------------------------------------------------------------
  * hdy_roi_align_fwd/bwd replace torchvision.ops.roi_align as the reference calls it (metayolo/models/yolo_head.py:243 on ground

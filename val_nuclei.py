@@ -2,7 +2,7 @@
 """Validation entry point with the reference's `run(model, dataloader, meta_info, callbacks, ...)` surface
 (reference: val_nuclei.py:108-221), on the MI355X path: eval forward (HIP plan) -> decode + NMS kernels -> APMeter.
 
-    python val_nuclei.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4
+    python val_nuclei.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--device-metrics]
 """
 import argparse
 import os
@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 
 from metayolo import LOGGER  # noqa: E402
 from metayolo.engines.torch_utils import select_device, time_sync, to_device  # noqa: E402
-from metayolo.models.metrics import APMeter  # noqa: E402
+from metayolo.models.metrics import APMeter, DeviceAPMeter  # noqa: E402
 
 
 class _NoCallbacks:
@@ -59,14 +59,42 @@ def summarize_stats(ap_meter, task_id, **kwargs):
     return {'mp': mp, 'mr': mr, 'f1': mf1, 'map50': map50, 'map': map_, 'fitness': map50 * 0.1 + map_ * 0.9}
 
 
+def _pixel_boxes(boxes, counts, w, h):
+    """run()'s per-image rule `max(boxes) <= 1.0: normalised training boxes -> pixels` for a whole batch of truths (boxes concatenated,
+    `counts` rows per image) as one segmented reduction on the device, no read: every image's boxes times (w, h, w, h) or times 1."""
+    dev = boxes.device
+    image = torch.repeat_interleave(torch.arange(len(counts), device=dev), torch.tensor(counts, device=dev), output_size=int(sum(counts)))
+    top = torch.full((len(counts),), float('-inf'), dtype=boxes.dtype, device=dev)
+    top = top.scatter_reduce(0, image, boxes.reshape(len(boxes), -1).max(1).values, 'amax')
+    scale = torch.where((top <= 1.0)[image, None], boxes.new_tensor([w, h, w, h]), boxes.new_ones(4))
+    return boxes * scale
+
+
+def _add_batch_on_device(meter, outputs, targets, task_id, w, h):
+    """one batch of one single-label task into a DeviceAPMeter: no device-to-host read"""
+    outs = [output[task_id] for output in outputs]
+    tgts = [target['anns'][task_id][0] for target in targets]
+    counts = [len(t['labels']) for t in tgts]
+    if sum(counts):
+        boxes = _pixel_boxes(torch.cat([t['boxes'].reshape(-1, 4) for t in tgts]), counts, w, h).split(counts)
+    else:
+        boxes = [t['boxes'] for t in tgts]
+    meter.add_batch(outs, [{'boxes': b, 'labels': t['labels']} for b, t in zip(boxes, tgts)])
+
+
 @torch.no_grad()
 def run(model, dataloader, meta_info=None, callbacks=None, batch_size=32, half=True, verbose=False, save_txt=False,
-        save_dir='', plots=False, epoch=0):
+        save_dir='', plots=False, epoch=0, device_metrics=False):
+    """device_metrics=True: the tasks whose header is single-label are scored by DeviceAPMeter (the matching on the device, one call per
+    batch, no device-to-host read in the loop); the others, and everything by default, by the host APMeter.  Return values and the log
+    table are the same in both modes."""
     callbacks = callbacks or _NoCallbacks()
     device = next(model.parameters()).device
     model.half() if half else model.float()
     model.eval()
-    meters = {task_id: APMeter((meta_info or {}).get(task_id, {}).get('labels_text', {})) for task_id in model.headers}
+    names = lambda task_id: (meta_info or {}).get(task_id, {}).get('labels_text', {})   # noqa: E731
+    on_device = {task_id: bool(device_metrics) and not getattr(h, 'multi_label', False) for task_id, h in model.headers.items()}
+    meters = {task_id: (DeviceAPMeter if on_device[task_id] else APMeter)(names(task_id)) for task_id in model.headers}
     callbacks.run('on_val_start')
     dt, n_image = [0.0, 0.0, 0.0], 0
     for batch_i, (imgs, targets) in enumerate(dataloader):
@@ -79,9 +107,14 @@ def run(model, dataloader, meta_info=None, callbacks=None, batch_size=32, half=T
         _, outputs = model(imgs, compute_masks=False)
         t3 = time_sync()
         dt[1] += t3 - t2
+        for task_id in model.headers:
+            if on_device[task_id]:
+                _add_batch_on_device(meters[task_id], outputs, targets, task_id, imgs.shape[-1], imgs.shape[-2])
         for output, target in zip(outputs, targets):
             n_image += 1
             for task_id in model.headers:
+                if on_device[task_id]:
+                    continue
                 o, t = output[task_id], dict(target['anns'][task_id][0])
                 h, w = imgs.shape[-2:]
                 if t['boxes'].numel() and float(t['boxes'].max()) <= 1.0:      # normalised training boxes -> pixels
@@ -110,6 +143,7 @@ def main():
     ap.add_argument('--weights', default='')
     ap.add_argument('--device', default='')
     ap.add_argument('--no-half', action='store_true')
+    ap.add_argument('--device-metrics', action='store_true', help='score single-label tasks on the device (DeviceAPMeter) instead of the host APMeter')
     opt = ap.parse_args()
     from hd_yolo_amd import synth
     from metayolo.datasets import SyntheticTiles
@@ -125,7 +159,7 @@ def main():
         model.load_state_dict(synth.synth_state_dict(synth.shapes_of(model), seed=0), strict=False)
     model = model.to(device)
     loader = SyntheticTiles(opt.batch_size, opt.imgsz, opt.nc, opt.batches, seed=12345)
-    fitness, stats, speeds = run(model, loader, half=not opt.no_half)
+    fitness, stats, speeds = run(model, loader, half=not opt.no_half, device_metrics=opt.device_metrics)
     print(f'fitness {fitness:.4f}; ms/img pre {speeds[0]:.3f} infer+nms {speeds[1]:.3f} metrics {speeds[2]:.3f}')
 
 
