@@ -12,6 +12,10 @@ NHWC buffers; forward and backward are replays of two launch lists.  What the tr
                 is one streaming pass; in eval mode BN is folded into the conv epilogue (scale/shift/SiLU/residual).
   * backward    reverse replay: [BN+SiLU backward -> dy] -> wgrad -> dgrad, gradients of multiply-consumed tensors are
                 accumulated in the dgrad epilogue (no add kernels); the Bottleneck shortcut aliases gradient storage.
+                _mark_needs_grad says which tensors get a gradient, then one emitter per unit kind (_bwd_det / _bwd_up /
+                _bwd_pool / _bwd_conv) appends to a _BackwardList (records, fork tokens, dy ring slots, who wrote a gradient
+                last, which record writes which parameter's).  A ConvUnit's BatchNorm backward is (consumer, statistics
+                mode) = _bn_bwd_mode(u): one _bn_bwd_<mode> emitter each; the consumer picks the gradient launches.
   * gradients   all parameter gradients live in one flat fp32 buffer (views per parameter) so data-parallel
                 all-reduce is a few large RCCL calls (hd_yolo_amd/parallel.py).
 
@@ -100,6 +104,74 @@ class UpUnit:
         self.x, self.out = x, out
 
 
+class _BackwardList:
+    """The backward launch list while Plan._compile_backward builds it: the records, the side stream weight gradients fork to, and what the
+    units of the reversed walk have to know of each other."""
+
+    def __init__(self, plan, side):
+        self.plan, self.side = plan, side       # side: ops.SideStream, or None = everything on the main stream
+        self.recs, self.nfork = [], 0
+        self.nslot, self.slot_user = 0, {}      # dy ring: slots handed out so far; slot -> token of the fork that read it last
+        # Producer-side statistics: `last[id(v)]` = the launch record that wrote the LAST contribution of v's gradient (kind, index into
+        # recs when it is a launch which can serve statistics, channel offset of v inside that launch's output, slab count); remake[index]
+        # rebuilds that record with statistics requests, pending[index] are the requests made of it so far.
+        self.last, self.pending, self.remake = {}, {}, {}
+        self.grad_log = []                      # (parameter, position of the record that writes its gradient)
+
+    def add(self, rec):
+        self.recs.append(rec)
+
+    def grad(self, p):
+        """p's view of the flat gradient buffer, for the record appended NEXT (its position is what the bucket marks go by)"""
+        self.grad_log.append((p, len(self.recs)))
+        return self.plan._grad_views(p)
+
+    def wgrad(self, make, pixels=None, reads_slot=None):
+        """A weight-gradient launch, make(workspace): forked to the side stream, or inline on the main stream when there is none or the
+        layer has fewer than FORK_MIN_PIXELS output pixels — then on a workspace of its own beside the side stream's split slabs."""
+        if SKIP_WGRAD:              # timing experiment only (gradients wrong): what the step costs without the weight-gradient stream
+            return
+        if self.side is None:
+            self.recs.append(make(self.plan.wg_ws))
+        elif pixels is not None and pixels < FORK_MIN_PIXELS:
+            self.recs.append(make(self.plan.wg_ws_main))
+        else:
+            self.recs.append(('@fork', self.side, [make(self.plan.wg_ws)], self.nfork))
+            if reads_slot is not None:
+                self.slot_user[reads_slot] = self.nfork
+            self.nfork += 1
+
+    def next_slot(self):
+        """the dy ring slot of the next unit; the weight gradient that last read it must be done"""
+        slot = self.nslot % len(self.plan.dy_ring)
+        self.nslot += 1
+        if slot in self.slot_user:
+            self.recs.append(('@join', self.side, self.slot_user.pop(slot)))
+        return slot
+
+    def note_grad(self, xv, kind, make=None, slabs=0):
+        """the record appended last wrote (so far) the last contribution to xv's gradient; make(requests) rebuilds it serving statistics"""
+        idx = None if make is None else len(self.recs) - 1
+        for pv, off in ([(xv, 0)] if xv.parts is None else xv.parts):
+            self.last[id(pv)] = (kind, idx, off, slabs)
+        if idx is not None:
+            self.remake[idx] = make
+
+    def add_producer(self, xv, kind, make, slabs):
+        self.recs.append(make(None))
+        self.note_grad(xv, kind, make, slabs)
+
+    def producers(self, outs):
+        """`last` of every value of `outs` when each can still serve that value's statistics (a launch takes two requests), else None"""
+        prod = [self.last.get(id(o)) for o in outs]
+        kinds = ('dgrad', 'fused') if PRODUCER_STATS == '1' else ('fused',)
+        ok = all(q is not None and q[0] in kinds and q[3] > 0 and o.gfinal is None and o.c % 8 == 0 and q[2] % 8 == 0 and
+                 len(self.pending.get(q[1], [])) < 2 for q, o in zip(prod, outs))
+        if ok and len(outs) == 2 and prod[0][1] == prod[1][1]:
+            ok = len(self.pending.get(prod[0][1], [])) == 0
+        return prod if ok else None
+
+
 def act_code(act):
     if isinstance(act, nn.SiLU):
         return ops.ACT_SILU
@@ -138,7 +210,6 @@ class Plan:
         # gradients are written into the flat store by the outside backward, or zeroed when it did not run)
         self.tap_keys, self.tap_params = list(taps), list(tap_params)
         self.tap_grads_ready = False
-        self._grad_log = None
         self.bucket_hook = None         # engine: called as hook(a, b, side_stream) when gradient elements [a, b) of the flat buffer are final
         self._order = 0
         self._trace(backbone, neck, head)
@@ -339,10 +410,7 @@ class Plan:
                 o = u.outs[0]
                 M = o.n * o.h * o.w
                 kind = ops.PACK_STEM if u.stem else ops.PACK_FWD
-                if self.training or len(u.mods) > 1:
-                    u.wp = ops.pack_alloc(u.K, u.C, u.k, u.k, u.s, u.p, kind, dt, self.device)
-                else:
-                    u.wp = ops.pack_alloc(u.K, u.C, u.k, u.k, u.s, u.p, kind, dt, self.device)
+                u.wp = ops.pack_alloc(u.K, u.C, u.k, u.k, u.s, u.p, kind, dt, self.device)
                 u.scale, u.shift = self._new(u.K, dtype=f32), self._new(u.K, dtype=f32)
                 if self.training:
                     if not u.has_bn:
@@ -362,8 +430,6 @@ class Plan:
                     max_bnws = max(max_bnws, ops.bn_bwd_ws_floats(M, u.K))
                     if self._fusable_1x1(u):
                         max_f1 = max(max_f1, ops.fused_1x1_ws_bytes(M, u.C, u.K))
-                        wgb = ops.fused_1x1_ws_bytes(M, u.C, u.K)
-                    # batched split reductions: the slabs of a unit stay untouched until its bucket's one reduction launch has read them
                     if not u.stem:
                         u.wpd = ops.pack_alloc(u.K, u.C, u.k, u.k, u.s, u.p, ops.PACK_DGRAD, dt, self.device)
             elif isinstance(u, DetUnit):
@@ -395,13 +461,12 @@ class Plan:
         # BN-backward output of the layer in flight; a small ring, so that the weight-gradient kernels of the previous layers
         # (side stream) may still be reading theirs while the main stream moves on
         self.dy_ring = [self._new(max_dy) for _ in range(DY_RING if SIDE_WGRAD else 1)]
-        self.dy = self.dy_ring[0]
         self.wg_ws = self._new(max_wg // 4 + 16, dtype=f32)
         self.wg_ws_main = self._new(max_wg // 4 + 16, dtype=f32) if (FORK_MIN_PIXELS > 0 and SIDE_WGRAD) else self.wg_ws
-        self.bn_c12 = self._new(2, kmax if False else max(u.K for u in self.units if isinstance(u, ConvUnit)), dtype=f32)     # c1 / c2 of the unit in flight
+        kmax = max(u.K for u in self.units if isinstance(u, ConvUnit))
+        self.bn_c12 = self._new(2, kmax, dtype=f32)     # c1 / c2 of the unit in flight
         self.f1_ws = self._new(max_f1 // 4 + 16, dtype=f32)      # weight-gradient slabs of the fused 1x1 backward (main stream: not shared with wg_ws)
         self.bn_ws = self._new(max_bnws, dtype=f32)
-        kmax = max(u.K for u in self.units if isinstance(u, ConvUnit))
         self.fin_ws = self._new(32 * 2 * kmax, dtype=torch.float64)
         self.sync_sums = self._new(2 * kmax + 1, dtype=torch.float64) if self.sync else None
         # gradient storage mirrors activation storage
@@ -430,9 +495,6 @@ class Plan:
         return m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var
 
     def _grad_views(self, p):
-        # compiling the backward list: remember which launch record produces this parameter's gradient (the one appended next)
-        if self._grad_log is not None:
-            self._grad_log.append((p, self._grad_pos()))
         return self.grad_store.view_of(p)
 
     # ------------------------------------------------------------------ forward
@@ -634,256 +696,233 @@ class Plan:
         group = None if self.sync is True else self.sync
         return ('@call', lambda buf=buf, group=group: dist.all_reduce(buf, group=group))
 
-    def _compile_backward(self):
-        recs = []
-        self._grad_log = []
-        self._grad_pos = lambda: len(recs)
-        for v in self.vals:
-            v.ginit = False
-        # Weight gradients are consumed only by the optimizer: with SIDE_WGRAD they run on a second stream beside the
-        # dgrad / BN-backward chain (which is what the next layer waits for), filling the CUs that the many small launches
-        # of the 20x20 and 40x40 layers leave idle.
-        side = ops.SideStream(self.device) if SIDE_WGRAD else None
-        nfork = [0]
-
-        def wgrad(rec, reads_dy_slot=None, pixels=None):
-            if SKIP_WGRAD:          # timing experiment only (gradients wrong): what the step costs without the weight-gradient stream
-                return
-            if callable(rec):       # rec(workspace): an inline launch must not share the side stream's split-slab workspace
-                inline = side is None or (pixels is not None and pixels < FORK_MIN_PIXELS)
-                rec = rec(self.wg_ws_main if (inline and side is not None) else self.wg_ws)
-                if inline:
-                    recs.append(rec)
-                    return
-            if side is None:
-                recs.append(rec)
-                return
-            recs.append(('@fork', side, [rec], nfork[0]))
-            if reads_dy_slot is not None:
-                slot_user[reads_dy_slot] = nfork[0]
-            nfork[0] += 1
-
-        slot_user = {}
-        nconv = 0
-        # Producer-side statistics: `last[id(v)]` = the launch record that wrote the LAST contribution of v's gradient, when that is a
-        # data-gradient launch which can serve statistics (index into recs, channel offset of v inside the producer's output, how to
-        # rebuild the record with requests, slab count).  A unit whose outputs all have such a producer skips its reduce pass: the
-        # producers' epilogues leave (SUM du, SUM du*xhat) slabs and a finalize launch turns them into dgamma / dbeta / c1 / c2.
-        last, pending, remake = {}, {}, {}
-
-        def note_grad(xv, kind, idx=None, make=None, slabs=0):
-            for pv, off in ([(xv, 0)] if xv.parts is None else xv.parts):
-                last[id(pv)] = (kind, idx, off, slabs)
-            if idx is not None:
-                remake[idx] = make
-
-        # Model.freeze: a tensor needs a gradient only if something trainable lies upstream of it; units without trainable
-        # parameters below frozen inputs are skipped altogether, frozen filters skip their weight gradient
+    def _mark_needs_grad(self):
+        """Model.freeze: a tensor needs a gradient only if something trainable lies upstream of it.  Sets `needs_grad` of every unit output
+        and of every concat a unit reads; the backward walk reads that and nothing else: units without trainable parameters below frozen
+        inputs are skipped altogether, frozen filters skip their weight gradient."""
         def trainable(u):
-            if isinstance(u, DetUnit):
-                return u.conv.weight.requires_grad or u.conv.bias.requires_grad
             ps = [m.conv.weight for m in u.mods]
             if u.has_bn and not u.frozen:
                 ps += [q for m in u.mods for q in (m.bn.weight, m.bn.bias)]
             return any(q.requires_grad for q in ps)
 
-        if self.input is not None:
-            self.input.needs_grad = False
-        for v in self.ext.values():
+        def up(v):                                   # needs_grad of a (possibly concatenated) input value; None: the stem's image, no shortcut
+            if v is not None and v.parts is not None:
+                v.needs_grad = any(pv.needs_grad for pv, _ in v.parts)
+            return v is not None and v.needs_grad
+
+        for v in list(self.ext.values()) + ([self.input] if self.input is not None else []):
             v.needs_grad = False
         for k in self.tap_keys:
             v = self.outs[k]
             if v.cat is not None or v.parts is not None or v.galias is not None:
                 raise _lib.HdyError(f'layer {k} cannot be tapped: its gradient storage is shared (concat member / shortcut)')
-            v.ginit = True                  # holds the outside consumer's gradient when the list starts: everything else accumulates
-
-        def up(v):                                   # needs_grad of a (possibly concatenated) input value
-            if v is None:
-                return False
-            if v.parts is not None:
-                v.needs_grad = any(pv.needs_grad for pv, _ in v.parts)
-            return v.needs_grad
-
         for u in self.units:
+            below = up(u.x)
             if isinstance(u, ConvUnit):
-                ng = trainable(u) or up(u.x) or up(u.res)
-                for o in u.outs:
-                    o.needs_grad = ng
-            elif isinstance(u, PoolUnit):
-                for o in u.outs:
-                    o.needs_grad = up(u.x)
-            elif isinstance(u, UpUnit):
-                u.out.needs_grad = up(u.x)
-        first_conv = next((q for q in self.units if isinstance(q, ConvUnit)), None)      # = the last unit the reversed walk reaches
+                below = up(u.res) or below or trainable(u)
+            for o in ([] if isinstance(u, DetUnit) else [u.out] if isinstance(u, UpUnit) else u.outs):
+                o.needs_grad = below
+
+    def _compile_backward(self):
+        self._mark_needs_grad()
+        for v in self.vals:
+            v.ginit = False
+        for k in self.tap_keys:
+            self.outs[k].ginit = True       # holds the outside consumer's gradient when the list starts: everything else accumulates
+        # Weight gradients are consumed only by the optimizer: with SIDE_WGRAD they run on a second stream beside the
+        # dgrad / BN-backward chain (which is what the next layer waits for), filling the CUs that the many small launches
+        # of the 20x20 and 40x40 layers leave idle.
+        b = _BackwardList(self, ops.SideStream(self.device) if SIDE_WGRAD else None)
+        emit = {DetUnit: self._bwd_det, UpUnit: self._bwd_up, PoolUnit: self._bwd_pool, ConvUnit: self._bwd_conv}
         for u in reversed(self.units):
-            if isinstance(u, DetUnit):
-                x = u.x
-                tmp = self._det_bias_tmp(u)
-                recs.append(ops.rec_colsum(u.gdet, tmp, self.bn_ws))
-                gb = self._grad_views(u.conv.bias)
-                recs.append(ops.rec_copy_f32(tmp[:u.K], gb))                                    # Kp-padded column sums -> the bias gradient
-                gw = self._grad_views(u.conv.weight)
-                wgrad(lambda ws, x=x, u=u, gw=gw: ops.rec_conv_wgrad(x.t(), u.gdet, gw, None, 1, 1, 1, 0, ws), pixels=x.n * x.h * x.w)
-                if not up(x):
-                    continue
-                self.packs.add(u.conv.weight, None, 1, 0, ops.PACK_DGRAD, u.wpd, K=u.Kp)
-                acc_x = self._contrib(x)
-                mk = (lambda st, u=u, x=x, acc_x=acc_x: ops.rec_conv_dgrad(u.gdet, u.wpd, x.g(), 1, 1, 1, 0, accumulate=acc_x, stats=st))
-                recs.append(mk(None))
-                note_grad(x, 'dgrad', len(recs) - 1, mk, ops.conv_dgrad_stat_slabs(x.n, x.h, x.w, x.c, u.Kp, 1, 1, 1, 0, self.dtype) if self.dtype == torch.bfloat16 else 0)
-            elif isinstance(u, UpUnit):
-                if up(u.x):
-                    recs.append(ops.rec_upsample_bwd(u.out.gread(), u.x.g(), accumulate=self._contrib(u.x)))
-                    note_grad(u.x, 'other')
-            elif isinstance(u, PoolUnit):
-                a = u.x
-                if not up(a):
-                    continue
-                gs = [a.g()] + [o.g() for o in u.outs]
-                recs.append(ops.rec_sppf_pool_bwd(gs[0], gs[1], gs[2], gs[3], u.idx, a.gfinal))
-                note_grad(a, 'other')
-            elif isinstance(u, ConvUnit):
-                if not u.outs[0].needs_grad:
-                    continue
-                o0 = u.outs[0]
-                sync = bool(self.sync) and u.has_bn and not u.frozen
-                fused = self._fusable_1x1(u) and not sync
-                pair = len(u.mods) == 2 and not u.frozen
-                # the stem has no data gradient: its dy has one reader, the weight-gradient kernel, which can apply the BatchNorm / SiLU backward
-                # itself while it stages the tile (no apply pass, no dy tensor).  It is the last unit of the backward list, so the c1 / c2 it
-                # reads from the statistics workspace on the side stream are not overwritten before the list's final join.
-                stem_fused = (STEM_FUSED and u.stem and not sync and not u.frozen and u.has_bn and len(u.mods) == 1 and u is first_conv and
-                              u.mods[0].conv.weight.requires_grad and ops.wgrad_stem_fused_ok(self.B, self.H, self.W, u.K, self.dtype))
-                dy = None
-                if not fused and not stem_fused:
-                    slot = nconv % len(self.dy_ring)
-                    nconv += 1
-                    if slot in slot_user:              # the weight gradient that last read this ring slot must be done
-                        recs.append(('@join', side, slot_user.pop(slot)))
-                    dy = self.dy_ring[slot][:o0.n * o0.h * o0.w * u.K].view(o0.n, o0.h, o0.w, u.K)
-                # BatchNorm / SiLU backward: statistics (reduce + finalize) and, unless the fused kernel applies them, dy.
-                M = o0.n * o0.h * o0.w
-                c1, c2 = self.bn_c12[0, :u.K], self.bn_c12[1, :u.K]
-                prod = None
-                if sync:
-                    # SyncBatchNorm: local statistics pass (local dgamma / dbeta: the gradient all-reduce sums them), its partial slabs -> fp64 sums
-                    # -> all-reduce -> c1 / c2 of the GLOBAL batch -> one apply pass
-                    nb = ops.bn_bwd_blocks(M)
-                    k0 = 0
-                    for m, o in zip(u.mods, u.outs):
-                        K = m.conv.out_channels
-                        buf = self.sync_sums[:2 * K + 1]
-                        recs.append(ops.rec_bn_act_bwd(o.gread(), u.yraw[..., k0:k0 + K], u.scale[k0:k0 + K], u.shift[k0:k0 + K], u.mean[k0:k0 + K],
-                                                       u.invstd[k0:k0 + K], None, self._grad_views(m.bn.weight), self._grad_views(m.bn.bias), self.bn_ws, act=u.act))
-                        recs.append(ops.rec_bn_slab_sums(self.bn_ws[:nb * 2 * K].view(nb, 2, K), nb, K, M, buf))
-                        recs.append(self._sync_call(buf))
-                        recs.append(ops.rec_bn_bwd_coeffs_sums(buf, K, c1[k0:k0 + K], c2[k0:k0 + K]))
-                        k0 += K
-                    recs.append(ops.rec_bn_act_bwd_apply(u.outs[0].gread(), u.outs[1].gread() if len(u.outs) > 1 else None, u.yraw, u.scale, u.shift, u.mean,
-                                                         u.invstd, c1, c2, dy, act=u.act))
-                if not sync and not stem_fused and PRODUCER_STATS != '0' and self.dtype == torch.bfloat16 and u.has_bn and not u.frozen and not USE_GRAPHS:
-                    prod = [last.get(id(o)) for o in u.outs]
-                    kinds = ('dgrad', 'fused') if PRODUCER_STATS == '1' else ('fused',)
-                    ok = all(q is not None and q[0] in kinds and q[3] > 0 and o.gfinal is None and o.c % 8 == 0 and q[2] % 8 == 0 and
-                             len(pending.get(q[1], [])) < 2 for q, o in zip(prod, u.outs))
-                    if ok and len(u.outs) == 2 and prod[0][1] == prod[1][1]:
-                        ok = len(pending.get(prod[0][1], [])) == 0
-                    if not ok:
-                        prod = None
-                if prod is not None:
-                    k0 = 0
-                    for m, o, (kind, idx, off, nslabs) in zip(u.mods, u.outs, prod):
-                        K = o.c
-                        slabs = self._new(nslabs, 2, K, dtype=torch.float32, zero=True)     # workgroups without tiles never write theirs
-                        pending.setdefault(idx, []).append(ops.StatRequest(u.yraw[..., k0:k0 + K], u.scale[k0:k0 + K], u.shift[k0:k0 + K], slabs, off, u.act))
-                        recs.append(ops.rec_bn_bwd_finalize_slabs(slabs, M, u.mean[k0:k0 + K], u.invstd[k0:k0 + K], self._grad_views(m.bn.weight),
-                                                                  self._grad_views(m.bn.bias), c1[k0:k0 + K], c2[k0:k0 + K]))
-                        k0 += K
-                    if not fused:
-                        recs.append(ops.rec_bn_act_bwd_apply(u.outs[0].gread(), u.outs[1].gread() if len(u.outs) > 1 else None, u.yraw, u.scale, u.shift, u.mean,
-                                                             u.invstd, c1, c2, dy, act=u.act))
-                elif sync:
-                    pass
-                elif pair:
-                    ma, mb = u.mods
-                    recs.append(ops.rec_bn_act_bwd_pair(u.outs[0].gread(), u.outs[1].gread(), u.yraw, u.scale, u.shift, u.mean, u.invstd, dy,
-                                                        self._grad_views(ma.bn.weight), self._grad_views(ma.bn.bias),
-                                                        self._grad_views(mb.bn.weight), self._grad_views(mb.bn.bias), self.bn_ws, act=u.act))
-                    if fused:
-                        c1, c2 = ops.bn_bwd_coeffs(self.bn_ws, M, u.K)
-                k0 = 0
-                for m, o in zip(u.mods, u.outs):
-                    if pair or prod is not None or sync:
-                        break
-                    K = m.conv.out_channels
-                    dyk = None if dy is None else dy[..., k0:k0 + K]
-                    if u.frozen:
-                        recs.append(ops.rec_bn_act_bwd(o.gread(), u.yraw[..., k0:k0 + K], u.scale[k0:k0 + K], u.shift[k0:k0 + K], None, None,
-                                                       dyk, None, None, self.bn_ws, act=u.act))
-                    else:
-                        recs.append(ops.rec_bn_act_bwd(o.gread(), u.yraw[..., k0:k0 + K], u.scale[k0:k0 + K], u.shift[k0:k0 + K],
-                                                       u.mean[k0:k0 + K], u.invstd[k0:k0 + K], dyk,
-                                                       self._grad_views(m.bn.weight), self._grad_views(m.bn.bias), self.bn_ws, act=u.act))
-                        if fused or stem_fused:
-                            c1, c2 = ops.bn_bwd_coeffs(self.bn_ws, M, u.K)
-                    k0 += K
-                x = self.prep if u.stem else u.x.t()
-                stem_hw = (self.H, self.W) if u.stem else None
-                want_w = any(m.conv.weight.requires_grad for m in u.mods)
-                want_x = not u.stem and u.x is not self.input and up(u.x)
-                acc, xv = False, u.x
-                if want_x:
-                    wb = u.mods[1].conv.weight if len(u.mods) > 1 else None
-                    self.packs.add(u.mods[0].conv.weight, wb, u.s, u.p, ops.PACK_DGRAD, u.wpd)
-                    if xv.parts is not None:
-                        # writing the whole concat gradient: no part may already hold a partial contribution
-                        if any(pv.ginit for pv, _ in xv.parts) and not xv.ginit:
-                            raise _lib.HdyError('gradient ordering not plannable: a concat input receives gradient before the concat')
-                        acc = xv.ginit
-                        xv.ginit = True
-                    else:
-                        acc = self._contrib(xv)
-                if fused:
-                    if want_w or want_x:
-                        ga = self._grad_views(u.mods[0].conv.weight) if want_w else None
-                        gb = self._grad_views(u.mods[1].conv.weight) if want_w and len(u.mods) > 1 else None
-                        mk = (lambda st, u=u, x=x, xv=xv, c1=c1, c2=c2, ga=ga, gb=gb, acc=acc, want_x=want_x: ops.rec_conv1x1_bwd_fused(
-                            u.outs[0].gread(), u.outs[1].gread() if len(u.mods) > 1 else None, u.yraw, u.scale, u.shift, u.mean, u.invstd, c1, c2, x,
-                            u.wpd if want_x else None, xv.g() if want_x else None, ga, gb, self.f1_ws, accumulate_dx=acc, stats=st))
-                        recs.append(mk(None))
-                        if want_x:
-                            note_grad(xv, 'fused', len(recs) - 1, mk, ops.fused_1x1_stat_slabs(M, u.C, u.K, self.dtype))
-                    continue
-                ga = self._grad_views(u.mods[0].conv.weight)
-                gb = self._grad_views(u.mods[1].conv.weight) if len(u.mods) > 1 else None
-                if stem_fused:
-                    wgrad(ops.rec_conv_wgrad_stem_fused(x, u.outs[0].gread(), u.yraw, u.scale, u.shift, u.mean, u.invstd, c1, c2, stem_hw, ga, None,
-                                                        self.wg_ws))
-                    continue
-                if want_w:
-                    wgrad(lambda ws, x=x, dy=dy, ga=ga, gb=gb, u=u, stem_hw=stem_hw: ops.rec_conv_wgrad(x, dy, ga, gb, u.k, u.k, u.s, u.p, ws, stem_hw=stem_hw),
-                          reads_dy_slot=slot, pixels=M)
-                if want_x:
-                    mk = (lambda st, u=u, dy=dy, xv=xv, acc=acc: ops.rec_conv_dgrad(dy, u.wpd, xv.g(), u.k, u.k, u.s, u.p, accumulate=acc, stats=st))
-                    recs.append(mk(None))
-                    note_grad(xv, 'dgrad', len(recs) - 1, mk,
-                              ops.conv_dgrad_stat_slabs(xv.n, xv.h, xv.w, xv.c, u.K, u.k, u.k, u.s, u.p, self.dtype) if self.dtype == torch.bfloat16 else 0)
-        for idx, reqs in pending.items():                   # rebuild the producers with the statistics requests they serve
-            recs[idx] = remake[idx](reqs)
-        self.producer_stat_units = sum(len(v) for v in pending.values())
-        self._mark_buckets(recs, side, nfork)
-        last_fork = next((r[3] for r in reversed(recs) if r[0] == '@fork'), None)      # in LIST order (the reduce forks got their tokens later)
+            emit[type(u)](b, u)
+        recs, side = b.recs, b.side
+        for idx, reqs in b.pending.items():                 # rebuild the producers with the statistics requests they serve
+            recs[idx] = b.remake[idx](reqs)
+        self.producer_stat_units = sum(len(v) for v in b.pending.values())
+        self._mark_buckets(recs, side, b.grad_log)
+        last_fork = next((r[3] for r in reversed(recs) if r[0] == '@fork'), None)      # in LIST order (tokens need not follow it)
         if side is not None and last_fork is not None:
             recs.append(('@join', side, last_fork))             # side-stream work is in order: the last fork covers all
         return recs
 
-    def _mark_buckets(self, recs, side, nfork=None):
+    def _bwd_det(self, b, u):
+        x = u.x
+        tmp = self._det_bias_tmp(u)
+        b.add(ops.rec_colsum(u.gdet, tmp, self.bn_ws))
+        b.add(ops.rec_copy_f32(tmp[:u.K], b.grad(u.conv.bias)))                                # Kp-padded column sums -> the bias gradient
+        gw = b.grad(u.conv.weight)
+        b.wgrad(lambda ws: ops.rec_conv_wgrad(x.t(), u.gdet, gw, None, 1, 1, 1, 0, ws), pixels=x.n * x.h * x.w)
+        if not x.needs_grad:
+            return
+        self.packs.add(u.conv.weight, None, 1, 0, ops.PACK_DGRAD, u.wpd, K=u.Kp)
+        acc = self._contrib(x)
+        b.add_producer(x, 'dgrad', lambda st: ops.rec_conv_dgrad(u.gdet, u.wpd, x.g(), 1, 1, 1, 0, accumulate=acc, stats=st),
+                       self._dgrad_slabs(x, u.Kp, 1, 1, 0))
+
+    def _bwd_up(self, b, u):
+        if u.x.needs_grad:
+            b.add(ops.rec_upsample_bwd(u.out.gread(), u.x.g(), accumulate=self._contrib(u.x)))
+            b.note_grad(u.x, 'other')
+
+    def _bwd_pool(self, b, u):
+        a = u.x
+        if a.needs_grad:
+            b.add(ops.rec_sppf_pool_bwd(a.g(), u.outs[0].g(), u.outs[1].g(), u.outs[2].g(), u.idx, a.gfinal))
+            b.note_grad(a, 'other')
+
+    def _dgrad_slabs(self, xv, K, k, s, p):
+        """statistics slabs a data-gradient launch into xv could serve (0: none)"""
+        return ops.conv_dgrad_stat_slabs(xv.n, xv.h, xv.w, xv.c, K, k, k, s, p, self.dtype) if self.dtype == torch.bfloat16 else 0
+
+    def _bn_bwd_mode(self, u, b):
+        """How a ConvUnit's BatchNorm / SiLU backward is done: (consumer, statistics mode).
+        consumer    who applies it: 'dy' (an apply pass writes a dy tensor for the weight- and data-gradient launches), 'fused_1x1' (the one-launch
+                    1x1 backward) or 'fused_stem' (the stem's weight gradient; the stem has no data gradient, so its dy would have that one reader)
+        mode        where SUM du, SUM du*xhat come from: 'sync' (local pass + all-reduce), 'producer' (the launches that completed dz), 'pair' (one
+                    pass over both halves of a C3 pair), 'single' (one pass per module), 'frozen' (constant scale / shift: no statistics)"""
+        live = u.has_bn and not u.frozen
+        sync = bool(self.sync) and live
+        if self._fusable_1x1(u) and not sync:
+            consumer = 'fused_1x1'
+        elif (STEM_FUSED and u.stem and live and not sync and len(u.mods) == 1 and u.mods[0].conv.weight.requires_grad
+              # the last unit of the backward list only: the c1 / c2 it reads from the statistics workspace on the side stream are not
+              # overwritten before the list's final join
+              and u is next(q for q in self.units if isinstance(q, ConvUnit))
+              and ops.wgrad_stem_fused_ok(self.B, self.H, self.W, u.K, self.dtype)):
+            consumer = 'fused_stem'
+        else:
+            consumer = 'dy'
+        if sync:
+            mode = 'sync'
+        elif (consumer != 'fused_stem' and PRODUCER_STATS != '0' and self.dtype == torch.bfloat16 and live and not USE_GRAPHS
+              and b.producers(u.outs) is not None):
+            mode = 'producer'
+        elif u.frozen:
+            mode = 'frozen'
+        else:
+            mode = 'pair' if len(u.mods) == 2 else 'single'
+        return consumer, mode
+
+    @staticmethod
+    def _channels(u):
+        """(module, output value, its channel slice of the unit's K-wide tensors) of every module of a ConvUnit"""
+        k0 = 0
+        for m, o in zip(u.mods, u.outs):
+            yield m, o, slice(k0, k0 + m.conv.out_channels)
+            k0 += m.conv.out_channels
+
+    # One emitter per statistics mode.  dy: the tensor to write, None when a fused consumer applies the coefficients itself; each returns the
+    # (c1, c2) that consumer reads.
+    def _bn_bwd_sync(self, b, u, dy, M):
+        # SyncBatchNorm: local statistics pass (local dgamma / dbeta: the gradient all-reduce sums them), its partial slabs -> fp64 sums
+        # -> all-reduce -> c1 / c2 of the GLOBAL batch in the bn_c12 rows -> one apply pass
+        c1, c2 = self.bn_c12[0, :u.K], self.bn_c12[1, :u.K]
+        nb = ops.bn_bwd_blocks(M)
+        for m, o, ch in self._channels(u):
+            K = ch.stop - ch.start
+            buf = self.sync_sums[:2 * K + 1]
+            b.add(ops.rec_bn_act_bwd(o.gread(), u.yraw[..., ch], u.scale[ch], u.shift[ch], u.mean[ch], u.invstd[ch], None,
+                                     b.grad(m.bn.weight), b.grad(m.bn.bias), self.bn_ws, act=u.act))
+            b.add(ops.rec_bn_slab_sums(self.bn_ws[:nb * 2 * K].view(nb, 2, K), nb, K, M, buf))
+            b.add(self._sync_call(buf))
+            b.add(ops.rec_bn_bwd_coeffs_sums(buf, K, c1[ch], c2[ch]))
+        self._bn_bwd_apply(b, u, c1, c2, dy)
+        return c1, c2
+
+    def _bn_bwd_producer(self, b, u, dy, M):
+        # the launches that wrote the last contribution to each output's gradient leave (SUM du, SUM du*xhat) slabs; a finalize launch per
+        # module turns them into dgamma / dbeta and c1 / c2 in the bn_c12 rows
+        c1, c2 = self.bn_c12[0, :u.K], self.bn_c12[1, :u.K]
+        for (m, o, ch), (kind, idx, off, nslabs) in zip(self._channels(u), b.producers(u.outs)):
+            slabs = self._new(nslabs, 2, o.c, dtype=torch.float32, zero=True)     # workgroups without tiles never write theirs
+            b.pending.setdefault(idx, []).append(ops.StatRequest(u.yraw[..., ch], u.scale[ch], u.shift[ch], slabs, off, u.act))
+            b.add(ops.rec_bn_bwd_finalize_slabs(slabs, M, u.mean[ch], u.invstd[ch], b.grad(m.bn.weight), b.grad(m.bn.bias), c1[ch], c2[ch]))
+        if dy is not None:
+            self._bn_bwd_apply(b, u, c1, c2, dy)
+        return c1, c2
+
+    def _bn_bwd_pair(self, b, u, dy, M):
+        # c1 / c2: where the kernel's finalize stage leaves them in the statistics workspace
+        ma, mb = u.mods
+        b.add(ops.rec_bn_act_bwd_pair(u.outs[0].gread(), u.outs[1].gread(), u.yraw, u.scale, u.shift, u.mean, u.invstd, dy,
+                                      b.grad(ma.bn.weight), b.grad(ma.bn.bias), b.grad(mb.bn.weight), b.grad(mb.bn.bias), self.bn_ws, act=u.act))
+        return ops.bn_bwd_coeffs(self.bn_ws, M, u.K)
+
+    def _bn_bwd_single(self, b, u, dy, M):
+        # c1 / c2: as for the pair
+        for m, o, ch in self._channels(u):
+            b.add(ops.rec_bn_act_bwd(o.gread(), u.yraw[..., ch], u.scale[ch], u.shift[ch], u.mean[ch], u.invstd[ch], None if dy is None else dy[..., ch],
+                                     b.grad(m.bn.weight), b.grad(m.bn.bias), self.bn_ws, act=u.act))
+        return ops.bn_bwd_coeffs(self.bn_ws, M, u.K)
+
+    def _bn_bwd_frozen(self, b, u, dy, M):
+        # no statistics, no parameter gradients, no c1 / c2 (and no fused consumer)
+        for m, o, ch in self._channels(u):
+            b.add(ops.rec_bn_act_bwd(o.gread(), u.yraw[..., ch], u.scale[ch], u.shift[ch], None, None, dy[..., ch], None, None, self.bn_ws, act=u.act))
+        return None, None
+
+    def _bn_bwd_apply(self, b, u, c1, c2, dy):
+        b.add(ops.rec_bn_act_bwd_apply(u.outs[0].gread(), u.outs[1].gread() if len(u.outs) > 1 else None, u.yraw, u.scale, u.shift, u.mean, u.invstd,
+                                       c1, c2, dy, act=u.act))
+
+    def _bwd_conv(self, b, u):
+        if not u.outs[0].needs_grad:
+            return
+        o0 = u.outs[0]
+        M = o0.n * o0.h * o0.w
+        consumer, mode = self._bn_bwd_mode(u, b)
+        dy = slot = None
+        if consumer == 'dy':
+            slot = b.next_slot()
+            dy = self.dy_ring[slot][:M * u.K].view(o0.n, o0.h, o0.w, u.K)
+        c1, c2 = getattr(self, '_bn_bwd_' + mode)(b, u, dy, M)
+        x = self.prep if u.stem else u.x.t()
+        want_w = any(m.conv.weight.requires_grad for m in u.mods)
+        want_x = not u.stem and u.x is not self.input and u.x.needs_grad
+        acc, xv = False, u.x
+        if want_x:
+            wb = u.mods[1].conv.weight if len(u.mods) > 1 else None
+            self.packs.add(u.mods[0].conv.weight, wb, u.s, u.p, ops.PACK_DGRAD, u.wpd)
+            if xv.parts is not None:
+                # writing the whole concat gradient: no part may already hold a partial contribution
+                if any(pv.ginit for pv, _ in xv.parts) and not xv.ginit:
+                    raise _lib.HdyError('gradient ordering not plannable: a concat input receives gradient before the concat')
+                acc = xv.ginit
+                xv.ginit = True
+            else:
+                acc = self._contrib(xv)
+        if consumer == 'fused_1x1':
+            if want_w or want_x:
+                ga = b.grad(u.mods[0].conv.weight) if want_w else None
+                gb = b.grad(u.mods[1].conv.weight) if want_w and len(u.mods) > 1 else None
+                mk = (lambda st: ops.rec_conv1x1_bwd_fused(
+                    u.outs[0].gread(), u.outs[1].gread() if len(u.mods) > 1 else None, u.yraw, u.scale, u.shift, u.mean, u.invstd, c1, c2, x,
+                    u.wpd if want_x else None, xv.g() if want_x else None, ga, gb, self.f1_ws, accumulate_dx=acc, stats=st))
+                if want_x:
+                    b.add_producer(xv, 'fused', mk, ops.fused_1x1_stat_slabs(M, u.C, u.K, self.dtype))
+                else:
+                    b.add(mk(None))
+            return
+        stem_hw = (self.H, self.W) if u.stem else None
+        ga = b.grad(u.mods[0].conv.weight)          # (logged for frozen filters too: the record behind them bounds their range's mark)
+        gb = b.grad(u.mods[1].conv.weight) if len(u.mods) > 1 else None
+        if consumer == 'fused_stem':
+            b.wgrad(lambda ws: ops.rec_conv_wgrad_stem_fused(x, o0.gread(), u.yraw, u.scale, u.shift, u.mean, u.invstd, c1, c2, stem_hw, ga, None, ws))
+            return
+        if want_w:
+            b.wgrad(lambda ws: ops.rec_conv_wgrad(x, dy, ga, gb, u.k, u.k, u.s, u.p, ws, stem_hw=stem_hw), pixels=M, reads_slot=slot)
+        if want_x:
+            b.add_producer(xv, 'dgrad', lambda st: ops.rec_conv_dgrad(dy, u.wpd, xv.g(), u.k, u.k, u.s, u.p, accumulate=acc, stats=st),
+                           self._dgrad_slabs(xv, u.K, u.k, u.s, u.p))
+
+    def _mark_buckets(self, recs, side, log):
         """Data-parallel overlap (reference: DDP's autograd-hook buckets, train.py:331): cut the flat gradient buffer into ranges of
         about GRAD_BUCKET_BYTES and insert, behind the launch record that completes a range, a '@call' that tells the engine so.
         Parameters are laid out in registration (= forward) order and the backward list runs in reverse, so ranges complete from the
         end of the buffer; a range's mark sits behind the LAST record writing into it whatever the order.  Gradients this list does
         not produce (frozen parameters, the mask head's, which MaskBranchFn writes before the list runs) are final from the start."""
-        log, self._grad_log = self._grad_log, None
         store = self.grad_store
         done = {}
         for q, pos in log:

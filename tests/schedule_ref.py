@@ -8,6 +8,7 @@ list too), and `('@call', fn)` host callbacks.  Nothing here launches a kernel; 
   windows(recs)     for every fork: the main-stream records that may run beside it, plus the structural rules of a list
   footprint(rec)    the bytes every pointer argument of a launch record covers, and whether the launch may write them
   conflicts(recs)   every (forked record, main record in its window) pair whose footprints overlap with one side writable: a data race
+  canonical(recs)   the list with addresses replaced by (storage ordinal, offset, shape of the region): equal for equal lists over other memory
   writers(...)      launch records that may write a byte range, from a list position on (the "gradient range is final" marks)
   early / late      the two extreme legal orders of a list, run on ONE stream: a missing join makes them compute different numbers
 
@@ -224,6 +225,57 @@ def footprint(rec):
                         out.append(Access(f'{p.name}[{i}].{f}', write, _extent(fa, keep, f'{name}[{p.name}[{i}].{f}]')))
             continue
         out.append(Access(p.name, not p.const, _extent(a, keep, f'{name}[{p.name}]')))
+    return out
+
+
+# ------------------------------------------------------------------------------------------ canonical form
+STAT_REQ_POINTERS = ('y', 'scale', 'shift', 'slabs')
+
+
+def canonical(recs):
+    """The list with the addresses taken out, for comparing two lists built over different allocations: per record the symbol and its
+    arguments, scalars verbatim, a null pointer as None, every other pointer as (ordinal of its underlying storage in order of first
+    appearance in the list, byte offset inside that storage, rows, row bytes, pitch of the region behind it).  An hdy_stat_req array becomes
+    its requests field by field; '@fork' keeps its token and the canonical form of its records, '@join' its token, '@call' the range of its
+    `hdy_mark` or the tag 'host'.  A pointer no kept tensor accounts for raises ScheduleError, as in footprint()."""
+    ordinal = {}
+
+    def pointer(p, keep, what):
+        r = _extent(p, keep, what)
+        bases = {t.untyped_storage().data_ptr() for t in keep if t.data_ptr() <= p < max(region_of(t).hi, t.data_ptr() + 1)}
+        if len(bases) != 1:
+            raise ScheduleError(f'{what} = {p:#x}: the tensors kept there belong to {len(bases)} storages')
+        base = bases.pop()
+        return (ordinal.setdefault(base, len(ordinal)), p - base, r.rows, r.row, r.pitch)
+
+    def launch(rec):
+        name, args = rec[0], rec[1]
+        footprint(rec)                          # the structural checks: declared, argument count, request array kept
+        keep = [t for t in rec[2] if hasattr(t, 'data_ptr')]
+        out = []
+        for p, v in zip(prototypes()[name], args):
+            if not p.pointer:
+                out.append(v.value if isinstance(v, ctypes._SimpleCData) else v)
+            elif _addr(v) == 0:
+                out.append(None)
+            elif 'hdy_stat_req' in p.ctype:
+                arr = next(x for x in rec[3] if ctypes.addressof(x) == _addr(v))
+                out.append(tuple(tuple(pointer(getattr(q, f), keep, f'{name}[{p.name}[{i}].{f}]') if f in STAT_REQ_POINTERS and getattr(q, f) else
+                                       getattr(q, f) for f, _ in q._fields_) for i, q in enumerate(arr)))
+            else:
+                out.append(pointer(_addr(v), keep, f'{name}[{p.name}]'))
+        return (name, tuple(out))
+
+    out = []
+    for r in recs:
+        if r[0] == '@fork':
+            out.append(('@fork', r[3], tuple(launch(q) for q in r[2])))
+        elif r[0] == '@join':
+            out.append(('@join', r[2]))
+        elif r[0] == '@call':
+            out.append(('@call', tuple(r[1].hdy_mark) if hasattr(r[1], 'hdy_mark') else 'host'))
+        else:
+            out.append(launch(r))
     return out
 
 

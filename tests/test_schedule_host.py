@@ -259,6 +259,59 @@ def test_early_marks_sees_a_writer_behind_the_mark():
     assert S.writers(bad, flat.data_ptr() + 40 * 4, flat.data_ptr() + 41 * 4) == [(0, 'hdy_copy_f32', 'dst')]
 
 
+# ------------------------------------------------------------------------------------------ canonical form
+def canon_list(dy_off=16, first='hdy_bn_act_bwd', second_forked=True, join_at=4):
+    """one small two-stream list over FRESH allocations: BatchNorm backward into a channel slice of a wide buffer, two forked weight gradients
+    (one fed by a data gradient that serves a statistics request), a mark, a host call, the join"""
+    x, wide, bn_ws, wg_ws, flat = nhwc_buf(8), nhwc_buf(48), torch.zeros(64), torch.zeros(100), torch.zeros(2 * 16 * 8 * 9 + 32)
+    dz, y, dx, wp, scale = nhwc_buf(16), nhwc_buf(16), nhwc_buf(8), torch.zeros(16 * 8, dtype=torch.bfloat16), torch.zeros(16)
+    g1, g2, dg, db = flat[:1152].view(16, 8, 3, 3), flat[1152:2304].view(16, 8, 3, 3), flat[2304:2320], flat[2320:]
+    dy = wide[..., dy_off:dy_off + 16]
+    a = bn_bwd(dz, y, dy, dg, db, bn_ws) if first == 'hdy_bn_act_bwd' else S.record(first, src=dg, dst=db, n=16)
+    slabs = torch.zeros(3, 2, 8)
+    arr = (_lib.StatReq * 1)(_lib.StatReq(y[..., 8:].data_ptr(), 16, scale[8:].data_ptr(), None, slabs.data_ptr(), 0, 8, 1, 3))
+    d = S.record('hdy_conv_dgrad_stats', dy=dy, lddy=48, w_packed_dgrad=wp, dx=dx, lddx=8, nstat=1)
+    args = list(d[1])
+    args[[p.name for p in S.prototypes()[d[0]]].index('stats')] = ctypes.cast(arr, ctypes.c_void_p)
+    d = (d[0], tuple(args), d[2] + (y[..., 8:], scale[8:], slabs), (arr,))
+    mark = lambda: None
+    mark.hdy_mark = (1152, 2304)
+    w1, w2 = wgrad(x, dy, g1, wg_ws), wgrad(dx, dy, g2, wg_ws)
+    recs = [a, d, fork(0, w1, w2) if second_forked else fork(0, w1), ('@call', mark), ('@call', lambda: None)]
+    if not second_forked:
+        recs.insert(3, w2)
+    recs.insert(join_at, join(0))
+    return recs
+
+
+def test_canonical_form_is_free_of_addresses_and_sees_every_change():
+    base = S.canonical(canon_list())
+    assert base == S.canonical(canon_list())                    # same structure, other allocations
+    kinds = [r[0] for r in base]
+    assert kinds == ['hdy_bn_act_bwd', 'hdy_conv_dgrad_stats', '@fork', '@call', '@join', '@call']
+    assert base[3] == ('@call', (1152, 2304)) and base[5] == ('@call', 'host') and base[4] == ('@join', 0) and base[2][1] == 0
+    # storages are numbered as they first appear (dz, y, the wide buffer ...); a channel slice keeps its offset and its rows at the pitch
+    bn = dict(zip([p.name for p in S.prototypes()['hdy_bn_act_bwd']], base[0][1]))
+    assert bn['dz'] == (0, 0, 1, 30 * 16 * 2, 30 * 16 * 2) and bn['y'][0] == 1 and bn['dy'] == (2, 16 * 2, 30, 16 * 2, 48 * 2) and bn['mean'] is None
+    assert bn['lddy'] == 48 and bn['dbeta'][:2] == (bn['dgamma'][0], bn['dgamma'][1] + 64)
+    # both forked weight gradients write one flat buffer at their offsets, and read the dy the first record wrote
+    w1, w2 = (dict(zip([p.name for p in S.prototypes()['hdy_conv_wgrad']], q[1])) for q in base[2][2])
+    assert w1['grad_a'][:2] == (bn['dgamma'][0], 0) and w2['grad_a'][:2] == (bn['dgamma'][0], 1152 * 4) and w1['dy'] == w2['dy'] == bn['dy']
+    # the request array, field by field: y is a slice of the second storage, the null shift stays None, scalars verbatim
+    req, = dict(zip([p.name for p in S.prototypes()['hdy_conv_dgrad_stats']], base[1][1]))['stats']
+    assert req[0] == (1, 8 * 2, 30, 8 * 2, 16 * 2) and req[1] == 16 and req[2][1] == 8 * 4 and req[3] is None and req[5:] == (0, 8, 1, 3)
+    for other in (canon_list(dy_off=24),                        # a changed offset
+                  canon_list(first='hdy_copy_f32'),             # a changed symbol
+                  canon_list(second_forked=False),              # a record moved from the fork to the main list
+                  canon_list(join_at=3)):                       # a moved join
+        assert S.canonical(other) != base
+    # a pointer that no kept tensor accounts for is an error here too
+    recs = canon_list()
+    recs[0] = (recs[0][0], recs[0][1], recs[0][2][1:])
+    with pytest.raises(S.ScheduleError, match=r'hdy_bn_act_bwd\[dz\]'):
+        S.canonical(recs)
+
+
 # ------------------------------------------------------------------------------------------ the two extreme orders
 def drive(recs, log):
     """ops.run's dispatch without a device: launch records are logged instead of launched"""
