@@ -1,7 +1,7 @@
-// C-ABI entry points for the convolution family (see include/hdyolo.h).  Everything here is host code that
-// validates shapes, derives the tap-window geometry and launches the kernels (forward / data gradient: through conv_dispatch.hip's
-// hdy_conv_launch; weight gradient: conv_wgrad*.hip) on the caller's stream.  No allocation, no synchronisation; process state = the
-// option table below (atomics, initialised once from the environment), the per-kernel "LDS size attribute set" once-flags, and the thread-local error text / dispatch log.
+// C-ABI entry points for the convolution family (see include/hdyolo.h): options, error text, the dispatch log, weight packing and the
+// forward / data-gradient entry points.  Everything here is host code that validates shapes, derives the tap-window geometry and hands
+// the launch to conv_dispatch.hip's hdy_conv_launch on the caller's stream; the weight-gradient entry points live in conv_dispatch.hip
+// next to their kernel selection.  No allocation, no synchronisation; process state = the option table below (atomics, initialised once from the environment), the per-kernel "LDS size attribute set" once-flags, and the thread-local error text / dispatch log.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,8 +13,6 @@
 #include "hdyolo_internal.h"
 #include "hdyolo.h"
 
-int hdy_wgrad_reduce_launch(const float* partial, int splits, size_t slab_stride, int K, int Q, int mode, int C, int R, int S, float* grad,
-                            int accumulate, hipStream_t st);
 int hdy_pack_weight_launch(const hdy_pack_desc& d, hipStream_t st);
 int hdy_pack_batch_launch(const hdy_pack_desc* table, int n, int total_blocks, hipStream_t st);
 
@@ -33,7 +31,7 @@ const OptDef g_opt_def[HDY_OPT_COUNT] = {
     {"HDY_NO_CLASS_WALK", 0, true}, {"HDY_NO_CONV3X3", 0, true}, {"HDY_C3_GRID", 0, false}, {"HDY_NO_CONV3X3S2", 0, false},
     {"HDY_NO_DGRAD_S2", 0, false}, {"HDY_TILE_INTERLEAVE", 1, false}, {"HDY_NO_BIG_TILES", 0, true}, {"HDY_NO_STEM_KERNEL", 0, true},
     {"HDY_WGRAD_BLOCKS", 512, false}, {"HDY_NO_STEM_WGRAD", 0, true}, {"HDY_NO_WGRAD3X3", 0, true}, 
-    {"HDY_LOSS_GRID", 2048, false}, {"HDY_NO_DEEP", 0, true}, {"HDY_NO_WGRAD_S2", 0, true}, {"HDY_NO_WGRAD_DEEP", 0, true}, {"HDY_DEEP_BN", 0, false}, {"HDY_DEEP_DEBUG", 0, false}, {"HDY_DEEP_ALL", 1, false}, {"HDY_DEEP_MIN_TILES", 160, false}, {"HDY_DEEP_WALK", 2, false}, {"HDY_NO_BN_REDUCE4", 0, true},
+    {"HDY_LOSS_GRID", 2048, false}, {"HDY_NO_DEEP", 0, true}, {"HDY_NO_WGRAD_DEEP", 0, true}, {"HDY_DEEP_BN", 0, false}, {"HDY_DEEP_DEBUG", 0, false}, {"HDY_DEEP_ALL", 1, false}, {"HDY_DEEP_MIN_TILES", 160, false}, {"HDY_DEEP_WALK", 2, false}, {"HDY_NO_BN_REDUCE4", 0, true},
     {"HDY_WGRAD_TILE", 0, false}, {"HDY_SPPF_NO_KEYS", 0, true}, {"HDY_WGRAD_DEEP_KMIN", 192, false}, {"HDY_NO_CONV3X3_C128", 0, true}, {"HDY_NO_F1X1_96", 0, true},
     {"HDY_AP_CHUNK", 0, false}, {"HDY_AP_NO_PRUNE", 0, true},
 };
@@ -369,108 +367,6 @@ static int dgrad_impl(const void* dy, int lddy, const void* w_packed_dgrad, void
             if (rc) return rc;
         }
     return HDY_OK;
-}
-
-size_t hdy_conv_wgrad_workspace_bytes(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype, int stem) {
-    const int Ho = hdy_conv_out_dim(H, R, stride, pad), Wo = hdy_conv_out_dim(W, S, stride, pad);
-    const int Q = stem ? R * S * 4 : R * S * C;
-    int splits = 1, pps = 64;
-    hdy_wgrad_plan(K, Q, (long long)N * Ho * Wo, dtype, &splits, &pps);
-    if (stem) {
-        const int g = hdy_wgrad_stem_grid(N, Ho, Wo, K, dtype);        // patch-resident stem kernel: one slab per workgroup
-        if (g > splits) splits = g;
-    }
-    size_t bytes = (size_t)splits * K * Q * sizeof(float);
-    if (!stem && R == 3 && S == 3 && pad == 1) {                       // patch-resident 3x3 kernel: its own split count
-        const size_t b3 = hdy_wgrad3x3_workspace_bytes(N, Ho, Wo, C, K, stride, dtype);
-        if (b3 > bytes) bytes = b3;
-    }
-    if (!stem) {                                                       // deep-pipelined 256 x 256 kernel: one slab per pixel split of its own plan
-        const size_t bd = hdy_wgrad_deep_workspace_bytes(N, H, W, Ho, Wo, C, K, R, S, stride, dtype);
-        if (bd > bytes) bytes = bd;
-    }
-    return bytes;
-}
-
-// grad_a [K_a][C][R][S] (and optionally grad_b [K_b][C][R][S], the lower rows of a stacked weight) (+)= dW.
-int hdy_conv_wgrad(const void* x, int ldx, const void* dy, int lddy, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
-                   float* grad_a, int K_a, float* grad_b, int K_b, int accumulate, void* workspace, size_t ws_bytes, int dtype, int stem,
-                   void* stream) {
-    HDY_ARG(grad_a && K_a > 0 && K_a + K_b <= K && K_b >= 0 && (K_b == 0) == (grad_b == nullptr), "conv_wgrad: bad gradient split");
-    HDY_ARG(dtype == HDY_BF16 || dtype == HDY_F32, "conv_wgrad: unknown dtype %d", dtype);
-    HDY_ARG(workspace && ws_bytes >= hdy_conv_wgrad_workspace_bytes(N, H, W, C, K, R, S, stride, pad, dtype, stem), "conv_wgrad: workspace too small");
-    WgradArgs a = {};
-    a.x = x; a.dy = dy; a.partial = (float*)workspace;
-    a.N = N; a.K = K; a.lddy = lddy;
-    a.Ho = hdy_conv_out_dim(H, R, stride, pad);
-    a.Wo = hdy_conv_out_dim(W, S, stride, pad);
-    HDY_ARG(a.Ho > 0 && a.Wo > 0, "conv_wgrad: empty dy");
-    if (stem) {
-        HDY_ARG(C == 3 && R == 6 && S == 6 && stride == 2 && pad == 2 && ldx == 4, "conv_wgrad: stem expects C=3 k=6 s=2 p=2 on a 4-channel padded image");
-        a.Hin = H + 2 * pad; a.Win = W + 2 * pad; a.C = 24; a.ldx = 4; a.span_pixels = 1;
-        a.ih_mul = a.iw_mul = 2; a.dh0 = a.dw0 = 0; a.TH = 6; a.TW = 1;
-    } else {
-        a.Hin = H; a.Win = W; a.C = C; a.ldx = ldx;
-        a.ih_mul = a.iw_mul = stride; a.dh0 = a.dw0 = -pad; a.TH = R; a.TW = S;
-    }
-    const int Q = a.TH * a.TW * a.C;
-    const int stem_grid = stem ? hdy_wgrad_stem_grid(N, a.Ho, a.Wo, K, dtype) : 0;
-    int rc;
-    if (!stem && R == 3 && S == 3 && pad == 1 &&
-        hdy_wgrad3x3_try(x, ldx, dy, lddy, N, H, W, a.Ho, a.Wo, C, K, stride, a.partial, dtype, (hipStream_t)stream, &a.splits, &rc)) {
-        // patch-resident kernel launched (conv_wgrad3x3.hip)
-    } else if (!stem && hdy_wgrad_deep_try(x, ldx, dy, lddy, N, H, W, a.Ho, a.Wo, C, K, R, S, stride, pad, a.partial, dtype, (hipStream_t)stream, &a.splits, &rc)) {
-        // deep-pipelined 256 x 256 kernel launched (conv_wgrad_deep.hip)
-    } else if (stem_grid > 0) {
-        a.splits = stem_grid;
-        rc = hdy_wgrad_stem_launch(a, stem_grid, (hipStream_t)stream);
-    } else {
-        hdy_wgrad_plan(K, Q, (long long)N * a.Ho * a.Wo, dtype, &a.splits, &a.pix_per_split);
-        rc = hdy_wgrad_launch(a, dtype, (hipStream_t)stream);
-    }
-    if (rc) return rc;
-    const int mode = stem ? 1 : 0;
-    rc = hdy_wgrad_reduce_launch(a.partial, a.splits, (size_t)K * Q, K_a, Q, mode, C, R, S, grad_a, accumulate, (hipStream_t)stream);
-    if (rc) return rc;
-    if (K_b) {
-        // rows K_a.. of every slab belong to the second tensor
-        rc = hdy_wgrad_reduce_launch(a.partial + (size_t)K_a * Q, a.splits, (size_t)K * Q, K_b, Q, mode, C, R, S, grad_b, accumulate,
-                                     (hipStream_t)stream);
-    }
-    return rc;
-}
-
-// The stem's weight gradient with the BatchNorm / SiLU backward of its unit applied while the tile is staged (conv_wgrad.hip,
-// wgrad_stem_kernel<.., true>): dz = gradient of the unit's output, y = its raw conv output, c1 / c2 from the statistics pass
-// (hdy_bn_act_bwd with dy == NULL).  The stem has no data gradient, so dy is never materialised.  bf16, K in {16, 32, 64}.
-int hdy_conv_wgrad_stem_fused_ok(int N, int H, int W, int K) {
-    if (K != 16 && K != 32 && K != 64) return 0;
-    const int Ho = hdy_conv_out_dim(H, 6, 2, 2), Wo = hdy_conv_out_dim(W, 6, 2, 2);
-    return hdy_wgrad_stem_grid(N, Ho, Wo, K, HDY_BF16) > 0 ? 1 : 0;
-}
-
-int hdy_conv_wgrad_stem_fused(const void* x, const void* dz, int lddz, const void* y, int ldy, const float* scale, const float* shift, const float* mean,
-                              const float* invstd, const float* c1, const float* c2, int N, int H, int W, int K, float* grad_a, int K_a, float* grad_b,
-                              int K_b, int accumulate, void* workspace, size_t ws_bytes, void* stream) {
-    HDY_ARG(x && dz && y && grad_a && K_a > 0 && K_a + K_b <= K && K_b >= 0 && (K_b == 0) == (grad_b == nullptr), "conv_wgrad_stem_fused: bad arguments");
-    HDY_ARG(hdy_conv_wgrad_stem_fused_ok(N, H, W, K), "conv_wgrad_stem_fused: shape not served (K in {16, 32, 64}, output a multiple of 16 x 32)");
-    HDY_ARG(workspace && ws_bytes >= hdy_conv_wgrad_workspace_bytes(N, H, W, 3, K, 6, 6, 2, 2, HDY_BF16, 1), "conv_wgrad_stem_fused: workspace too small");
-    WgradArgs a = {};
-    a.x = x; a.dy = dz; a.lddy = lddz; a.partial = (float*)workspace;
-    a.y = y; a.ldy = ldy; a.bn_scale = scale; a.bn_shift = shift; a.bn_mean = mean; a.bn_invstd = invstd; a.bn_c1 = c1; a.bn_c2 = c2;
-    a.N = N; a.K = K;
-    a.Ho = hdy_conv_out_dim(H, 6, 2, 2);
-    a.Wo = hdy_conv_out_dim(W, 6, 2, 2);
-    a.Hin = H + 4; a.Win = W + 4; a.C = 24; a.ldx = 4; a.span_pixels = 1;
-    a.ih_mul = a.iw_mul = 2; a.dh0 = a.dw0 = 0; a.TH = 6; a.TW = 1;
-    const int Q = a.TH * a.TW * a.C;
-    a.splits = hdy_wgrad_stem_grid(N, a.Ho, a.Wo, K, HDY_BF16);
-    int rc = hdy_wgrad_stem_launch(a, a.splits, (hipStream_t)stream);
-    if (rc) return rc;
-    rc = hdy_wgrad_reduce_launch(a.partial, a.splits, (size_t)K * Q, K_a, Q, 1, 3, 6, 6, grad_a, accumulate, (hipStream_t)stream);
-    if (rc) return rc;
-    if (K_b) rc = hdy_wgrad_reduce_launch(a.partial + (size_t)K_a * Q, a.splits, (size_t)K * Q, K_b, Q, 1, 3, 6, 6, grad_b, accumulate, (hipStream_t)stream);
-    return rc;
 }
 
 }  // extern "C"

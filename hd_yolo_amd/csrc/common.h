@@ -32,7 +32,6 @@ enum HdyOption {
     HDY_OPT_NO_WGRAD3X3,       // HDY_NO_WGRAD3X3: patch-resident 3x3 weight gradient off
     HDY_OPT_LOSS_GRID,         // HDY_LOSS_GRID: workgroups of the detection loss' dense pass (default 2048)
     HDY_OPT_NO_DEEP,           // HDY_NO_DEEP: deep-pipelined 256-row implicit GEMM off (generic kernel instead)
-    HDY_OPT_NO_WGRAD_S2,       // HDY_NO_WGRAD_S2: tap-walking stride-2 3x3 weight gradient off
     HDY_OPT_NO_WGRAD_DEEP,     // HDY_NO_WGRAD_DEEP: deep-pipelined 256 x 256 weight gradient off (generic weight gradient instead)
     HDY_OPT_DEEP_BN,           // HDY_DEEP_BN: column tile of the deep-pipelined kernel (0 = by shape, 128, 256)
     HDY_OPT_DEEP_DEBUG,        // HDY_DEEP_DEBUG: timing ablations of the deep-pipelined kernel (bit mask, results wrong; measurement only)

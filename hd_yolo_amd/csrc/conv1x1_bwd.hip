@@ -445,9 +445,6 @@ inline int tile_rows(int K) { return K >= 96 ? 64 : 128; }
 
 }  // namespace
 
-int hdy_wgrad_reduce_launch(const float* partial, int splits, size_t slab_stride, int K, int Q, int mode, int C, int R, int S, float* grad,
-                            int accumulate, hipStream_t st);
-
 extern "C" {
 
 // 1 when hdy_conv1x1_bwd_fused has a kernel for this (C, K, dtype)
@@ -535,10 +532,7 @@ static int fused_impl(const void* dz_a, int lddz_a, const void* dz_b, int lddz_b
     else if (K == 96) rc = fused_launch<96, 96, 64, 2>(a, grid, st);          // round 6: yolov5m's 96-wide 1x1 units (two 64-channel sub-tiles per row, the second half full)
     else rc = fused_launch<128, 128, 64, 1>(a, grid, st);
     if (rc || !grad_a) return rc;
-    rc = hdy_wgrad_reduce_launch(a.partial, grid, (size_t)K * C, K_a, C, 0, C, 1, 1, grad_a, accumulate_w, st);
-    if (rc) return rc;
-    if (K_b) rc = hdy_wgrad_reduce_launch(a.partial + (size_t)K_a * C, grid, (size_t)K * C, K_b, C, 0, C, 1, 1, grad_b, accumulate_w, st);
-    return rc;
+    return hdy_wgrad_reduce(a.partial, grid, K, C, 0, C, 1, 1, grad_a, K_a, grad_b, K_b, accumulate_w, st);
 }
 
 }  // extern "C"

@@ -1,8 +1,11 @@
-// Kernel selection and launch of the convolution forward / data-gradient families (host code only).
+// Kernel selection and launch of the convolution families (host code only).
 //
-// conv_fwd_plan() is the one ordered walk over the families: each family's <name>_plan (in its own file) says whether a ConvShape is
-// its own and, if so, with which instance, grid and statistic-slab count.  The sizing query (hdy_conv_stat_slabs) and the launch
-// (hdy_conv_launch) below both read that plan, so the slab array a caller sized is the one the kernel about to start writes.
+// Forward / data gradient: conv_fwd_plan() is the one ordered walk over the families: each family's <name>_plan (in its own file) says
+// whether a ConvShape is its own and, if so, with which instance, grid and statistic-slab count.  The sizing query (hdy_conv_stat_slabs)
+// and the launch (hdy_conv_launch) below both read that plan, so the slab array a caller sized is the one the kernel about to start writes.
+//
+// Weight gradient: the same with WgradShape / WgradPlan and wgrad_plan(); the workspace query (hdy_conv_wgrad_workspace_bytes) and the
+// entry points that launch (hdy_conv_wgrad, hdy_conv_wgrad_stem_fused) are at the end of this file.
 #include "common.h"
 #include "hdyolo_internal.h"
 #include "hdyolo.h"
@@ -117,3 +120,108 @@ int hdy_conv_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st) {
         first = p.family + 1;
     }
 }
+
+// ---- weight gradient ------------------------------------------------------------------------------------------------------------------
+// the plan of the first family from `first` on that takes the shape
+static WgradPlan wgrad_plan(const WgradShape& s, int first = WGRAD_STEM) {
+    WgradPlan p = {};
+    if (first <= WGRAD_STEM && hdy_wgrad_stem_plan(s, &p)) return p;              // patch-resident 6x6/s2 stem
+    if (first <= WGRAD_3X3 && hdy_wgrad3x3_plan(s, &p)) return p;                 // patch-resident 3x3 / stride 1
+    if (first <= WGRAD_DEEP && hdy_wgrad_deep_plan(s, &p)) return p;              // deep-pipelined 256 x 256 tiles (multi-tap, C % 64 == 0, K >= 192)
+    hdy_wgrad_generic_plan(s, &p);                                                // generic kernel: takes everything
+    return p;
+}
+
+static int wgrad_launch_planned(const WgradArgs& a, const WgradPlan& p, hipStream_t st) {
+    switch (p.family) {
+        case WGRAD_STEM: return hdy_wgrad_stem_launch(a, p, st);
+        case WGRAD_3X3: return hdy_wgrad3x3_launch(a, p, st);
+        case WGRAD_DEEP: return hdy_wgrad_deep_launch(a, p, st);
+        default: return hdy_wgrad_generic_launch(a, p, st);
+    }
+}
+
+// The kernels' view of the layer: the tap window over x, the stem as six row taps over the 24 pseudo channels of its padded 4-channel image.
+static WgradArgs wgrad_args(const WgradShape& s, const void* x, int ldx, const void* dy, int lddy, void* workspace) {
+    WgradArgs a = {};
+    a.x = x; a.dy = dy; a.partial = (float*)workspace;
+    a.N = s.N; a.K = s.K; a.lddy = lddy; a.Ho = s.Ho; a.Wo = s.Wo;
+    if (s.stem) {
+        a.Hin = s.H + 2 * s.pad; a.Win = s.W + 2 * s.pad; a.C = 24; a.ldx = 4; a.span_pixels = 1;
+        a.ih_mul = a.iw_mul = 2; a.dh0 = a.dw0 = 0; a.TH = 6; a.TW = 1;
+    } else {
+        a.Hin = s.H; a.Win = s.W; a.C = s.C; a.ldx = ldx;
+        a.ih_mul = a.iw_mul = s.stride; a.dh0 = a.dw0 = -s.pad; a.TH = s.R; a.TW = s.S;
+    }
+    return a;
+}
+
+// What every weight-gradient kernel needs of a call, checked once; then the planned family (one that declines hands the launch to the
+// families after it) and the reduction of its slabs.  a.y set (the stem's fused BatchNorm backward): the caller has asked the stem's plan.
+static int wgrad_run(const WgradShape& s, const WgradArgs& a, float* grad_a, int K_a, float* grad_b, int K_b, int accumulate, size_t ws_bytes, hipStream_t st) {
+    const int VE = s.dtype == HDY_BF16 ? 8 : 4;
+    HDY_ARG(grad_a && K_a > 0 && K_a + K_b <= a.K && K_b >= 0 && (K_b == 0) == (grad_b == nullptr), "wgrad: bad gradient split");
+    HDY_ARG(a.x && a.dy && a.partial, "wgrad: null pointer");
+    HDY_ARG(a.C % VE == 0 && a.K % VE == 0, "wgrad: C=%d and K=%d must be multiples of %d", a.C, a.K, VE);
+    HDY_ARG(a.ldx % (a.span_pixels ? 4 : VE) == 0 && a.lddy % VE == 0 && (a.span_pixels || a.ldx >= a.C) && a.lddy >= a.K, "wgrad: bad pitches ldx=%d lddy=%d", a.ldx, a.lddy);
+    HDY_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.dy & 15) == 0, "wgrad: x/dy must be 16-byte aligned");
+    HDY_ARG((long long)a.N * a.Hin * a.Win < (1LL << 31) && (long long)a.N * a.Ho * a.Wo < (1LL << 31), "wgrad: too many pixels");
+    HDY_ARG(ws_bytes >= hdy_conv_wgrad_workspace_bytes(s.N, s.H, s.W, s.C, s.K, s.R, s.S, s.stride, s.pad, s.dtype, s.stem), "wgrad: workspace too small");
+    WgradPlan p;
+    int rc;
+    for (int first = WGRAD_STEM;; first = p.family + 1) {
+        p = wgrad_plan(s, first);
+        rc = wgrad_launch_planned(a, p, st);
+        if (rc != HDY_CONV_DECLINE) break;
+    }
+    if (rc) return rc;
+    return hdy_wgrad_reduce(a.partial, p.splits, s.K, wgrad_cols(s), s.stem, s.C, s.R, s.S, grad_a, K_a, grad_b, K_b, accumulate, st);
+}
+
+extern "C" {
+
+// The maximum over the plans of ALL families that take the shape, not the first one's: a call that does not fit its planned kernel (the
+// deep-pipelined kernel's offset bound depends on the caller's pitches) falls to a later family and must find room for that one's slabs.
+size_t hdy_conv_wgrad_workspace_bytes(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype, int stem) {
+    const WgradShape s = wgrad_shape(N, H, W, C, K, R, S, stride, pad, dtype, stem);
+    int splits = 0;
+    for (int first = WGRAD_STEM; first <= WGRAD_GENERIC;) {
+        const WgradPlan p = wgrad_plan(s, first);
+        if (p.splits > splits) splits = p.splits;
+        first = p.family + 1;
+    }
+    return (size_t)splits * K * wgrad_cols(s) * sizeof(float);
+}
+
+// grad_a [K_a][C][R][S] (and optionally grad_b [K_b][C][R][S], the lower rows of a stacked weight) (+)= dW.
+int hdy_conv_wgrad(const void* x, int ldx, const void* dy, int lddy, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
+                   float* grad_a, int K_a, float* grad_b, int K_b, int accumulate, void* workspace, size_t ws_bytes, int dtype, int stem,
+                   void* stream) {
+    HDY_ARG(dtype == HDY_BF16 || dtype == HDY_F32, "conv_wgrad: unknown dtype %d", dtype);
+    const WgradShape s = wgrad_shape(N, H, W, C, K, R, S, stride, pad, dtype, stem != 0);
+    HDY_ARG(s.Ho > 0 && s.Wo > 0, "conv_wgrad: empty dy");
+    HDY_ARG(!stem || (C == 3 && R == 6 && S == 6 && stride == 2 && pad == 2 && ldx == 4), "conv_wgrad: stem expects C=3 k=6 s=2 p=2 on a 4-channel padded image");
+    return wgrad_run(s, wgrad_args(s, x, ldx, dy, lddy, workspace), grad_a, K_a, grad_b, K_b, accumulate, ws_bytes, (hipStream_t)stream);
+}
+
+// The stem's weight gradient with the BatchNorm / SiLU backward of its unit applied while the tile is staged (conv_wgrad.hip,
+// wgrad_stem_kernel<.., true>): dz = gradient of the unit's output, y = its raw conv output, c1 / c2 from the statistics pass
+// (hdy_bn_act_bwd with dy == NULL).  The stem has no data gradient, so dy is never materialised.  bf16, K in {16, 32, 64}: the stem
+// family's plan, launched with the fused operands set.
+int hdy_conv_wgrad_stem_fused_ok(int N, int H, int W, int K) {
+    WgradPlan p;
+    return (K == 16 || K == 32 || K == 64) && hdy_wgrad_stem_plan(wgrad_shape(N, H, W, 3, K, 6, 6, 2, 2, HDY_BF16, 1), &p);
+}
+
+int hdy_conv_wgrad_stem_fused(const void* x, const void* dz, int lddz, const void* y, int ldy, const float* scale, const float* shift, const float* mean,
+                              const float* invstd, const float* c1, const float* c2, int N, int H, int W, int K, float* grad_a, int K_a, float* grad_b,
+                              int K_b, int accumulate, void* workspace, size_t ws_bytes, void* stream) {
+    HDY_ARG(y, "conv_wgrad_stem_fused: null pointer");
+    HDY_ARG(hdy_conv_wgrad_stem_fused_ok(N, H, W, K), "conv_wgrad_stem_fused: shape not served (K in {16, 32, 64}, output a multiple of 16 x 32)");
+    const WgradShape s = wgrad_shape(N, H, W, 3, K, 6, 6, 2, 2, HDY_BF16, 1);
+    WgradArgs a = wgrad_args(s, x, 4, dz, lddz, workspace);
+    a.y = y; a.ldy = ldy; a.bn_scale = scale; a.bn_shift = shift; a.bn_mean = mean; a.bn_invstd = invstd; a.bn_c1 = c1; a.bn_c2 = c2;
+    return wgrad_run(s, a, grad_a, K_a, grad_b, K_b, accumulate, ws_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

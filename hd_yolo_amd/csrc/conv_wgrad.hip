@@ -553,81 +553,76 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const hdy_pack_desc* __
 
 }  // namespace
 
-static inline void wgrad_tile(int K, int Q, long long P, int dtype, int* sd, int* sx) {
-    const int TK = dtype == HDY_BF16 ? 64 : 32;
+// The generic kernel takes everything.  Its tile (HDY_WGRAD_TILE) and pixel splits (HDY_WGRAD_BLOCKS):
+bool hdy_wgrad_generic_plan(const WgradShape& s, WgradPlan* p) {
+    const int TK = s.dtype == HDY_BF16 ? 64 : 32;
+    const int K = s.K, Q = wgrad_cols(s);
+    const long long P = wgrad_pixels(s);
     // measurement switch (profiles/r05_wgrad_splits_ab.txt): 64 = 64 x 64 blocks everywhere, N > 64 = only for layers with at most N pixels
     const int opt = hdy_opt(HDY_OPT_WGRAD_TILE);
     const bool small = opt == 64 || (opt > 64 && P <= opt);
-    *sd = (K > TK && !small) ? 2 : 1;
-    *sx = (Q > TK && !small) ? 2 : 1;
-}
-
-int hdy_wgrad_plan(int K, int Q, long long P, int dtype, int* splits, int* pix_per_split) {
-    const int TK = dtype == HDY_BF16 ? 64 : 32;
-    int sd, sx;
-    wgrad_tile(K, Q, P, dtype, &sd, &sx);
-    const int tiles = cdiv(K, TK * sd) * cdiv(Q, TK * sx);
+    const int sd = (K > TK && !small) ? 2 : 1, sx = (Q > TK && !small) ? 2 : 1;
+    *p = WgradPlan{};
+    p->family = WGRAD_GENERIC;
+    p->variant = (s.dtype == HDY_BF16 ? 0 : 4) + (sd == 2 ? 2 : 0) + (sx == 2 ? 1 : 0);
+    p->ktiles = cdiv(K, TK * sd);
+    p->qtiles = cdiv(Q, TK * sx);
+    const int tiles = p->ktiles * p->qtiles;
     const int target = hdy_opt(HDY_OPT_WGRAD_BLOCKS);     // = resident workgroups (2 per CU): one wave of blocks, half the slab traffic of 1024
-    int s = cdiv(target, tiles);
-    if (s > 512) s = 512;
+    int n = cdiv(target, tiles);
+    if (n > 512) n = 512;
     const int maxs = cdiv(P, 256);
-    if (s > maxs) s = maxs;
-    if (s < 1) s = 1;
-    int pps = round_up(cdiv(P, s), PB);
-    s = cdiv(P, pps);
-    *splits = s;
-    *pix_per_split = pps;
-    return HDY_OK;
+    if (n > maxs) n = maxs;
+    if (n < 1) n = 1;
+    p->pix_per_split = round_up(cdiv(P, n), PB);
+    p->splits = cdiv(P, p->pix_per_split);
+    p->grid = p->splits * tiles;
+    return true;
 }
 
 template <typename T>
-static void wgrad_dispatch(const WgradArgs& a, int sd, int sx, int grid, hipStream_t st) {
-    hdy_note_dispatch("wgrad_generic");
-    if (sd == 2 && sx == 2) hipLaunchKernelGGL((wgrad_kernel<T, 2, 2>), dim3(grid), dim3(256), 0, st, a);
-    else if (sd == 2) hipLaunchKernelGGL((wgrad_kernel<T, 2, 1>), dim3(grid), dim3(256), 0, st, a);
-    else if (sx == 2) hipLaunchKernelGGL((wgrad_kernel<T, 1, 2>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((wgrad_kernel<T, 1, 1>), dim3(grid), dim3(256), 0, st, a);
+static void wgrad_dispatch(const WgradArgs& a, const WgradPlan& p, hipStream_t st) {
+    const bool sd2 = p.variant & 2, sx2 = p.variant & 1;
+    if (sd2 && sx2) hipLaunchKernelGGL((wgrad_kernel<T, 2, 2>), dim3(p.grid), dim3(256), 0, st, a);
+    else if (sd2) hipLaunchKernelGGL((wgrad_kernel<T, 2, 1>), dim3(p.grid), dim3(256), 0, st, a);
+    else if (sx2) hipLaunchKernelGGL((wgrad_kernel<T, 1, 2>), dim3(p.grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((wgrad_kernel<T, 1, 1>), dim3(p.grid), dim3(256), 0, st, a);
 }
 
-int hdy_wgrad_launch(WgradArgs a, int dtype, hipStream_t st) {
-    const int VE = dtype == HDY_BF16 ? 8 : 4, TK = dtype == HDY_BF16 ? 64 : 32;
-    HDY_ARG(a.x && a.dy && a.partial, "wgrad: null pointer");
-    HDY_ARG(a.C % VE == 0 && a.K % VE == 0, "wgrad: C=%d and K=%d must be multiples of %d", a.C, a.K, VE);
-    HDY_ARG(a.ldx % (a.span_pixels ? 4 : VE) == 0 && a.lddy % VE == 0 && (a.span_pixels || a.ldx >= a.C) && a.lddy >= a.K, "wgrad: bad pitches ldx=%d lddy=%d", a.ldx, a.lddy);
-    HDY_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.dy & 15) == 0, "wgrad: x/dy must be 16-byte aligned");
-    HDY_ARG((long long)a.N * a.Hin * a.Win < (1LL << 31) && (long long)a.N * a.Ho * a.Wo < (1LL << 31), "wgrad: too many pixels");
+int hdy_wgrad_generic_launch(const WgradArgs& args, const WgradPlan& p, hipStream_t st) {
+    WgradArgs a = args;
     a.Q = a.TH * a.TW * a.C;
     a.P = a.N * a.Ho * a.Wo;
-    int sd, sx;
-    wgrad_tile(a.K, a.Q, a.P, dtype, &sd, &sx);
-    a.ktiles = cdiv(a.K, TK * sd);
-    a.qtiles = cdiv(a.Q, TK * sx);
-    HDY_ARG(a.splits >= 1 && a.pix_per_split % PB == 0 && (long long)a.splits * a.pix_per_split >= a.P, "wgrad: bad split plan");
-    const int grid = a.splits * a.ktiles * a.qtiles;
-    if (dtype == HDY_BF16) wgrad_dispatch<bf16_t>(a, sd, sx, grid, st);
-    else wgrad_dispatch<float>(a, sd, sx, grid, st);
-    HDY_LAUNCH_CHECK("wgrad");
-    return HDY_OK;
+    a.splits = p.splits; a.pix_per_split = p.pix_per_split; a.ktiles = p.ktiles; a.qtiles = p.qtiles;
+    hdy_note_dispatch("wgrad_generic");
+    if (!(p.variant & 4)) wgrad_dispatch<bf16_t>(a, p, st);
+    else wgrad_dispatch<float>(a, p, st);
+    return hdy_launch_status("wgrad");
 }
 
-// Workgroups (= fp32 slabs) of the patch-resident stem weight gradient, 0 = shape not eligible (generic kernel).
-int hdy_wgrad_stem_grid(int N, int Ho, int Wo, int K, int dtype) {
-    const bool disabled = hdy_opt(HDY_OPT_NO_STEM_WGRAD) != 0;
-    if (disabled || dtype != HDY_BF16 || K % 16 != 0 || K > 64 || Ho % stemw::TOH != 0 || Wo % stemw::TOW != 0) return 0;
-    const long long tiles = (long long)N * (Ho / stemw::TOH) * (Wo / stemw::TOW);
-    const int cap = K <= 32 ? 768 : 256;                 // 52 KB of LDS per workgroup at K = 32: three per CU
-    return (int)(tiles < cap ? tiles : cap);
+// Patch-resident stem kernel: bf16, K in {16, 32, 48, 64}, whole 16 x 32 output tiles; one fp32 slab per (persistent) workgroup.
+bool hdy_wgrad_stem_plan(const WgradShape& s, WgradPlan* p) {
+    if (!s.stem || hdy_opt(HDY_OPT_NO_STEM_WGRAD) || s.dtype != HDY_BF16 || s.K % 16 != 0 || s.K > 64 || s.Ho % stemw::TOH != 0 || s.Wo % stemw::TOW != 0)
+        return false;
+    const long long tiles = (long long)s.N * (s.Ho / stemw::TOH) * (s.Wo / stemw::TOW);
+    const int cap = s.K <= 32 ? 768 : 256;               // 52 KB of LDS per workgroup at K = 32: three per CU
+    if (tiles <= 0) return false;
+    *p = WgradPlan{};
+    p->family = WGRAD_STEM;
+    p->variant = s.K / 16;
+    p->grid = p->splits = (int)(tiles < cap ? tiles : cap);
+    return true;
 }
 
-int hdy_wgrad_stem_launch(const WgradArgs& a, int grid, hipStream_t st) {
-    HDY_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.dy & 15) == 0 && a.lddy % 8 == 0 && a.Win % 2 == 0, "wgrad(stem): x/dy alignment");
+int hdy_wgrad_stem_launch(const WgradArgs& a, const WgradPlan& p, hipStream_t st) {
+    HDY_ARG(a.Win % 2 == 0, "wgrad(stem): odd image width");
     const size_t smem = stemw::PATCH_B + 64 + (size_t)stemw::TOH * stemw::TOW * a.K * 2;
-    const int mt = a.K / 16;
+    const int mt = p.variant;
     hdy_note_dispatch(a.y ? "wgrad_stem_fused" : "wgrad_stem");
 #define STEMW_LAUNCH(MT, FU)                                                                                                         \
     {                                                                                                                              \
         (void)hipFuncSetAttribute((const void*)stemw::wgrad_stem_kernel<MT, FU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
-        hipLaunchKernelGGL((stemw::wgrad_stem_kernel<MT, FU>), dim3(grid), dim3(256), smem, st, a);                                \
+        hipLaunchKernelGGL((stemw::wgrad_stem_kernel<MT, FU>), dim3(p.grid), dim3(256), smem, st, a);                              \
     }
     if (a.y) {
         HDY_ARG((mt == 1 || mt == 2 || mt == 4) && a.ldy % 8 == 0 && ((uintptr_t)a.y & 15) == 0 && a.bn_scale && a.bn_shift && a.bn_mean && a.bn_invstd &&
@@ -635,22 +630,24 @@ int hdy_wgrad_stem_launch(const WgradArgs& a, int grid, hipStream_t st) {
         if (mt == 1) STEMW_LAUNCH(1, true) else if (mt == 2) STEMW_LAUNCH(2, true) else STEMW_LAUNCH(4, true)
     } else if (mt == 1) STEMW_LAUNCH(1, false) else if (mt == 2) STEMW_LAUNCH(2, false) else if (mt == 3) STEMW_LAUNCH(3, false) else STEMW_LAUNCH(4, false)
 #undef STEMW_LAUNCH
-    HDY_LAUNCH_CHECK("wgrad(stem)");
-    return HDY_OK;
+    return hdy_launch_status("wgrad(stem)");
 }
 
-// partial points at the first row to reduce; slabs are slab_stride floats apart; K rows of Q are reduced.
-int hdy_wgrad_reduce_launch(const float* partial, int splits, size_t slab_stride, int K, int Q, int mode, int C, int R, int S, float* grad,
-                            int accumulate, hipStream_t st) {
-    const int n = K * Q;
-    const bool vec = n % 4 == 0 && slab_stride % 4 == 0 && ((uintptr_t)partial & 15) == 0 && (!(mode == 0 && R == 1 && S == 1) || ((uintptr_t)grad & 15) == 0);
-    hdy_note_dispatch(vec ? "wgrad_reduce" : "wgrad_reduce_scalar");
-    if (vec)
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(1024), 0, st, partial, splits, slab_stride, K, Q, mode, C, R, S, grad, accumulate);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3(cdiv(n, 64)), dim3(1024), 0, st, partial, splits, slab_stride, K, Q, mode, C, R, S, grad,
-                           accumulate);
-    HDY_LAUNCH_CHECK("wgrad_reduce");
+int hdy_wgrad_reduce(const float* partial, int splits, int K, int Q, int mode, int C, int R, int S, float* grad_a, int K_a, float* grad_b, int K_b,
+                     int accumulate, hipStream_t st) {
+    const size_t slab_stride = (size_t)K * Q;
+    for (int t = 0; t < (K_b ? 2 : 1); ++t) {             // rows K_a.. of every slab belong to the second tensor
+        const float* src = t ? partial + (size_t)K_a * Q : partial;
+        float* grad = t ? grad_b : grad_a;
+        const int rows = t ? K_b : K_a, n = rows * Q;
+        const bool vec = n % 4 == 0 && slab_stride % 4 == 0 && ((uintptr_t)src & 15) == 0 && (!(mode == 0 && R == 1 && S == 1) || ((uintptr_t)grad & 15) == 0);
+        hdy_note_dispatch(vec ? "wgrad_reduce" : "wgrad_reduce_scalar");
+        if (vec)
+            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(1024), 0, st, src, splits, slab_stride, rows, Q, mode, C, R, S, grad, accumulate);
+        else
+            hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3(cdiv(n, 64)), dim3(1024), 0, st, src, splits, slab_stride, rows, Q, mode, C, R, S, grad, accumulate);
+        HDY_LAUNCH_CHECK("wgrad_reduce");
+    }
     return HDY_OK;
 }
 

@@ -246,66 +246,52 @@ __global__ __launch_bounds__(768) void wgrad3x3_kernel(const W3Args p) {
             }
 }
 
-struct W3Plan { int KB, CB, TOH, TOW, tiles_h, tiles_w, nkb, ncb, nsplit; };
+}  // namespace
 
-// tile shape (output pixels): whole image rows when they are short (W <= 40), 16x16 blocks when W divides by 16, else 8x32
-bool w3_plan(int N, int Ho, int Wo, int C, int K, int stride, W3Plan* pl) {
-    const bool off = hdy_opt(HDY_OPT_NO_WGRAD3X3) != 0;
+// 3x3 / stride 1 / pad 1, bf16.  Tile shape (output pixels): whole image rows when they are short (W <= 40), 16x16 blocks when W divides by 16, else 8x32
+bool hdy_wgrad3x3_plan(const WgradShape& s, WgradPlan* pl) {
+    const int C = s.C, K = s.K, Ho = s.Ho, Wo = s.Wo;
     // Stride 1 only (57 vs 82, 57 vs 75, 67 vs 95, 84 vs 168 us against the generic kernel on yolov5s B=64).  A stride-2 plan was built and measured in
     // round 2 and is gone from the library: its patch is 4x the output tile, 45 KB of LDS-DMA for two MFMA steps, load bound — 101 vs 100, 86 vs 75,
     // 177 vs 180, 166 vs 172, 166 vs 152, 238 vs 233 us.
-    if (off || C % 32 || K % 32 || stride != 1) return false;
-    pl->KB = K % 64 == 0 ? 64 : 32;
-    pl->CB = C % 64 == 0 ? 64 : 32;
+    if (s.stem || s.R != 3 || s.S != 3 || s.pad != 1 || s.stride != 1 || s.dtype != HDY_BF16 || hdy_opt(HDY_OPT_NO_WGRAD3X3) || C % 32 || K % 32) return false;
+    const int KB = K % 64 == 0 ? 64 : 32, CB = C % 64 == 0 ? 64 : 32;
+    *pl = WgradPlan{};
+    pl->family = WGRAD_3X3;
+    pl->variant = (KB == 64 ? 2 : 0) + (CB == 64 ? 1 : 0);
+    pl->ktiles = K / KB;
+    pl->qtiles = C / CB;
+    const int blocks = pl->ktiles * pl->qtiles;
     // several 32-wide blocks per split (yolov5m's 96 x 96 = 3 x 3 of them) do too little MFMA work per staged tile: 83 us against 70 us on the
     // generic kernel at 96x96 @80x80, B=32; a single 32 x 32 block (yolov5s' 32->32 @160x160) is 84 against 168 us
-    if ((pl->KB == 32 || pl->CB == 32) && (K / pl->KB) * (C / pl->CB) > 1) return false;
+    if ((KB == 32 || CB == 32) && blocks > 1) return false;
     if (Wo <= 40) { pl->TOW = Wo; pl->TOH = W3_MAXTP / Wo; }
     else if (Wo % 16 == 0) { pl->TOW = 16; pl->TOH = 16; }
     else { pl->TOW = 32; pl->TOH = 8; }
     if (pl->TOH > Ho) pl->TOH = Ho;
     if (pl->TOH < 1) return false;
     // fewest rows per tile that need the same number of tiles: no more padding than necessary
-    const int th = cdiv(Ho, pl->TOH);
-    pl->TOH = cdiv(Ho, th);
-    const int PH = stride * pl->TOH + 3 - stride, PW = stride * pl->TOW + 3 - stride;
-    if (PH * PW > W3_MAXPP || pl->TOH * pl->TOW > W3_MAXTP) return false;
-    pl->tiles_h = th;
+    pl->tiles_h = cdiv(Ho, pl->TOH);
+    pl->TOH = cdiv(Ho, pl->tiles_h);
+    if ((pl->TOH + 2) * (pl->TOW + 2) > W3_MAXPP || pl->TOH * pl->TOW > W3_MAXTP) return false;
     pl->tiles_w = cdiv(Wo, pl->TOW);
-    pl->nkb = K / pl->KB;
-    pl->ncb = C / pl->CB;
-    const long long tiles = (long long)N * pl->tiles_h * pl->tiles_w;
-    const int blocks = pl->nkb * pl->ncb;
+    const long long tiles = (long long)s.N * pl->tiles_h * pl->tiles_w;
     long long ns = 256 / blocks;                                       // one resident workgroup per CU (double-buffered LDS)
     const long long cap = (48LL << 20) / ((long long)K * 9 * C * 4);   // slabs within 48 MB
     if (ns > cap) ns = cap;
     if (ns > tiles) ns = tiles;
     if (ns < 1) ns = 1;
-    pl->nsplit = (int)ns;
+    pl->splits = (int)ns;
+    pl->grid = blocks * pl->splits;
     return true;
 }
 
-}  // namespace
-
-// 0 = shape not handled by the patch-resident kernel
-size_t hdy_wgrad3x3_workspace_bytes(int N, int Ho, int Wo, int C, int K, int stride, int dtype) {
-    W3Plan pl;
-    if (dtype != HDY_BF16 || !w3_plan(N, Ho, Wo, C, K, stride, &pl)) return 0;
-    return (size_t)pl.nsplit * K * 9 * C * sizeof(float);
-}
-
-// returns 1 when it launched (rc set), 0 when the generic kernel must run; *splits = slabs written
-int hdy_wgrad3x3_try(const void* x, int ldx, const void* dy, int lddy, int N, int Hin, int Win, int Ho, int Wo, int C, int K, int stride, float* partial,
-                     int dtype, hipStream_t st, int* splits, int* rc) {
-    W3Plan pl;
-    if (dtype != HDY_BF16 || !w3_plan(N, Ho, Wo, C, K, stride, &pl)) return 0;
-    if ((((uintptr_t)x | (uintptr_t)dy) & 15) || ldx % 8 || lddy % 8) return 0;
+int hdy_wgrad3x3_launch(const WgradArgs& w, const WgradPlan& pl, hipStream_t st) {
     W3Args a = {};
-    a.x = x; a.ldx = ldx; a.dy = dy; a.lddy = lddy; a.partial = partial;
-    a.N = N; a.H = Ho; a.W = Wo; a.C = C; a.K = K; a.Hin = Hin; a.Win = Win; a.S = stride;
+    a.x = w.x; a.ldx = w.ldx; a.dy = w.dy; a.lddy = w.lddy; a.partial = w.partial;
+    a.N = w.N; a.H = w.Ho; a.W = w.Wo; a.C = w.C; a.K = w.K; a.Hin = w.Hin; a.Win = w.Win; a.S = w.ih_mul;
     a.TOH = pl.TOH; a.TOW = pl.TOW; a.tiles_h = pl.tiles_h; a.tiles_w = pl.tiles_w;
-    a.nkb = pl.nkb; a.ncb = pl.ncb; a.nsplit = pl.nsplit;
-    const int grid = pl.nkb * pl.ncb * pl.nsplit;
+    a.nkb = pl.ktiles; a.ncb = pl.qtiles; a.nsplit = pl.splits;
     constexpr int smem = 2 * W3_BUF;
     static PerDeviceOnce attr_once;           // first launch of this instance on any thread
     attr_once.run([&] {
@@ -315,17 +301,9 @@ int hdy_wgrad3x3_try(const void* x, int ldx, const void* dy, int lddy, int N, in
         (void)hipFuncSetAttribute((const void*)wgrad3x3_kernel<32, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     });
     hdy_note_dispatch("wgrad3x3");
-    if (pl.KB == 64 && pl.CB == 64) hipLaunchKernelGGL((wgrad3x3_kernel<64, 64>), dim3(grid), dim3(768), smem, st, a);
-    else if (pl.KB == 64) hipLaunchKernelGGL((wgrad3x3_kernel<64, 32>), dim3(grid), dim3(768), smem, st, a);
-    else if (pl.CB == 64) hipLaunchKernelGGL((wgrad3x3_kernel<32, 64>), dim3(grid), dim3(768), smem, st, a);
-    else hipLaunchKernelGGL((wgrad3x3_kernel<32, 32>), dim3(grid), dim3(768), smem, st, a);
-    *splits = pl.nsplit;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        hdy_set_error("wgrad3x3: launch failed: %s", hipGetErrorString(e));
-        *rc = (int)e;
-    } else {
-        *rc = HDY_OK;
-    }
-    return 1;
+    if (pl.variant == 3) hipLaunchKernelGGL((wgrad3x3_kernel<64, 64>), dim3(pl.grid), dim3(768), smem, st, a);
+    else if (pl.variant == 2) hipLaunchKernelGGL((wgrad3x3_kernel<64, 32>), dim3(pl.grid), dim3(768), smem, st, a);
+    else if (pl.variant == 1) hipLaunchKernelGGL((wgrad3x3_kernel<32, 64>), dim3(pl.grid), dim3(768), smem, st, a);
+    else hipLaunchKernelGGL((wgrad3x3_kernel<32, 32>), dim3(pl.grid), dim3(768), smem, st, a);
+    return hdy_launch_status("wgrad3x3");
 }

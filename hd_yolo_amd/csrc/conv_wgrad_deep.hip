@@ -261,77 +261,61 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_deep_kernel(const WDArgs p) {
             }
 }
 
-// pixel splits of the deep kernel: one workgroup per CU over (tiles x splits)
-inline void deep_plan(int K, int Q, long long P, int* ktiles, int* qtiles, int* splits, int* pps) {
-    *ktiles = cdiv(K, 256);
-    *qtiles = cdiv(Q, 256);
-    const int tiles = *ktiles * *qtiles;
-    int s = 256 / tiles;
-    if (s < 1) s = 1;
-    const int maxs = cdiv(P, 512);                 // at least 8 stages per workgroup
-    if (s > maxs) s = maxs;
-    if (s < 1) s = 1;
-    *pps = round_up(cdiv(P, s), 64);
-    *splits = cdiv(P, *pps);
-}
-
-bool deep_ok(int N, int Hin, int Win, int Ho, int Wo, int C, int K, int R, int S, int stride, int ldx, int lddy, int dtype) {
-    if (hdy_opt(HDY_OPT_NO_WGRAD_DEEP) || dtype != HDY_BF16) return false;
-    // K: whole 64-channel sub-tiles (the loader's d_col[] test and the slab store's k < K test cover a last, partly filled 256-row tile); round 6: 192 and
-    // up (yolov5m's 192-wide layers: K = 192 fills three quarters of one tile), before that K % 128 == 0 && K >= 256
-    const int kmin = hdy_opt(HDY_OPT_WGRAD_DEEP_KMIN);
-    if (C % 64 != 0 || K % 64 != 0 || K < kmin || ldx % 8 != 0 || lddy % 8 != 0) return false;
-    // measured on yolov5s (B = 64): the multi-tap layers 158 -> 85 us (256x512 3x3/s2 @40x40), 158 -> 82 (128x256 @80x80), 96 -> 58 (256x256 s2); the
-    // 1x1 layers at 20x20 / 40x40 lose (20 -> 28 us, 35 -> 39 us: a 256 x 256 tile leaves them 4-8 tiles, i.e. 32-64 pixel splits of 7-25 stages,
-    // and twice the slab bytes): multi-tap layers only
-    if (R * S == 1) return false;
-    const long long P = (long long)N * Ho * Wo;
-    if (P < 8192) return false;                                         // too few pixels to stream
-    if ((long long)N * Hin * Win * ldx * 2 >= (1LL << 31) - (1LL << 24)) return false;    // 31-bit x offsets (bit 31 = out of range)
-    if (P * lddy * 2 >= (1LL << 31)) return false;
-    return true;
+// 31-bit x / dy offsets (bit 31 = out of range) with these pitches
+inline bool deep_offsets_fit(long long in_pixels, int ldx, long long P, int lddy) {
+    return in_pixels * ldx * 2 < (1LL << 31) - (1LL << 24) && P * lddy * 2 < (1LL << 31);
 }
 
 }  // namespace
 
-// workspace bytes of the deep weight gradient for this shape; 0: not its shape (the caller's generic path applies)
-size_t hdy_wgrad_deep_workspace_bytes(int N, int Hin, int Win, int Ho, int Wo, int C, int K, int R, int S, int stride, int dtype) {
-    if (!deep_ok(N, Hin, Win, Ho, Wo, C, K, R, S, stride, 8, 8, dtype)) return 0;
-    int kt, qt, sp, pps;
-    deep_plan(K, R * S * C, (long long)N * Ho * Wo, &kt, &qt, &sp, &pps);
-    return (size_t)sp * K * R * S * C * sizeof(float);
+bool hdy_wgrad_deep_plan(const WgradShape& s, WgradPlan* p) {
+    if (s.stem || hdy_opt(HDY_OPT_NO_WGRAD_DEEP) || s.dtype != HDY_BF16) return false;
+    // K: whole 64-channel sub-tiles (the loader's d_col[] test and the slab store's k < K test cover a last, partly filled 256-row tile); round 6: 192 and
+    // up (yolov5m's 192-wide layers: K = 192 fills three quarters of one tile), before that K % 128 == 0 && K >= 256
+    if (s.C % 64 != 0 || s.K % 64 != 0 || s.K < hdy_opt(HDY_OPT_WGRAD_DEEP_KMIN)) return false;
+    // measured on yolov5s (B = 64): the multi-tap layers 158 -> 85 us (256x512 3x3/s2 @40x40), 158 -> 82 (128x256 @80x80), 96 -> 58 (256x256 s2); the
+    // 1x1 layers at 20x20 / 40x40 lose (20 -> 28 us, 35 -> 39 us: a 256 x 256 tile leaves them 4-8 tiles, i.e. 32-64 pixel splits of 7-25 stages,
+    // and twice the slab bytes): multi-tap layers only
+    if (s.R * s.S == 1) return false;
+    const long long P = wgrad_pixels(s);
+    if (P < 8192) return false;                                         // too few pixels to stream
+    // the pitch-free form of the offset bound (8 elements per pixel); the launch checks it with the caller's pitches and may decline
+    if (!deep_offsets_fit((long long)s.N * s.H * s.W, 8, P, 8)) return false;
+    *p = WgradPlan{};
+    p->family = WGRAD_DEEP;
+    p->ktiles = cdiv(s.K, 256);
+    p->qtiles = cdiv(wgrad_cols(s), 256);
+    // pixel splits: one workgroup per CU over (tiles x splits)
+    const int tiles = p->ktiles * p->qtiles;
+    int n = 256 / tiles;
+    if (n < 1) n = 1;
+    const int maxs = cdiv(P, 512);                 // at least 8 stages per workgroup
+    if (n > maxs) n = maxs;
+    if (n < 1) n = 1;
+    p->pix_per_split = round_up(cdiv(P, n), 64);
+    p->splits = cdiv(P, p->pix_per_split);
+    p->grid = tiles * p->splits;
+    return true;
 }
 
-// launches the deep kernel when the shape is its; *splits = slabs written ([split][K][Q] in `partial`)
-int hdy_wgrad_deep_try(const void* x, int ldx, const void* dy, int lddy, int N, int Hin, int Win, int Ho, int Wo, int C, int K, int R, int S, int stride,
-                       int pad, float* partial, int dtype, hipStream_t st, int* splits, int* rc) {
-    if (!deep_ok(N, Hin, Win, Ho, Wo, C, K, R, S, stride, ldx, lddy, dtype)) return 0;
-    if ((((uintptr_t)x | (uintptr_t)dy) & 15) != 0) return 0;
+int hdy_wgrad_deep_launch(const WgradArgs& w, const WgradPlan& p, hipStream_t st) {
+    if (!deep_offsets_fit((long long)w.N * w.Hin * w.Win, w.ldx, (long long)w.N * w.Ho * w.Wo, w.lddy)) return HDY_CONV_DECLINE;
     WDArgs a = {};
-    a.x = x; a.dy = dy; a.partial = partial;
-    a.N = N; a.Hin = Hin; a.Win = Win; a.C = C; a.ldx = ldx; a.Ho = Ho; a.Wo = Wo; a.K = K; a.lddy = lddy;
-    a.stride = stride; a.dh0 = -pad; a.dw0 = -pad; a.TW = S;
-    a.Q = R * S * C;
-    a.P = N * Ho * Wo;
-    deep_plan(K, a.Q, a.P, &a.ktiles, &a.qtiles, &a.splits, &a.pix_per_split);
-    hdy_magic((unsigned)(Ho * Wo), &a.mg_howo, &a.sh_howo);
-    hdy_magic((unsigned)Wo, &a.mg_wo, &a.sh_wo);
-    hdy_magic((unsigned)C, &a.mg_c, &a.sh_c);
-    hdy_magic((unsigned)S, &a.mg_tw, &a.sh_tw);
-    const int grid = a.ktiles * a.qtiles * a.splits;
+    a.x = w.x; a.dy = w.dy; a.partial = w.partial;
+    a.N = w.N; a.Hin = w.Hin; a.Win = w.Win; a.C = w.C; a.ldx = w.ldx; a.Ho = w.Ho; a.Wo = w.Wo; a.K = w.K; a.lddy = w.lddy;
+    a.stride = w.ih_mul; a.dh0 = w.dh0; a.dw0 = w.dw0; a.TW = w.TW;
+    a.Q = w.TH * w.TW * w.C;
+    a.P = w.N * w.Ho * w.Wo;
+    a.ktiles = p.ktiles; a.qtiles = p.qtiles; a.splits = p.splits; a.pix_per_split = p.pix_per_split;
+    hdy_magic((unsigned)(w.Ho * w.Wo), &a.mg_howo, &a.sh_howo);
+    hdy_magic((unsigned)w.Wo, &a.mg_wo, &a.sh_wo);
+    hdy_magic((unsigned)w.C, &a.mg_c, &a.sh_c);
+    hdy_magic((unsigned)w.TW, &a.mg_tw, &a.sh_tw);
     static PerDeviceOnce attr_once;
     attr_once.run([&] {
         (void)hipFuncSetAttribute((const void*)wgrad_deep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RING);
     });
     hdy_note_dispatch("wgrad_deep");
-    hipLaunchKernelGGL(wgrad_deep_kernel, dim3(grid), dim3(NTHR), RING, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        hdy_set_error("wgrad_deep: launch failed: %s", hipGetErrorString(e));
-        *rc = (int)e;
-        return 1;
-    }
-    *splits = a.splits;
-    *rc = HDY_OK;
-    return 1;
+    hipLaunchKernelGGL(wgrad_deep_kernel, dim3(p.grid), dim3(NTHR), RING, st, a);
+    return hdy_launch_status("wgrad_deep");
 }

@@ -177,15 +177,48 @@ struct WgradArgs {
     const float *bn_scale, *bn_shift, *bn_mean, *bn_invstd, *bn_c1, *bn_c2;
 };
 
-int hdy_wgrad_stem_grid(int N, int Ho, int Wo, int K, int dtype);
-int hdy_wgrad_stem_launch(const WgradArgs& a, int grid, hipStream_t st);
-int hdy_wgrad_launch(WgradArgs a, int dtype, hipStream_t st);
-int hdy_wgrad_plan(int K, int Q, long long P, int dtype, int* splits, int* pix_per_split);
-size_t hdy_wgrad3x3_workspace_bytes(int N, int Ho, int Wo, int C, int K, int stride, int dtype);
-int hdy_wgrad3x3_try(const void* x, int ldx, const void* dy, int lddy, int N, int Hin, int Win, int Ho, int Wo, int C, int K, int stride, float* partial,
-                     int dtype, hipStream_t st, int* splits, int* rc);
-size_t hdy_wgrad_deep_workspace_bytes(int N, int Hin, int Win, int Ho, int Wo, int C, int K, int R, int S, int stride, int dtype);
-int hdy_wgrad_deep_try(const void* x, int ldx, const void* dy, int lddy, int N, int Hin, int Win, int Ho, int Wo, int C, int K, int R, int S, int stride,
-                       int pad, float* partial, int dtype, hipStream_t st, int* splits, int* rc);
+// ---- weight-gradient kernel selection (same scheme as the forward side: shape -> plan in one walk, conv_dispatch.hip) ------------------
+// The layer as hdy_conv_wgrad / hdy_conv_wgrad_workspace_bytes are called with it.
+struct WgradShape {
+    int N, H, W;          // input pixel grid (stem: the image, without its padding)
+    int Ho, Wo;           // dy pixels per image
+    int C, K, R, S, stride, pad, dtype;
+    int stem;             // the 6x6 / stride 2 / pad 2 stem on its 4-channel padded image (C == 3)
+};
+inline WgradShape wgrad_shape(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype, int stem) {
+    return WgradShape{N, H, W, conv_out_dim(H, R, stride, pad), conv_out_dim(W, S, stride, pad), C, K, R, S, stride, pad, dtype, stem};
+}
+inline long long wgrad_pixels(const WgradShape& s) { return (long long)s.N * s.Ho * s.Wo; }
+inline int wgrad_cols(const WgradShape& s) { return s.R * s.S * (s.stem ? 4 : s.C); }      // Q: columns of a slab [K][Q]
+
+// The order of this list is the order the families are asked in (wgrad_plan, conv_dispatch.hip); the generic kernel takes everything.
+enum WgradFamily { WGRAD_STEM, WGRAD_3X3, WGRAD_DEEP, WGRAD_GENERIC };
+
+// What one family answers for a shape.  The launch writes `splits` slabs: splits * K * Q floats of workspace.
+struct WgradPlan {
+    int family;           // WgradFamily
+    int variant;          // the family's instance (stem: K / 16; 3x3: 2 * (KB == 64) + (CB == 64); generic: 4 * fp32 + 2 * (SD == 2) + (SX == 2))
+    int grid;             // workgroups
+    int splits;           // slabs written
+    int pix_per_split;    // generic and deep-pipelined kernel
+    int ktiles, qtiles;   // tiles of the K x Q gradient (3x3: its KB x CB blocks)
+    int TOH, TOW, tiles_h, tiles_w;      // 3x3: output tile and tiles per image
+};
+
+// <family>_plan: true = the shape is this family's, *p filled.  Pure host functions of the shape and the option table.
+bool hdy_wgrad_stem_plan(const WgradShape& s, WgradPlan* p);
+bool hdy_wgrad3x3_plan(const WgradShape& s, WgradPlan* p);
+bool hdy_wgrad_deep_plan(const WgradShape& s, WgradPlan* p);
+bool hdy_wgrad_generic_plan(const WgradShape& s, WgradPlan* p);
+
+// <family>_launch: fills the family's argument block from the validated WgradArgs (hdy_conv_wgrad) and the plan and starts the planned
+// instance.  Only the deep-pipelined kernel can answer HDY_CONV_DECLINE (its 31-bit offsets depend on the caller's pitches).
+int hdy_wgrad_stem_launch(const WgradArgs& a, const WgradPlan& p, hipStream_t st);
+int hdy_wgrad3x3_launch(const WgradArgs& a, const WgradPlan& p, hipStream_t st);
+int hdy_wgrad_deep_launch(const WgradArgs& a, const WgradPlan& p, hipStream_t st);
+int hdy_wgrad_generic_launch(const WgradArgs& a, const WgradPlan& p, hipStream_t st);
+// grad_a [K_a][C][R][S] and the optional grad_b [K_b][C][R][S] (rows K_a.. of every slab) (+)= SUM over `splits` slabs [K][Q] (conv_wgrad.hip)
+int hdy_wgrad_reduce(const float* partial, int splits, int K, int Q, int mode, int C, int R, int S, float* grad_a, int K_a, float* grad_b, int K_b,
+                     int accumulate, hipStream_t st);
 int hdy_conv_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st);      // validation + plan + launch (conv_dispatch.hip, next to hdy_conv_stat_slabs)
 int hdy_dgrad3x3s2_try(const ConvArgs& a, int dtype, hipStream_t st, int* rc);
