@@ -14,7 +14,7 @@ wrapped Model is the deployed artefact (yolo.Deploy) —, checkpoints may hold s
 hot path.  Timing brackets exactly what the reference brackets (:98-105: resize + model call), with a device
 synchronisation on both sides because HIP launches are asynchronous.
 
-    python evaluation.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--weights w.pt] [--slide 2048 [--u8] [--min-tissue 0.05] [--score]]
+    python evaluation.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--weights w.pt] [--slide 2048 [--u8] [--min-tissue 0.05] [--score] [--masks --label-map]]
 """
 import argparse
 import os
@@ -151,7 +151,7 @@ def _check_slide(slide):
 
 @torch.no_grad()
 def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=1.0, iou_thres=None, compute_masks=False, min_tissue=0.0,
-                       background=220):
+                       background=220, label_map=False):
     """Whole-slide detection as the reference's ROI protocol composes it: tiles of one amplification are run in batches, each tile's
     detections carry their 'roi' offset, `Detect.merge_outputs` shifts and concatenates them (yolo_head.py:450-462), overlapping
     windows are de-duplicated by one class-agnostic NMS on the MI355X kernel (as Ensemble.merge does, yolo.py:189-199), and
@@ -162,12 +162,22 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     tiles are gathered straight into the network's input buffer (pixel / 255, correctly rounded), and for single-label headers without
     masks the detections stay on the device until the merge — one read of a device cursor per slide, none per batch.
     min_tissue > 0 (8-bit slides only; not in the reference): tiles with fewer than min_tissue * tile * tile pixels that are not
-    background are skipped, a pixel being background when min(R, G, B) >= background.  0.0 keeps every tile and launches nothing."""
-    if _check_slide(slide):
-        return _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background)
+    background are skipped, a pixel being background when min(R, G, B) >= background.  0.0 keeps every tile and launches nothing.
+    label_map=True (with compute_masks, on a model with a mask branch; not in the reference, which pastes per image: val_nuclei.py:169-176):
+    every task with masks gains 'label_map', the int32 (round(H * scale), round(W * scale)) nucleus segmentation of the slide drawn from the
+    final boxes and masks (-1 background, else the row of the returned detection that owns the pixel: slide_label_map), and 'areas'."""
+    u8 = _check_slide(slide)
+    inner = model._model if isinstance(model, Deploy) else model
+    if label_map:
+        headers = getattr(inner, 'headers', None)
+        if not compute_masks:
+            raise ValueError('inference_on_slide: label_map=True needs compute_masks=True (the map is drawn from the masks)')
+        if headers is None or not any(getattr(h, 'nc_masks', 0) > 0 for h in headers.values()):
+            raise ValueError('inference_on_slide: label_map=True needs a model with a mask branch')
+    if u8:
+        return _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map)
     if min_tissue:
         raise ValueError('inference_on_slide: min_tissue applies to 8-bit slides (the background rule is defined on 8-bit RGB values)')
-    inner = model._model if isinstance(model, Deploy) else model
     _, H, W = slide.shape
     rois = slide_rois(H, W, tile, overlap)
     per_task = {}
@@ -181,11 +191,37 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
         for (x0, y0), out in zip(chunk, outputs):
             for task_id, o in out.items():
                 per_task.setdefault(task_id, []).append(dict(o, roi=(float(x0), float(y0))))
+    if label_map:
+        _zero_row_masks(inner.headers, per_task)
     merged = {task_id: inner.headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map)
 
 
-def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres):
+def _zero_row_masks(headers, per_task):
+    """label_map path: a tile without detections carries no 'masks' key and Detect.merge_outputs looks only at the first tile, so such tiles get
+    a zero-row 'masks' before the merge (merge_outputs itself keeps the reference's text)"""
+    for task_id, parts in per_task.items():
+        h = headers[task_id]
+        if getattr(h, 'nc_masks', 0) > 0:
+            for i, o in enumerate(parts):
+                if 'masks' not in o:
+                    parts[i] = dict(o, masks=o['boxes'].new_zeros((0, 1, h.mask_output_size, h.mask_output_size), dtype=torch.float32))
+
+
+@torch.no_grad()
+def slide_label_map(result, size, window=None, threshold=0.5):
+    """One task's result ({'boxes', 'masks', ...} as inference_on_slide(compute_masks=True) returns it, device tensors) -> (label_map, areas):
+    the int32 map of the (H, W) = size canvas, or of its window (x0, y0, w, h) — -1 background, else the row of the detection that owns the
+    pixel, the lowest row (= highest score after the slide NMS) among those whose pasted mask is >= threshold there — and the int32 pixel
+    count of every row.  Two launches (ops.paste_label_map, ops.label_areas) for any number of detections; nothing is read back."""
+    from hd_yolo_amd import ops
+    if 'masks' not in result:
+        raise ValueError("slide_label_map: the result has no 'masks' (run the model with compute_masks=True)")
+    lm = ops.paste_label_map(result['masks'], result['boxes'], size, window=window, threshold=threshold)
+    return lm, ops.label_areas(lm, len(result['boxes']))
+
+
+def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=False):
     """everything after the merge: de-duplication of overlapping windows, clamp to the slide, rescale"""
     out = {}
     for task_id, r in merged.items():
@@ -197,10 +233,13 @@ def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres):
         r['boxes'][:, [0, 2]] = r['boxes'][:, [0, 2]].clamp(0, W)
         r['boxes'][:, [1, 3]] = r['boxes'][:, [1, 3]].clamp(0, H)
         out[task_id] = header.rescale_outputs(r, scale)
+        if label_map and 'masks' in out[task_id]:
+            size = (int(round(H * scale)), int(round(W * scale)))
+            out[task_id]['label_map'], out[task_id]['areas'] = slide_label_map(out[task_id], size)
     return out
 
 
-def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background):
+def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map=False):
     from hd_yolo_amd import ops
     if isinstance(model, Ensemble):
         raise NotImplementedError('inference_on_slide: 8-bit slides run on one model (Model / Deploy); an Ensemble takes the float slide')
@@ -243,8 +282,10 @@ def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_t
             for (x0, y0), out in zip(table[i:i + count].tolist(), outputs):
                 for task_id, o in out.items():
                     per_task.setdefault(task_id, []).append(dict(o, roi=(float(x0), float(y0))))
+        if label_map:
+            _zero_row_masks(headers, per_task)
         merged = {task_id: headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map)
 
 
 SCORE_CELL_SIDES = 4.0          # score_slide: side of an ordering cell, in mean box sides (a block of 256 rows then spans a few cells)
@@ -317,6 +358,8 @@ def main():
     ap.add_argument('--u8', action='store_true', help='--slide: the synthetic slide as an 8-bit (H, W, 3) tensor (from the same seed), the way a slide reader delivers it')
     ap.add_argument('--min-tissue', type=float, default=0.0, help='--slide --u8: skip tiles with less than this fraction of non-background pixels')
     ap.add_argument('--score', action='store_true', help='--slide: also score a synthetic set of slide detections against a synthetic truth (score_slide)')
+    ap.add_argument('--masks', action='store_true', help='--slide: also run the slide through a synthetic mask model (the tiny variant, one mask class, fp32) with compute_masks')
+    ap.add_argument('--label-map', action='store_true', help='--slide --masks: paste the masks into one int32 label map of the slide (slide_label_map) and count the owned pixels')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
     opt = ap.parse_args()
@@ -345,6 +388,26 @@ def main():
         out = inference_on_slide(deployed.to(device), slide, tile=opt.imgsz, batch_size=opt.batch_size, min_tissue=opt.min_tissue)
         torch.cuda.synchronize()
         print(f'slide {opt.slide}x{opt.slide}: ' + ', '.join(f'{k}: {len(v["boxes"])} detections' for k, v in out.items()) + f' in {(time.time() - t0) * 1e3:.1f} ms')
+        if opt.label_map and not opt.masks:
+            ap.error('--label-map needs --masks')
+        if opt.masks:
+            cfg = synth.make_cfg('n', 2)
+            cfg['headers'][0][3][3] = 1                                   # one mask class: the mask model of tests/test_gpu_mask.py
+            mm = Model(cfg, synth.make_hyp(conf_thres=0.05))
+            mm.load_state_dict(synth.mask_state_dict(mm), strict=False)
+            mdep = Deploy(mm.to(device).eval())
+            kw = dict(tile=min(opt.imgsz, opt.slide), batch_size=opt.batch_size, compute_masks=True, label_map=opt.label_map)
+            inference_on_slide(mdep, slide, **kw)                         # warm-up: plans
+            torch.cuda.synchronize()
+            t0 = time.time()
+            out = inference_on_slide(mdep, slide, **kw)
+            torch.cuda.synchronize()
+            dt = (time.time() - t0) * 1e3
+            for k, v in out.items():
+                line = f'masks {opt.slide}x{opt.slide}, task {k}: {len(v["boxes"])} detections'
+                if 'areas' in v:
+                    line += f', {int(v["areas"].sum())} owned pixels of {v["label_map"].numel()} ({int((v["areas"] > 0).sum())} detections own some)'
+                print(line + f' in {dt:.1f} ms')
         if opt.score:
             # synthetic weights detect nothing meaningful, so the scored detections are synthetic too: annotations at nucleus density and
             # detections made from them (synth.synth_slide_truth)

@@ -1046,6 +1046,71 @@ def ap_match(pred_boxes, pred_scores, pred_labels, pred_off, true_boxes, true_la
     return hit, live, match, miou
 
 
+# ------------------------------------------------------------------------------------------ mask paste (csrc/paste.hip)
+PASTE_MIN_M, PASTE_MAX_M = 2, 62             # HDY_PASTE_MIN_M / HDY_PASTE_MAX_M (include/hdyolo.h)
+
+
+def _paste_inputs(who, masks, boxes, padding):
+    require_gpu(masks)
+    require_gpu(boxes)
+    if masks.dim() == 4 and masks.shape[1] == 1:
+        masks = masks[:, 0]
+    if masks.dim() != 3 or masks.shape[1] != masks.shape[2]:
+        raise _lib.HdyError(f'{who}: masks must be (R, M, M) or (R, 1, M, M), got {tuple(masks.shape)}')
+    m = masks.detach().float().contiguous()
+    b = boxes.detach().float().reshape(-1, 4).contiguous()
+    R, M = m.shape[0], m.shape[1]
+    if b.shape[0] != R:
+        raise _lib.HdyError(f'{who}: {R} masks, {b.shape[0]} boxes')
+    if not PASTE_MIN_M <= M <= PASTE_MAX_M:
+        raise _lib.HdyError(f'{who}: M={M} outside [{PASTE_MIN_M}, {PASTE_MAX_M}]')
+    if padding not in (0, 1):
+        raise _lib.HdyError(f'{who}: padding={padding} (0 or 1)')
+    return m, b, R, M
+
+
+def paste_masks(masks, boxes, size, padding=1):
+    """torchvision's paste_masks_in_image(masks, boxes, size, padding) on the device (hdy_paste_masks; reference val_nuclei.py:169-176): masks
+    (R, M, M) or (R, 1, M, M) probabilities in box coordinates, boxes (R, 4) xyxy in pixels of the (H, W) = size canvas -> (R, 1, H, W) fp32,
+    the resized mask inside each (expanded, integer) box and zero elsewhere.  One launch for all rows; zero rows give an empty result."""
+    m, b, R, M = _paste_inputs('paste_masks', masks, boxes, padding)
+    H, W = int(size[0]), int(size[1])
+    if H < 1 or W < 1:
+        raise _lib.HdyError(f'paste_masks: canvas {H} x {W}')
+    out = torch.empty((R, 1, H, W), dtype=torch.float32, device=m.device)
+    if R:
+        _lib.call('hdy_paste_masks', m.data_ptr(), R, M, int(padding), b.data_ptr(), out.data_ptr(), out.numel(), H, W, stream_ptr())
+    return out
+
+
+def paste_label_map(masks, boxes, size, window=None, threshold=0.5, padding=1):
+    """One int32 label map of the (H, W) = size canvas, or of its window (x0, y0, w, h) (hdy_paste_label_map): -1 = background, otherwise the
+    lowest row whose pasted mask (as paste_masks computes it) is >= threshold at the pixel — rows in descending score order, as the slide NMS
+    leaves them, give every pixel to its best detection.  One launch for all rows, no host synchronisation; the map may pass 2^31 entries."""
+    m, b, R, M = _paste_inputs('paste_label_map', masks, boxes, padding)
+    H, W = int(size[0]), int(size[1])
+    x0, y0, w, h = (0, 0, W, H) if window is None else (int(v) for v in window)
+    if H < 1 or W < 1 or w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise _lib.HdyError(f'paste_label_map: window {(x0, y0, w, h)} is not a non-empty part of the {H} x {W} canvas')
+    out = torch.empty((h, w), dtype=torch.int32, device=m.device)
+    _lib.call('hdy_paste_label_map', ptr(m) if R else None, R, M, int(padding), ptr(b) if R else None, float(threshold), x0, y0, out.data_ptr(),
+              out.numel(), h, w, stream_ptr())
+    return out
+
+
+def label_areas(label_map, R):
+    """areas (int32, R entries): pixels of the int32 label map that each row owns (hdy_label_areas)"""
+    require_gpu(label_map)
+    if label_map.dtype != torch.int32:
+        raise _lib.HdyError(f'label_areas: the map must be int32, got {label_map.dtype}')
+    lm = label_map.contiguous()
+    R = int(R)
+    areas = torch.empty((R,), dtype=torch.int32, device=lm.device)
+    if R:
+        _lib.call('hdy_label_areas', ptr(lm) if lm.numel() else None, lm.numel(), areas.data_ptr(), R, stream_ptr())
+    return areas
+
+
 # ------------------------------------------------------------------------------------------ mask branch primitives (row f2)
 def roi_align(feat, rois, spatial_scale, P, sampling_ratio=2, aligned=False):
     """feat NHWC (B, H, W, C) (possibly a pitched view), rois (R, 5) fp32 [image, x1, y1, x2, y2] -> (R, P, P, C) NHWC."""

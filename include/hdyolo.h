@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 10
+#define HDY_ABI_VERSION 11
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -425,6 +425,47 @@ int hdy_ap_match(const float* pred_boxes, const float* pred_scores, const long l
                  int pred_capacity, const float* true_boxes, const long long* true_labels, const int* true_off, const int* true_row,
                  int true_capacity, int n_img, const float* iouv, int n_iou, float pair_iou, const long long* ignore, int n_ignore,
                  unsigned short* hit, unsigned char* live, int* match, float* match_iou, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- mask paste: image-space instance masks, a slide label map and its areas (csrc/paste.hip) ------------------------------------------
+ * hdy_paste_masks replaces torchvision.models.detection.roi_heads.paste_masks_in_image as the reference calls it (val_nuclei.py:31,169-176 on
+ * every validation image, data.py:16,491); hdy_paste_label_map and hdy_label_areas give the whole-slide form the reference composes on the host
+ * from those pasted masks (one nucleus segmentation of the slide instead of one canvas per nucleus).  The arithmetic is torchvision's published
+ * algorithm (expand_boxes, paste_mask_in_image) with torch's CPU bilinear resize, stated here in full so that tests/paste_ref.py reproduces
+ * both modes bit for bit.  Everything is fp32 and every product, sum and quotient is rounded on its own (no FMA).
+ *
+ * masks fp32 [R][M][M] (Detect.attach_masks' probabilities in box coordinates; HDY_PASTE_MIN_M <= M <= HDY_PASTE_MAX_M), boxes fp32 [R][4]
+ * xyxy in canvas pixels, padding 0 or 1 (torchvision: 1).  Per row r:
+ *   P = M + 2 padding; the mask is framed by `padding` rows and columns of zeros: patch[P][P]
+ *   scale = float(P) / float(M)                                                                                   (expand_boxes)
+ *   hx = ((x2 - x1) * 0.5f) * scale, cx = (x2 + x1) * 0.5f;  ex1 = cx - hx, ex2 = cx + hx;  y alike
+ *   bx1 = int(ex1), bx2 = int(ex2), by1, by2: truncation toward zero (.to(int64)), not floor
+ *   a row with a non-finite expanded coordinate, or one of magnitude >= 2^30, pastes nothing
+ *   w = max(bx2 - bx1 + 1, 1), h = max(by2 - by1 + 1, 1): a degenerate box (x2 < x1) pastes one column
+ *   the patch is resized to h x w (F.interpolate, bilinear, align_corners=False); along x, for destination column d in [0, w):
+ *     sc = float(P) / float(w) (one IEEE division);  s = max(sc * (float(d) + 0.5f) - 0.5f, 0)
+ *     i0 = int(s), i1 = i0 + (i0 < P - 1), l1 = s - float(i0), l0 = 1 - l1;  along y alike with h
+ *   value(dy, dx) = ly0 * (lx0 * patch[iy0][ix0] + lx1 * patch[iy0][ix1]) + ly1 * (lx0 * patch[iy1][ix0] + lx1 * patch[iy1][ix1])
+ *   it belongs to canvas pixel (bx1 + dx, by1 + dy); the resized patch covers [bx1, bx1 + w) x [by1, by1 + h), clipped to the output.
+ * Rows whose mask label is negative arrive as all-zero masks (attach_masks) and therefore paste zeros / own nothing.
+ *
+ * hdy_paste_masks (dense mode): out fp32 [R][H][W], out_elems = R * H * W exactly (else HDY_EINVAL): the value where row r's box covers the
+ * canvas, zero elsewhere; every element is written.  No atomics.
+ * hdy_paste_label_map: map int32 [h][w] (map_elems = h * w exactly, 64-bit: it may pass 2^31) of the canvas window [x0, x0 + w) x [y0, y0 + h):
+ * -1 = background, otherwise the lowest row r whose value at the pixel is >= threshold (after the slide NMS the rows are in descending score
+ * order: the highest score owns the pixel).  The entry point fills the map with 0xFF bytes and one launch for all R rows does an unsigned
+ * 32-bit atomic minimum per covered pixel: order-independent, so repeats are bit-identical.  R is a host value; no device-to-host copy.
+ * hdy_label_areas: areas int32 [R], zeroed by the call; areas[r] = number of map entries equal to r (entries outside [0, R) are not counted).
+ * Integer adds of run lengths: exact and order-independent.
+ * HDY_EINVAL with a message: null pointers, M or padding out of range, sides outside [1, HDY_PASTE_MAX_SIDE], out_elems / map_elems that
+ * differ from what the call writes.  All argument checks are made before any launch. */
+#define HDY_PASTE_MIN_M 2
+#define HDY_PASTE_MAX_M 62
+#define HDY_PASTE_MAX_SIDE (1 << 29)
+int hdy_paste_masks(const float* masks, int R, int M, int padding, const float* boxes, float* out, long long out_elems, int H, int W,
+                    void* stream);
+int hdy_paste_label_map(const float* masks, int R, int M, int padding, const float* boxes, float threshold, int x0, int y0, int* map,
+                        long long map_elems, int h, int w, void* stream);
+int hdy_label_areas(const int* map, long long map_elems, int* areas, int R, void* stream);
 
 /* ---- mask branch primitives ------------------------------------------------------------
  * hdy_roi_align_fwd/bwd replace torchvision.ops.roi_align as the reference calls it (metayolo/models/yolo_head.py:243 on ground
