@@ -18,8 +18,9 @@
 // Epilogue: a lane holds 4 consecutive channels of one dx pixel; the block is staged as rows of 128 bytes (NCG = 2: two neighbouring dx pixels per
 // row, NCG = 4: one), 8-byte slots XORed with the tile column, and leaves with 16-byte stores, every dx row of the block as one contiguous run.
 //
-// Requirements (checked by the launcher, otherwise the class walk runs): bf16, (dy, dx) channels (64, 32) or (128, 64), even H and W, H/2 % 8 == 0,
-// W/2 % 16 == 0, 16-byte aligned rows, no producer-side statistics.
+// Selection (the CONV_DGRAD_S2 family of conv_dispatch.hip's walk, otherwise the generic kernel's class walk runs): hdy_dgrad3x3s2_plan takes the
+// four-class walk of a bf16 3x3 / stride 2 / pad 1 layer with (dy, dx) channels (64, 32) or (128, 64), H/2 % 8 == 0 (64 <- 128: % 4) and W/2 % 16 == 0;
+// hdy_dgrad3x3s2_launch declines a call without 16-byte aligned rows.  Producer-side statistics never come here (they start the walk at the generic kernel).
 #include <stdlib.h>
 
 #include "common.h"
@@ -240,14 +241,12 @@ __global__ __launch_bounds__(64 * NCG * (TH / 4), 2) void dgrad3x3s2_kernel(cons
 }  // namespace
 
 template <int NP, int NCG, int TH>
-static int dgrad_s2_launch(const ConvArgs& a, hipStream_t st) {
+static int dgrad_s2_launch(const ConvArgs& a, int grid, hipStream_t st) {
     using G = Geo<NP, NCG, TH>;
     static PerDeviceOnce attr_once;           // first launch of this instance on any thread
     attr_once.run([&] {
         (void)hipFuncSetAttribute((const void*)dgrad3x3s2_kernel<NP, NCG, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM_B);
     });
-    const int tiles = a.N * (a.Ho / TH) * (a.Wo / TW);
-    const int grid = tiles < 512 ? tiles : 512;                  // two ~70 KB, 4-wave workgroups per CU
 #ifdef HDY_PROBE_BUILD      // timing ablations (results wrong) exist only in a -DHDY_PROBE_BUILD library, never in the shipped one
     const int abl = hdy_opt(HDY_OPT_DEEP_DEBUG);
     if constexpr (NP == 2) if (abl) {
@@ -257,29 +256,27 @@ static int dgrad_s2_launch(const ConvArgs& a, hipStream_t st) {
     }
 #endif
     hipLaunchKernelGGL((dgrad3x3s2_kernel<NP, NCG, TH>), dim3(grid), dim3(G::NTHR), G::SMEM_B, st, a);
-    return (int)hipGetLastError();
+    return hdy_launch_status("dgrad3x3s2");
 }
 
-// Returns 1 and launches when the class-walk arguments describe one of the two layers; 0 = not eligible (the generic kernel runs).
-int hdy_dgrad3x3s2_try(const ConvArgs& a, int dtype, hipStream_t st, int* rc) {
+// The shape is this kernel's (hdyolo_internal.h, ConvPlan): the four-class walk of one of the two layers.  variant = dy planes, 1 = <1, 2, 8>
+// (32 <- 64), 2 = <2, 4, 4> (64 <- 128).  Two ~70 KB, 4-wave workgroups per CU.  With R = S = 3 and pad 1 the class tables are the ones in the
+// header comment: taps 1 / 2 per axis, every window starting at dy offset 0.
+bool hdy_dgrad3x3s2_plan(const ConvShape& s, ConvPlan* p) {
     const int disabled = hdy_opt(HDY_OPT_NO_DGRAD_S2);            // tests: 1 forces the class walk for A/B comparison, 2 only for the 64 <- 128 layer
-    if (disabled == 1 || dtype != HDY_BF16 || a.ncls != 4 || a.nstat != 0 || a.res || a.scale || a.shift || a.act != 0 || a.stats) return 0;
-    const int np = a.C / 64;                                     // dy planes
-    if (!((a.C == 64 && a.K == 32) || (a.C == 128 && a.K == 64 && disabled != 2))) return 0;
-    if (a.Ho % (np == 1 ? 8 : 4) || a.Wo % TW || a.Hin != a.Ho || a.Win != a.Wo || a.Hout != 2 * a.Ho || a.Wout != 2 * a.Wo) return 0;
-    static const int dh[4] = {0, 0, 0, 0}, dw[4] = {0, 0, 0, 0}, nth[4] = {1, 1, 2, 2}, ntw[4] = {1, 2, 1, 2}, oh[4] = {0, 0, 1, 1}, ow[4] = {0, 1, 0, 1};
-    for (int c = 0; c < 4; ++c)
-        if (a.c_dh[c] != dh[c] || a.c_dw[c] != dw[c] || a.c_TH[c] != nth[c] || a.c_TW[c] != ntw[c] || a.c_oh[c] != oh[c] || a.c_ow[c] != ow[c] ||
-            a.c_nkb[c] != nth[c] * ntw[c] * np || a.c_w[c] % 8)
-            return 0;
-    if (a.ldx % 8 || a.ldy % 8 || ((uintptr_t)a.x & 15) || ((uintptr_t)a.y & 15) || ((uintptr_t)a.w & 15)) return 0;
-    hdy_note_dispatch(np == 1 ? "dgrad3x3s2_k64c32" : "dgrad3x3s2_k128c64");
-    const int e = np == 1 ? dgrad_s2_launch<1, 2, 8>(a, st) : dgrad_s2_launch<2, 4, 4>(a, st);
-    if (e != (int)hipSuccess) {
-        hdy_set_error("dgrad3x3s2: launch failed: %s", hipGetErrorString((hipError_t)e));
-        *rc = e;
-        return 1;
-    }
-    *rc = HDY_OK;
-    return 1;
+    if (disabled == 1 || s.dtype != HDY_BF16 || s.ncls != 4 || s.stats || s.R != 3 || s.S != 3 || s.stride != 2 || s.pad != 1) return false;
+    const int planes = (s.C == 64 && s.K == 32) ? 1 : ((s.C == 128 && s.K == 64 && disabled != 2) ? 2 : 0);
+    const int th = planes == 1 ? 8 : 4;
+    if (!planes || s.Ho % th || s.Wo % TW) return false;
+    const int tiles = s.N * (s.Ho / th) * (s.Wo / TW);
+    *p = ConvPlan{CONV_DGRAD_S2, planes, tiles < 512 ? tiles : 512, 0, 0, 0};
+    return true;
+}
+
+int hdy_dgrad3x3s2_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st) {
+    if (out_f32 || a.res || a.scale || a.shift || a.act != 0) return HDY_CONV_DECLINE;
+    const bool aligned = rows_aligned(a, true) && a.c_w[0] % 8 == 0 && a.c_w[1] % 8 == 0 && a.c_w[2] % 8 == 0 && a.c_w[3] % 8 == 0;
+    if (const int rc = hdy_conv_take(a, p, aligned, "dgrad3x3s2")) return rc;
+    hdy_note_dispatch(p.variant == 1 ? "dgrad3x3s2_k64c32" : "dgrad3x3s2_k128c64");
+    return p.variant == 1 ? dgrad_s2_launch<1, 2, 8>(a, p.grid, st) : dgrad_s2_launch<2, 4, 4>(a, p.grid, st);
 }

@@ -1,14 +1,18 @@
 // Kernel selection and launch of the convolution families (host code only).
 //
 // Forward / data gradient: conv_fwd_plan() is the one ordered walk over the families: each family's <name>_plan (in its own file) says
-// whether a ConvShape is its own and, if so, with which instance, grid and statistic-slab count.  The sizing query (hdy_conv_stat_slabs)
-// and the launch (hdy_conv_launch) below both read that plan, so the slab array a caller sized is the one the kernel about to start writes.
+// whether a ConvShape is its own and, if so, with which instance, grid and statistic-slab count.  The sizing queries (hdy_conv_stat_slabs,
+// hdy_conv_dgrad_stat_slabs) and the launch (hdy_conv_launch) below both read that plan, so the slab array a caller sized is the one the
+// kernel about to start writes.  The entry points (hdy_conv_fwd, hdy_conv_dgrad, hdy_conv_dgrad_stats) follow: each states its layer as a
+// ConvShape for the walk and as a ConvArgs (tap-window geometry) for the kernels.
 //
 // Weight gradient: the same with WgradShape / WgradPlan and wgrad_plan(); the workspace query (hdy_conv_wgrad_workspace_bytes) and the
 // entry points that launch (hdy_conv_wgrad, hdy_conv_wgrad_stem_fused) are at the end of this file.
 #include "common.h"
 #include "hdyolo_internal.h"
 #include "hdyolo.h"
+
+static inline int bke(int dtype) { return dtype == HDY_BF16 ? 64 : 32; }      // elements of a 128-byte k-block
 
 // the plan of the first family from `first` on that takes the shape
 static ConvPlan conv_fwd_plan(const ConvShape& s, int first = CONV_STEM) {
@@ -17,6 +21,7 @@ static ConvPlan conv_fwd_plan(const ConvShape& s, int first = CONV_STEM) {
     if (first <= CONV_3X3_C64 && hdy_conv3x3_c64_plan(s, &p)) return p;           // filter-resident 3x3, 32 / 64 input channels
     if (first <= CONV_3X3_C128 && hdy_conv3x3_c128_plan(s, &p)) return p;         // ... its 128-input-channel form
     if (first <= CONV_3X3S2 && hdy_conv3x3s2_plan(s, &p)) return p;               // patch-resident 3x3 / stride 2
+    if (first <= CONV_DGRAD_S2 && hdy_dgrad3x3s2_plan(s, &p)) return p;           // ... its data gradient, 32 <- 64 and 64 <- 128 (four-class walk)
     if (first <= CONV_DEEP && hdy_conv_deep_plan(s, &p)) return p;                // deep-pipelined 256-row implicit GEMM (C % 64 == 0, K >= 128)
     hdy_conv_igemm_plan(s, &p);                                                   // generic implicit GEMM: takes everything
     return p;
@@ -33,29 +38,15 @@ static int launch_planned(const ConvArgs& a, const ConvPlan& p, int dtype, int o
         case CONV_3X3_C64: return hdy_conv3x3_c64_launch(a, p, out_f32, st);
         case CONV_3X3_C128: return hdy_conv3x3_c128_launch(a, p, out_f32, st);
         case CONV_3X3S2: return hdy_conv3x3s2_launch(a, p, out_f32, st);
+        case CONV_DGRAD_S2: return hdy_dgrad3x3s2_launch(a, p, out_f32, st);
         case CONV_DEEP: return hdy_conv_deep_launch(a, p, out_f32, st);
         default: return hdy_conv_igemm_launch(a, p, dtype, out_f32, st);
     }
 }
 
-// The layer a validated ConvArgs describes, derived in this one place.  A forward launch gives back what hdy_conv_fwd was called with; a
-// stride-1 data gradient is the convolution with C and K swapped and pad' = R - 1 - pad; a parity class of a stride-2 data gradient has no
-// such description (pad = -1) and only the implicit-GEMM families take it.
-static ConvShape shape_of(const ConvArgs& a, int dtype) {
-    ConvShape s = {};
-    s.N = a.N; s.H = a.Hin; s.W = a.Win; s.Ho = a.Ho; s.Wo = a.Wo; s.C = a.C; s.K = a.K; s.R = a.TH; s.S = a.TW; s.stride = a.ih_mul;
-    s.pad = -1; s.dense = a.dense_out; s.dtype = dtype; s.stats = a.stats != nullptr; s.ncls = a.ncls > 1 ? 4 : 1;
-    if (a.span_pixels) {                      // hdy_conv_fwd's stem: six row taps over the 24 pseudo channels of the padded 4-channel image
-        s.stem = 1; s.H = a.Hin - 4; s.W = a.Win - 4; s.C = 3; s.R = s.S = 6; s.stride = 2; s.pad = 2;
-    } else if (a.ncls <= 1 && a.dense_out && a.ih_mul == a.iw_mul && a.dh0 == a.dw0 && a.dh0 <= 0 && a.Ho == conv_out_dim(a.Hin, a.TH, a.ih_mul, -a.dh0) &&
-               a.Wo == conv_out_dim(a.Win, a.TW, a.iw_mul, -a.dw0)) {
-        s.pad = -a.dh0;
-    }
-    return s;
-}
-
-// Host-side validation + dispatch shared by the C-ABI entry points (api.hip).
-int hdy_conv_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st) {
+// Host-side validation + dispatch shared by the entry points below: `s` is the layer `a` describes, as its caller states it.
+static int hdy_conv_launch(ConvArgs a, const ConvShape& s, int out_f32, hipStream_t st) {
+    const int dtype = s.dtype;
     const int VE = dtype == HDY_BF16 ? 8 : 4;
     HDY_ARG(a.x && a.w && a.y, "conv: null pointer");
     HDY_ARG(a.N > 0 && a.Hin > 0 && a.Win > 0 && a.Ho > 0 && a.Wo > 0 && a.K > 0 && a.C > 0, "conv: non-positive dim");
@@ -111,7 +102,6 @@ int hdy_conv_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st) {
     for (int c = 0; c < 4; ++c) hdy_magic((unsigned)(a.ncls > 1 ? a.c_TW[c] : a.TW), &a.mg_tw[c], &a.sh_tw[c]);
     // Producer-side statistics (nstat) exist in the generic kernel only.  A family whose plan it is but whose kernel this call does not
     // fit (hdy_conv_take) hands the launch to the families after it.
-    const ConvShape s = shape_of(a, dtype);
     for (int first = a.nstat > 0 ? CONV_IGEMM : CONV_STEM;;) {
         const ConvPlan p = conv_fwd_plan(s, first);
         a.tile_interleave = p.interleave;
@@ -120,6 +110,148 @@ int hdy_conv_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st) {
         first = p.family + 1;
     }
 }
+
+// ---- data gradient --------------------------------------------------------------------------------------------------------------------
+// Stride-2 data gradient as ONE launch that walks the four parity classes per spatial tile: every class has the same Ho x Wo (even H and W)
+// and taps of its own.
+static bool dgrad_class_walk(int H, int W, int R, int S, int pad) {
+    if (H % 2 || W % 2 || hdy_opt(HDY_OPT_NO_CLASS_WALK)) return false;
+    for (int a = 0; a < 2; ++a)
+        if (!class_axis(R, pad, a).taps || !class_axis(S, pad, a).taps) return false;
+    return true;
+}
+
+// The data gradient of a layer as the convolution from dy's K channels, on dy's pixel grid, to dx's C.  Stride 1: the same window with
+// pad' = R - 1 - pad (-1 where no forward window has that padding).  Stride 2, where dgrad_class_walk holds: the four-class walk over
+// H/2 x W/2 pixels per class, with the window of the layer being differentiated (hdyolo_internal.h, ConvShape).
+static ConvShape dgrad_shape(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype) {
+    const bool walk = stride == 2;
+    const int pad1 = R == S && pad <= R - 1 ? R - 1 - pad : -1;
+    return ConvShape{N, conv_out_dim(H, R, stride, pad), conv_out_dim(W, S, stride, pad), H / stride, W / stride, K, C, R, S, stride, walk ? pad : pad1,
+                     !walk, dtype, 0, 0, walk ? 4 : 1};
+}
+
+// dx (+)= conv_transpose(dy, w): dx is [N][H][W][lddx] (C channels), dy is [N][Ho][Wo][lddy] (K channels).
+static int dgrad_impl(const void* dy, int lddy, const void* w_packed_dgrad, void* dx, int lddx, int N, int H, int W, int C, int K, int R,
+                      int S, int stride, int pad, int accumulate, int dtype, const hdy_stat_req* stats, int nstat, void* stream) {
+    HDY_ARG(stride == 1 || stride == 2, "conv_dgrad: stride %d unsupported", stride);
+    HDY_ARG(dtype == HDY_BF16 || dtype == HDY_F32, "conv_dgrad: unknown dtype %d", dtype);
+    const int Ho = conv_out_dim(H, R, stride, pad), Wo = conv_out_dim(W, S, stride, pad);
+    HDY_ARG(Ho > 0 && Wo > 0, "conv_dgrad: empty dy");
+    ConvArgs a = {};
+    a.x = dy; a.y = dx; a.N = N; a.Hin = Ho; a.Win = Wo; a.C = K; a.ldx = lddy;
+    a.K = C; a.ldy = lddx; a.Hout = H; a.Wout = W;
+    a.ih_mul = a.iw_mul = 1; a.accumulate = accumulate;
+    a.nstat = nstat;
+    for (int r = 0; r < nstat; ++r)
+        a.stat[r] = StatReq{stats[r].y, stats[r].ldy, stats[r].scale, stats[r].shift, stats[r].slabs, stats[r].c0, stats[r].c1, stats[r].act, stats[r].nslabs};
+    if (stride == 1) {
+        a.w = w_packed_dgrad;
+        a.Ho = H; a.Wo = W; a.oh_mul = a.ow_mul = 1; a.dense_out = 1;
+        a.dh0 = pad - (R - 1); a.dw0 = pad - (S - 1); a.TH = R; a.TW = S;
+        a.Kdp = round_up(R * S * K, bke(dtype));
+        return hdy_conv_launch(a, dgrad_shape(N, H, W, C, K, R, S, stride, pad, dtype), 0, (hipStream_t)stream);
+    }
+    const int rows_total = round_up(C, hdy_conv_bn_tile(C));
+    size_t off = 0;
+    // One launch walking the four parity classes per spatial tile (conv_igemm.hip, `walk`): every class has the same Ho x Wo when H and W
+    // are even.  As four launches each class wrote every other pixel of every other row (half cache lines, each line written by two
+    // launches) and read dy from HBM again: 32<-64 @320x320 B=64 took 353 us against a 100 us bound.
+    if (dgrad_class_walk(H, W, R, S, pad)) {
+        ConvArgs c = a;
+        c.ncls = 4;
+        c.Ho = H / 2; c.Wo = W / 2;
+        c.oh_mul = c.ow_mul = 2; c.dense_out = 0;
+        for (int ca = 0; ca < 2; ++ca)
+            for (int cb = 0; cb < 2; ++cb) {
+                const Axis ah = class_axis(R, pad, ca), aw = class_axis(S, pad, cb);
+                const int i = ca * 2 + cb;
+                const int Kdp = round_up(ah.taps * aw.taps * K, bke(dtype));
+                c.c_dh[i] = ah.d0; c.c_dw[i] = aw.d0; c.c_TH[i] = ah.taps; c.c_TW[i] = aw.taps;
+                c.c_nkb[i] = Kdp / bke(dtype); c.c_oh[i] = ca; c.c_ow[i] = cb; c.c_w[i] = (long long)off;
+                off += (size_t)rows_total * Kdp;
+            }
+        c.w = w_packed_dgrad;
+        c.dh0 = c.c_dh[0]; c.dw0 = c.c_dw[0]; c.TH = c.c_TH[0]; c.TW = c.c_TW[0]; c.oh_off = c.ow_off = 0;
+        c.Kdp = c.c_nkb[0] * bke(dtype);
+        return hdy_conv_launch(c, dgrad_shape(N, H, W, C, K, R, S, stride, pad, dtype), 0, (hipStream_t)stream);
+    }
+    for (int ca = 0; ca < 2; ++ca)
+        for (int cb = 0; cb < 2; ++cb) {
+            const Axis ah = class_axis(R, pad, ca), aw = class_axis(S, pad, cb);
+            ConvArgs c = a;
+            c.Ho = (H - ca + 1) / 2; c.Wo = (W - cb + 1) / 2;
+            c.oh_mul = c.ow_mul = 2; c.oh_off = ca; c.ow_off = cb; c.dense_out = 0;
+            if (!ah.taps || !aw.taps) {
+                HDY_ARG(false, "conv_dgrad: kernel %dx%d pad %d leaves a parity class without taps (unsupported)", R, S, pad);
+            }
+            if (c.Ho <= 0 || c.Wo <= 0) continue;
+            c.dh0 = ah.d0; c.dw0 = aw.d0; c.TH = ah.taps; c.TW = aw.taps;
+            c.Kdp = round_up(ah.taps * aw.taps * K, bke(dtype));
+            c.w = (const char*)w_packed_dgrad + off * (dtype == HDY_BF16 ? 2 : 4);
+            off += (size_t)rows_total * c.Kdp;
+            // one parity class alone: its own tap window at stride 1, no padding a forward window has; only the implicit-GEMM families take it
+            const ConvShape s = {N, Ho, Wo, c.Ho, c.Wo, K, C, ah.taps, aw.taps, 1, -1, 0, dtype, 0, 0, 1};
+            const int rc = hdy_conv_launch(c, s, 0, (hipStream_t)stream);
+            if (rc) return rc;
+        }
+    return HDY_OK;
+}
+
+extern "C" {
+
+// y = act(scale * conv(x, w) + shift) [+= y]; NHWC with pixel pitches; optional BatchNorm slabs in `stats`.
+// stem != 0: x is the hdy_stem_prep() buffer [N][H+2*pad][W+2*pad][4] and (C,R,S,stride,pad) must be (3,6,6,2,2).
+int hdy_conv_fwd(const void* x, int ldx, const void* w_packed, const float* scale, const float* shift, const void* res, int ldr, void* y,
+                 int ldy, float* stats, int stat_slabs, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int act, int accumulate,
+                 int dtype, int out_f32, int stem, void* stream) {
+    HDY_ARG(!stats || stat_slabs > 0, "conv_fwd: stats given with stat_slabs = %d", stat_slabs);
+    HDY_ARG(stride >= 1 && R >= 1 && S >= 1 && pad >= 0, "conv_fwd: bad window");
+    HDY_ARG(dtype == HDY_BF16 || dtype == HDY_F32, "conv_fwd: unknown dtype %d", dtype);
+    ConvArgs a = {};
+    a.x = x; a.w = w_packed; a.y = y; a.scale = scale; a.shift = shift; a.stats = stats; a.stat_cap = stat_slabs; a.res = res; a.ldr = ldr;
+    HDY_ARG(!res || ldr >= K, "conv_fwd: residual pitch %d < K", ldr);
+    a.N = N;
+    a.Ho = conv_out_dim(H, R, stride, pad);
+    a.Wo = conv_out_dim(W, S, stride, pad);
+    HDY_ARG(a.Ho > 0 && a.Wo > 0, "conv_fwd: empty output");
+    a.K = K; a.ldy = ldy;
+    a.Hout = a.Ho; a.Wout = a.Wo; a.oh_mul = a.ow_mul = 1; a.oh_off = a.ow_off = 0; a.dense_out = 1;
+    a.act = act; a.accumulate = accumulate;
+    if (stem) {
+        HDY_ARG(C == 3 && R == 6 && S == 6 && stride == 2 && pad == 2 && ldx == 4, "conv_fwd: stem expects C=3 k=6 s=2 p=2 on a 4-channel padded image");
+        a.Hin = H + 2 * pad; a.Win = W + 2 * pad; a.C = 24; a.ldx = 4; a.span_pixels = 1;
+        a.ih_mul = 2; a.iw_mul = 2; a.dh0 = 0; a.dw0 = 0; a.TH = 6; a.TW = 1;
+        a.Kdp = round_up(6 * 24, bke(dtype));
+    } else {
+        a.Hin = H; a.Win = W; a.C = C; a.ldx = ldx;
+        a.ih_mul = stride; a.iw_mul = stride; a.dh0 = -pad; a.dw0 = -pad; a.TH = R; a.TW = S;
+        a.Kdp = round_up(R * S * C, bke(dtype));
+    }
+    return hdy_conv_launch(a, conv_shape(N, H, W, C, K, R, S, stride, pad, dtype, stem != 0, stats != nullptr), out_f32, (hipStream_t)stream);
+}
+
+int hdy_conv_dgrad(const void* dy, int lddy, const void* w_packed_dgrad, void* dx, int lddx, int N, int H, int W, int C, int K, int R,
+                   int S, int stride, int pad, int accumulate, int dtype, void* stream) {
+    return dgrad_impl(dy, lddy, w_packed_dgrad, dx, lddx, N, H, W, C, K, R, S, stride, pad, accumulate, dtype, nullptr, 0, stream);
+}
+
+int hdy_conv_dgrad_stats(const void* dy, int lddy, const void* w_packed_dgrad, void* dx, int lddx, int N, int H, int W, int C, int K, int R,
+                         int S, int stride, int pad, int accumulate, int dtype, const hdy_stat_req* stats, int nstat, void* stream) {
+    HDY_ARG(nstat >= 0 && nstat <= 2 && (nstat == 0 || stats), "conv_dgrad_stats: bad request count");
+    HDY_ARG(nstat == 0 || hdy_conv_dgrad_stat_slabs(N, H, W, C, K, R, S, stride, pad, dtype) > 0, "conv_dgrad_stats: this shape cannot serve statistics");
+    return dgrad_impl(dy, lddy, w_packed_dgrad, dx, lddx, N, H, W, C, K, R, S, stride, pad, accumulate, dtype, stats, nstat, stream);
+}
+
+// workgroups of the data-gradient launch that would serve statistics: stride 1, or stride 2 as ONE class-walking launch.  The statistics
+// instances are the generic kernel's with at most 64 output channels (the 128-wide ones have no registers to spare for the operands).
+int hdy_conv_dgrad_stat_slabs(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype) {
+    if (dtype != HDY_BF16 || C % 8 || hdy_conv_bn_tile(C) > 64 || (stride != 1 && stride != 2)) return 0;
+    if (stride == 2 && !dgrad_class_walk(H, W, R, S, pad)) return 0;
+    return conv_fwd_plan(dgrad_shape(N, H, W, C, K, R, S, stride, pad, dtype), CONV_IGEMM).grid;
+}
+
+}  // extern "C"
 
 // ---- weight gradient ------------------------------------------------------------------------------------------------------------------
 // the plan of the first family from `first` on that takes the shape

@@ -1,4 +1,4 @@
-// Internal (not part of the C ABI): argument blocks shared between api.hip and the kernel files.
+// Internal (not part of the C ABI): argument blocks shared between the entry points (conv_dispatch.hip, api.hip) and the kernel files.
 #pragma once
 #include <type_traits>
 
@@ -57,12 +57,13 @@ struct ConvArgs {
 };
 
 // ---- forward / data-gradient kernel selection -----------------------------------------------------------------------------------------
-// The layer as the selection sees it: what hdy_conv_stat_slabs is asked with, and what conv_dispatch.hip derives ONCE from a ConvArgs
-// (a stride-1 data gradient is the same convolution with C and K swapped and pad' = R - 1 - pad).
+// The layer as the selection sees it, stated by every entry point that launches or sizes (conv_dispatch.hip: conv_shape for the forward
+// pass; dgrad_shape, or one shape per parity class where a side is odd, for the data gradient: a convolution from dy's K channels to dx's C).
 struct ConvShape {
-    int N, H, W;          // input pixel grid (stem: the image, without its padding)
+    int N, H, W;          // input pixel grid (stem: the image, without its padding; data gradient: dy's)
     int Ho, Wo;           // output pixels per image the launch walks (ncls == 4: per parity class)
-    int C, K, R, S, stride;
+    int C, K, R, S, stride;   // ncls == 4: R, S, stride (2) and pad are those of the layer being DIFFERENTIATED (hdy_dgrad3x3s2_plan reads them; no
+                          // other family reads R, S, pad, H or W of a class walk: conv_is is false for it and conv_taps is not asked)
     int pad;              // < 0: the window is not padded alike on both axes, or the output grid is not the one (H, W, R, S, stride, pad) give
     int dense;            // every output pixel is written (0: one parity class of a stride-2 data gradient)
     int dtype;
@@ -73,6 +74,18 @@ struct ConvShape {
 // column tile of the generic kernel = row padding of a packed filter block
 inline int hdy_conv_bn_tile(int K) { return K <= 32 ? 32 : (K <= 64 ? 64 : 128); }
 inline int conv_out_dim(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
+// One spatial axis of a stride-2 dgrad parity class: output positions h = 2*i + a take the kernel taps
+// r = rmax, rmax-2, ... (same parity as a + pad), reading dy row i + d0 + t for the t-th of them.
+struct Axis { int taps, d0, rmax; };
+inline Axis class_axis(int R, int pad, int a) {
+    Axis ax = {0, 0, -1};
+    for (int r = R - 1; r >= 0; --r)
+        if (((a + pad - r) & 1) == 0) {
+            if (ax.rmax < 0) { ax.rmax = r; ax.d0 = (a + pad - r) / 2; }
+            ++ax.taps;
+        }
+    return ax;
+}
 // the layer hdy_conv_fwd / hdy_conv_stat_slabs are called with
 inline ConvShape conv_shape(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dtype, int stem, int stats) {
     return ConvShape{N, H, W, conv_out_dim(H, R, stride, pad), conv_out_dim(W, S, stride, pad), C, K, R, S, stride, pad, 1, dtype, stem, stats, 1};
@@ -83,7 +96,7 @@ inline int conv_taps(const ConvShape& s) { return s.stem ? 6 : s.R * s.S; }
 inline bool conv_is(const ConvShape& s, int R, int stride, int pad) { return !s.stem && s.ncls <= 1 && s.R == R && s.S == R && s.stride == stride && s.pad == pad; }
 
 // The order of this list is the order the families are asked in (conv_fwd_plan, conv_dispatch.hip); the generic kernel takes everything.
-enum ConvFamily { CONV_NONE = 0, CONV_STEM, CONV_3X3_C64, CONV_3X3_C128, CONV_3X3S2, CONV_DEEP, CONV_IGEMM };
+enum ConvFamily { CONV_NONE = 0, CONV_STEM, CONV_3X3_C64, CONV_3X3_C128, CONV_3X3S2, CONV_DGRAD_S2, CONV_DEEP, CONV_IGEMM };
 
 // What one family answers for a shape: the sizing query reads `slabs`, the launch reads all of it.
 struct ConvPlan {
@@ -100,6 +113,7 @@ bool hdy_conv_stem_plan(const ConvShape& s, ConvPlan* p);
 bool hdy_conv3x3_c64_plan(const ConvShape& s, ConvPlan* p);
 bool hdy_conv3x3_c128_plan(const ConvShape& s, ConvPlan* p);
 bool hdy_conv3x3s2_plan(const ConvShape& s, ConvPlan* p);
+bool hdy_dgrad3x3s2_plan(const ConvShape& s, ConvPlan* p);
 bool hdy_conv_deep_plan(const ConvShape& s, ConvPlan* p);
 bool hdy_conv_igemm_plan(const ConvShape& s, ConvPlan* p);
 
@@ -110,6 +124,7 @@ int hdy_conv_stem_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipS
 int hdy_conv3x3_c64_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
 int hdy_conv3x3_c128_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
 int hdy_conv3x3s2_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
+int hdy_dgrad3x3s2_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
 int hdy_conv_deep_launch(const ConvArgs& a, const ConvPlan& p, int out_f32, hipStream_t st);
 int hdy_conv_igemm_launch(const ConvArgs& a, const ConvPlan& p, int dtype, int out_f32, hipStream_t st);
 
@@ -220,5 +235,3 @@ int hdy_wgrad_generic_launch(const WgradArgs& a, const WgradPlan& p, hipStream_t
 // grad_a [K_a][C][R][S] and the optional grad_b [K_b][C][R][S] (rows K_a.. of every slab) (+)= SUM over `splits` slabs [K][Q] (conv_wgrad.hip)
 int hdy_wgrad_reduce(const float* partial, int splits, int K, int Q, int mode, int C, int R, int S, float* grad_a, int K_a, float* grad_b, int K_b,
                      int accumulate, hipStream_t st);
-int hdy_conv_launch(ConvArgs a, int dtype, int out_f32, hipStream_t st);      // validation + plan + launch (conv_dispatch.hip, next to hdy_conv_stat_slabs)
-int hdy_dgrad3x3s2_try(const ConvArgs& a, int dtype, hipStream_t st, int* rc);

@@ -6,6 +6,8 @@ Tolerances: fp32 mode 1e-4 relative to the tensor's max magnitude (north star: 1
 bf16 mode 1.5e-2 (operands are pre-rounded to bf16 on both sides, so only accumulation order and the final
 bf16 rounding of outputs differ: 2^-8 = 3.9e-3 per rounding).
 """
+import fnmatch
+import functools
 import os
 
 import numpy as np
@@ -1015,6 +1017,57 @@ def test_specialised_kernel_agrees_with_generic_beyond_one_grid(case):
         assert_close(from_dev_nhwc(res[0].to(dt)), ref, TOL[dt], f'{name} vs torch')
         ulp = (res[0] - res[1]).abs() / (res[1].abs().clamp_min(2.0 ** -10) * 2.0 ** -7)
         assert ulp.max().item() <= 1.01, f'{name}: {ulp.max().item():.2f} bf16 ulps from the generic kernel'
+
+
+S2_EDGE_CASES = [
+    # ((N, H, W, C, K), dispatch-log pattern, dx pixel pitch, dx channel offset in its buffer, HDY_NO_DGRAD_S2, accumulate): C = dx channels, K = dy channels
+    ((1, 16, 32, 32, 64), 'dgrad3x3s2_k64c32', 32, 0, 0, False),       # the smallest shapes taken: one 8 x 16 tile of dy positions ...
+    ((1, 8, 32, 64, 128), 'dgrad3x3s2_k128c64', 64, 0, 0, False),      # ... one 4 x 16 tile
+    ((1, 24, 32, 32, 64), 'igemm_*_walk*', 32, 0, 0, False),           # H/2 = 12 is no multiple of 8
+    ((1, 12, 32, 64, 128), 'igemm_*_walk*', 64, 0, 0, False),          # H/2 = 6 is no multiple of 4
+    ((1, 16, 48, 32, 64), 'igemm_*_walk*', 32, 0, 0, False),           # W/2 = 24 is no multiple of 16
+    ((1, 16, 32, 32, 64), 'igemm_*_walk*', 36, 0, 0, False),           # the kernel's shape, declined by the launch: dx rows of 72 bytes
+    ((1, 16, 32, 32, 64), 'igemm_*_walk*', 40, 4, 0, False),           # ... dx base 8 bytes off a 16-byte boundary
+    ((1, 16, 32, 32, 64), 'dgrad3x3s2_k64c32', 32, 0, 2, False),       # HDY_NO_DGRAD_S2 = 2 switches off the 64 <- 128 form only
+    ((1, 8, 32, 64, 128), 'igemm_*_walk*', 64, 0, 2, False),
+    ((1, 16, 32, 32, 64), 'dgrad3x3s2_k64c32', 32, 0, 0, True),
+]
+
+
+@functools.lru_cache(maxsize=None)
+def s2_edge_reference(shape):
+    """dy, weight and the fp32 data gradient of a 3x3 / stride 2 / pad 1 layer on the CPU, computed once per shape and never modified"""
+    N, H, W, C, K = shape
+    w = rnd((K, C, 3, 3), 2, (3.0 / (C * 9)) ** 0.5)
+    dy = q(rnd((N, K, H // 2, W // 2), 5), torch.bfloat16)
+    return dy, w, F.conv_transpose2d(dy, q(w, torch.bfloat16), None, 2, 1, output_padding=1)
+
+
+@pytest.mark.parametrize('case', S2_EDGE_CASES, ids=[f'{"x".join(map(str, c[0]))}-ld{c[2]}+{c[3]}-off{c[4]}-{"acc" if c[5] else "store"}' for c in S2_EDGE_CASES])
+def test_stride2_data_gradient_selection_edges(case):
+    """The edges of the patch-resident stride-2 data gradient's selection (bf16, 3x3 / stride 2 / pad 1): the smallest shapes it takes, shapes one
+    step off each tile multiple, calls whose dx rows it cannot store with 16-byte accesses (the family declines and the generic kernel's class
+    walk runs), the value 2 of its switch, and accumulation.  Each against torch fp32 on the CPU; exactly one launch, named in the dispatch log;
+    dx starts as NaN (accumulate: a constant) and the pitch padding around it must stay NaN."""
+    shape, want, ld, off, no_s2, acc = case
+    N, H, W, C, K = shape
+    dt = torch.bfloat16
+    dy, w, ref = s2_edge_reference(shape)
+    dyd = to_dev_nhwc(dy, dt)
+    wpd = ops.pack_alloc(K, C, 3, 3, 2, 1, ops.PACK_DGRAD, dt, DEV)
+    ops.run([ops.rec_pack(w.to(DEV), None, 2, 1, ops.PACK_DGRAD, wpd)])
+    buf = torch.full((N, H, W, ld), float('nan'), dtype=dt, device=DEV)
+    dx = buf[..., off:off + C]
+    assert dx.data_ptr() % 16 == 2 * off % 16
+    if acc:
+        dx.fill_(0.5)
+    with _lib.option('HDY_NO_DGRAD_S2', no_s2):
+        _lib.dispatch_log(reset=True)
+        ops.run([ops.rec_conv_dgrad(dyd, wpd, dx, 3, 3, 2, 1, accumulate=acc)])
+        log = _lib.dispatch_log(reset=True)
+    assert len(log) == 1 and fnmatch.fnmatchcase(log[0], want), f'data gradient of {shape} ran {log}, expected {want}'
+    assert_close(from_dev_nhwc(dx), ref + 0.5 if acc else ref, TOL[dt], f'{log[0]} vs torch')
+    assert torch.isnan(buf[..., :off]).all() and torch.isnan(buf[..., off + C:]).all(), 'wrote into the pitch padding'
 
 
 WGRAD_DEEP_CASES = [

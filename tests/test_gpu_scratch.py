@@ -623,7 +623,8 @@ ROWS = [
     ('dgrad-igemm_walk', {}, lambda: dgrad_case('igemm stride-2 class walk', 2, 24, 24, 16, 32, 3, 2, 1, ['igemm_*_walk*'])),
     ('dgrad-conv3x3_c32', {}, lambda: dgrad_case('conv3x3_c32 dgrad', 2, 16, 32, 32, 32, 3, 1, 1, ['conv3x3_c32'])),
     ('dgrad-conv3x3_c64', {}, lambda: dgrad_case('conv3x3_c64 dgrad', 2, 16, 32, 64, 64, 3, 1, 1, ['conv3x3_c64'])),
-    # producer-side statistics are served by the generic kernel only (hdy_conv_dgrad_stat_slabs): the stride-2 form is its class walk
+    # producer-side statistics are served by the generic kernel only: their launch and hdy_conv_dgrad_stat_slabs both start the family walk at
+    # CONV_IGEMM, so the patch-resident families (dgrad3x3s2 among them) are never asked; the stride-2 form is the generic kernel's class walk
     ('dgrad-igemm-stats-3x3', {}, lambda: dgrad_case('igemm 3x3 dgrad + statistics', 3, 16, 16, 32, 64, 3, 1, 1, ['igemm_*'], stats=True)),
     ('dgrad-igemm_walk-stats', {}, lambda: dgrad_case('igemm class walk + statistics', 5, 128, 128, 32, 64, 3, 2, 1, ['igemm_*_walk*'], stats=True)),
     ('dgrad-conv3x3_c128', {}, lambda: dgrad_case('conv3x3_c128 dgrad', 3, 24, 40, 128, 128, 3, 1, 1, ['conv3x3_c128'])),
