@@ -206,7 +206,9 @@ __global__ __launch_bounds__(256) void match_kernel(const LossArgs p) {
         const float s0 = sigm(lg[0]), s1 = sigm(lg[1]), s2 = sigm(lg[2]), s3 = sigm(lg[3]);
         const D4 x1 = var(s0 * 2.f - 0.5f, 0), y1 = var(s1 * 2.f - 0.5f, 1);
         // a saturated sigmoid (logit < -88) gives w or h == 0 and the CIoU aspect term 0 * inf = NaN in the gradient (the
-        // reference's autograd has the same hole); a 1e-12 floor keeps everything finite and changes nothing measurable
+        // reference's autograd has the same hole); a 1e-12 floor keeps everything finite.  The floor is on the value only (the chain
+        // factor dpl below is the unfloored one) and acts from a logit of about -14.5 on (4 s^2 anchor < 1e-12), where the reference is
+        // still finite: there the aspect term sees the floored side.  tests/loss_ref.py has the same definition.
         const D4 w1 = var(fmaxf(4.f * s2 * s2 * aw, 1e-12f), 2), h1 = var(fmaxf(4.f * s3 * s3 * ah, 1e-12f), 3);
         const D4 x2 = cst(gx - gi), y2 = cst(gy - gj), w2 = cst(gw), h2 = cst(gh);
         const float eps = 1e-7f;

@@ -17,8 +17,10 @@ that picks their path).  Read-write operands (running statistics, the input slab
 Safety rule: a buffer that holds indices, counts, list heads or links is never filled with an arbitrary bit pattern — a buggy kernel could
 turn one into an address.  None of the rows below owns such a buffer.
 
-Not covered here: the fused detection loss (hdy_det_loss_ex, whose records carry links and list heads), hdy_nms_batched, hdy_mask_select and
-a whole training step with every non-zeroed plan buffer poisoned.  Those need in-range fills of their index buffers and are separate work.
+Not covered here: hdy_nms_batched, hdy_mask_select's scratch and a whole training step with every non-zeroed plan buffer poisoned.  Those need
+in-range fills of their index buffers and are separate work.  The fused detection loss (hdy_det_loss_ex, whose records carry links and list
+heads) has its stale-workspace test in tests/test_gpu_loss_direct.py: a call after a larger one on the same, never zeroed, record region must
+be bit-equal to a fresh call (stale records of a valid call hold in-range links, so nothing arbitrary is ever written into an index buffer).
 
 Repeat determinism: each row is also run R times on the same operands with a launch of a different family running concurrently on a side
 stream before every repeat (occupancy and timing change); every repeat must be bit-identical to the first.  The project promises fixed-order
