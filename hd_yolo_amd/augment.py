@@ -15,6 +15,8 @@ F_HFLIP, F_VFLIP, F_TRANSPOSE, F_HSV, F_PERSP = 1, 2, 4, 8, 16
 MAX_K = 8
 MAX_CELLS = 4096                       # B * k * k of one hdy_augment_boxes call
 MAX_BOXES_PER_TILE = 65536
+MASK_BACKGROUND = 0xFFFF               # an instance map's unowned pixels; a masked bank has at most 65535 boxes per tile
+MASK_SIDE = 28                         # side of a mask target (target_to_tensors)
 HYP_KEYS = ('degrees', 'translate', 'scale', 'shear', 'perspective', 'hsv_h', 'hsv_s', 'hsv_v', 'fliplr', 'flipud', 'transpose', 'cval',
             'k_mosaic', 'patch_size', 'img_size')
 
@@ -156,9 +158,12 @@ def identity_params(B, k, tile, patch, src=0):
 
 class TileBank:
     """Source tiles and their boxes.  `.npz` format: tiles uint8 (n, H, W, 3); boxes float32 (M, 4) xyxy in pixels; labels int64 (M,) in
-    1..nc; offsets int64 (n + 1,): tile t owns rows [offsets[t], offsets[t + 1]).  All tiles of a bank have one size; masks are refused."""
+    1..nc; offsets int64 (n + 1,): tile t owns rows [offsets[t], offsets[t + 1]).  All tiles of a bank have one size.  Optional: instances
+    uint16 (n, H, W), the instance map — a pixel holds the index of its object within its tile (bank row offsets[t] + value) or 0xFFFF for
+    background; one owner per pixel (overlapping objects get partial masks), every pixel of an object inside its box grown to pixel edges.
+    `has_mask` (uint8 per bank row: the object owns a pixel) is derived from it.  A `masks` array (any other mask format) is refused."""
 
-    def __init__(self, tiles, boxes, labels, offsets):
+    def __init__(self, tiles, boxes, labels, offsets, instances=None):
         tiles, boxes, labels, offsets = (np.asarray(a) for a in (tiles, boxes, labels, offsets))
         if tiles.dtype != np.uint8 or tiles.ndim != 4 or tiles.shape[3] not in (3, 4) or 0 in tiles.shape:
             raise ValueError(f'tile bank: tiles must be uint8 (n, H, W, 3) of one size, got {tiles.dtype} {tiles.shape} '
@@ -181,19 +186,48 @@ class TileBank:
         self.n, self.H, self.W = n, tiles.shape[1], tiles.shape[2]
         self.nc = int(labels.max()) if len(labels) else 0
         self.device = None
+        self.instances, self.has_mask = None, None
+        if instances is not None:
+            self.instances, self.has_mask = self._check_instances(np.asarray(instances))
+
+    def _check_instances(self, inst):
+        """the instance map against the boxes; -> (map, has_mask uint8 (M,))"""
+        if inst.dtype != np.uint16 or inst.shape != (self.n, self.H, self.W):
+            raise ValueError(f'tile bank: instances must be uint16 {(self.n, self.H, self.W)} (one value per tile pixel), got {inst.dtype} {inst.shape}')
+        if self.max_per_tile > MASK_BACKGROUND:
+            raise ValueError(f'tile bank: a tile with {self.max_per_tile} boxes (at most {MASK_BACKGROUND} with an instance map: 0xFFFF is background)')
+        has = np.zeros(len(self.boxes), np.uint8)
+        for t in range(self.n):
+            ys, xs = np.nonzero(inst[t] != MASK_BACKGROUND)
+            if not len(ys):
+                continue
+            v = inst[t][ys, xs].astype(np.int64)
+            lo, cnt = int(self.offsets[t]), int(self.offsets[t + 1] - self.offsets[t])
+            if (v >= cnt).any():
+                raise ValueError(f'tile bank: instances of tile {t} name object {int(v.max())}, the tile has {cnt} boxes')
+            b = self.boxes[lo + v]
+            inside = (np.floor(b[:, 0]) <= xs) & (xs < np.ceil(b[:, 2])) & (np.floor(b[:, 1]) <= ys) & (ys < np.ceil(b[:, 3]))
+            if not inside.all():
+                i = int(np.nonzero(~inside)[0][0])
+                raise ValueError(f'tile bank: pixel ({int(xs[i])}, {int(ys[i])}) of tile {t} belongs to object {int(v[i])} but lies outside its box '
+                                 f'{b[i].tolist()} grown to pixel edges')
+            has[lo + np.unique(v)] = 1
+        return inst, has
 
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
             if 'masks' in z.files:
-                raise ValueError('tile bank: mask targets are not supported by the device augmentation')
+                raise ValueError("tile bank: a 'masks' array is not supported by the device augmentation (instance masks travel as the uint16 "
+                                 "'instances' map)")
             missing = [key for key in ('tiles', 'boxes', 'labels', 'offsets') if key not in z.files]
             if missing:
                 raise ValueError(f'tile bank {path}: missing arrays {missing}')
-            return cls(z['tiles'], z['boxes'], z['labels'], z['offsets'])
+            return cls(z['tiles'], z['boxes'], z['labels'], z['offsets'], z['instances'] if 'instances' in z.files else None)
 
     def save(self, path):
-        np.savez(path, tiles=self.tiles, boxes=self.boxes, labels=self.labels, offsets=self.offsets)
+        extra = {} if self.instances is None else {'instances': self.instances}
+        np.savez(path, tiles=self.tiles, boxes=self.boxes, labels=self.labels, offsets=self.offsets, **extra)
 
     def to(self, device):
         """the bank as device tensors (uploaded once); returns self"""
@@ -205,5 +239,10 @@ class TileBank:
         boxes[:len(self.boxes)], labels[:len(self.labels)] = self.boxes, self.labels
         self.d_boxes, self.d_labels = torch.from_numpy(boxes).to(dev), torch.from_numpy(labels).to(dev)
         self.d_offsets = torch.from_numpy(np.ascontiguousarray(self.offsets)).to(dev)
+        if self.instances is not None:
+            self.d_instances = torch.from_numpy(np.ascontiguousarray(self.instances).view(np.int16)).to(dev)   # the map's bits (torch has no uint16 ops)
+            has = np.zeros((nb,), np.uint8)
+            has[:len(self.has_mask)] = self.has_mask
+            self.d_has_mask = torch.from_numpy(has).to(dev)
         self.device = dev
         return self

@@ -40,18 +40,26 @@ class DeviceTiles:
 
     `hyp` carries the reference's keys (degrees translate scale shear perspective hsv_h hsv_s hsv_v fliplr flipud transpose cval k_mosaic
     patch_size img_size); a missing one raises KeyError.  `cval` is the border value as the reference hands it to cv2 on an 8-bit image
-    (rounded half to even and clamped to 0..255).  Mask targets, keep_res > 0, color_aug other than 'hsv' and albumentations are refused.
+    (rounded half to even and clamped to 0..255).  keep_res > 0, color_aug other than 'hsv' and albumentations are refused.
+
+    A bank with an instance map (TileBank.instances) and `masks=True` (the default) adds `'masks'`: (n_i, 28, 28) fp32 views, to every
+    image's annotations, by three more launches per batch (csrc/augment_masks.hip: mask extents, the compaction with the masked objects'
+    boxes taken from their warped masks, the 28 x 28 targets); per buffer set it holds an extents workspace of batch_size * k^2 *
+    bank.max_per_tile * 32 bytes and `cap` x 28 x 28 floats, so pass `cap` (rows of a batch) when the default, every box of every cell, is
+    too much.  `masks=False`, or a bank without a map, takes the two launches and gives their bits.  Mask formats other than the instance
+    map (a bank with a `masks` attribute) are refused.
 
     The loader works on its own stream, one batch ahead: batch i + 1 is issued before batch i is handed out, and the per-image row counts —
     the only device-to-host copy, one per batch — are waited for through an event recorded a whole step earlier.  Two buffer sets
     alternate: a batch is valid until the next one is handed out.  Every (seed, rank, epoch, step) has its own numpy Generator, mixed as
     SyntheticTiles mixes them."""
 
-    def __init__(self, bank, hyp, batch_size, steps, rank=0, seed=0, device='cuda', dtype=torch.bfloat16, task='det', cap=None):
+    def __init__(self, bank, hyp, batch_size, steps, rank=0, seed=0, device='cuda', dtype=torch.bfloat16, task='det', cap=None, masks=True):
         from hd_yolo_amd import augment
         self.k, self.patch, self.imgsz, self.cval = augment.check_hyp(hyp)
         if getattr(bank, 'masks', None) is not None:
-            raise ValueError('DeviceTiles: mask targets are not supported')
+            raise ValueError("DeviceTiles: mask targets travel as the bank's uint16 instance map (TileBank.instances); other formats are not supported")
+        self.masks = bool(masks) and getattr(bank, 'instances', None) is not None
         self.hyp, self.bank, self.batch_size, self.steps, self.rank, self.seed, self.task = dict(hyp), bank, batch_size, steps, rank, seed, task
         self.device, self.dtype = torch.device(device), dtype
         if self.device.type != 'cuda':
@@ -75,6 +83,13 @@ class DeviceTiles:
                 'labels': torch.empty((self.cap,), dtype=torch.int64, device=dev), 'img': torch.empty((self.cap,), dtype=torch.float32, device=dev),
                 'counts': torch.empty((B + 1,), dtype=torch.int32, device=dev), 'counts_host': torch.empty((B + 1,), dtype=torch.int32).pin_memory(),
                 'event': torch.cuda.Event()})
+            if self.masks:
+                from hd_yolo_amd import ops
+                self.pitch = max(bank.max_per_tile, 1)
+                self.slots[-1].update({
+                    'ws': torch.empty(ops.augment_mask_workspace_bytes(n_cells, self.pitch), dtype=torch.uint8, device=dev),
+                    'ref': torch.empty((self.cap, 2), dtype=torch.int32, device=dev), 'total': torch.empty((1,), dtype=torch.int32, device=dev),
+                    'masks': torch.empty((self.cap, augment.MASK_SIDE, augment.MASK_SIDE), dtype=torch.float32, device=dev)})
         self._size = torch.tensor([S, S], dtype=torch.int64)
         self._ids = [torch.tensor([i], dtype=torch.int64) for i in range(B)]
 
@@ -97,9 +112,18 @@ class DeviceTiles:
             cells = slot['table'][:n_cells * augment.CELL_BYTES].view(n_cells, augment.CELL_BYTES)
             crop = slot['table'][n_cells * augment.CELL_BYTES:].view(torch.int32).view(self.batch_size, 2)
             ops.augment_tiles(self.bank.d_tiles, cells, crop, slot['imgs'], self.patch, self.k, self.cval)
-            ops.augment_boxes(self.bank.d_boxes, self.bank.d_labels, self.bank.d_offsets, len(self.bank.boxes), cells, crop, self.patch, self.k,
-                              self.imgsz, slot['boxes'], slot['labels'], slot['img'], slot['counts'][:self.batch_size],
-                              slot['counts'][self.batch_size:])
+            bank, nb = self.bank, len(self.bank.boxes)
+            if self.masks:
+                ops.augment_mask_extents(bank.d_instances, bank.d_boxes, bank.d_has_mask, bank.d_offsets, nb, cells, crop, self.patch, self.k,
+                                         self.imgsz, slot['ws'], self.pitch)
+                ops.augment_boxes_masks(bank.d_boxes, bank.d_labels, bank.d_has_mask, bank.d_offsets, nb, cells, crop, self.patch, self.k,
+                                        self.imgsz, slot['ws'], self.pitch, slot['boxes'], slot['labels'], slot['img'], slot['ref'],
+                                        slot['counts'][:self.batch_size], slot['counts'][self.batch_size:], slot['total'])
+                ops.augment_mask_targets(bank.d_instances, bank.d_has_mask, bank.d_offsets, nb, cells, crop, self.patch, self.k, self.imgsz,
+                                         slot['ws'], self.pitch, slot['boxes'], slot['ref'], slot['total'], slot['masks'])
+            else:
+                ops.augment_boxes(bank.d_boxes, bank.d_labels, bank.d_offsets, nb, cells, crop, self.patch, self.k, self.imgsz, slot['boxes'],
+                                  slot['labels'], slot['img'], slot['counts'][:self.batch_size], slot['counts'][self.batch_size:])
             slot['counts_host'].copy_(slot['counts'], non_blocking=True)
             self.d2h_copies += 1
             slot['event'].record(self.stream)
@@ -115,6 +139,9 @@ class DeviceTiles:
         boxes, labels = slot['boxes'][:total].split(counts), slot['labels'][:total].split(counts)
         targets = tuple({'image_id': self._ids[i], 'size': self._size,
                          'anns': {self.task: [{'size': self._size, 'boxes': boxes[i], 'labels': labels[i]}]}} for i in range(self.batch_size))
+        if self.masks:
+            for t, m in zip(targets, slot['masks'][:total].split(counts)):
+                t['anns'][self.task][0]['masks'] = m
         return tuple(slot['imgs'].unbind(0)), targets
 
     def __iter__(self):

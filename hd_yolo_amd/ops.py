@@ -847,6 +847,84 @@ def augment_boxes(bank_boxes, bank_labels, offsets, n_boxes, cells, crop, patch,
           int(patch), int(k), int(img_size), ptr(out_boxes), ptr(out_labels), ptr(out_img), cap, ptr(counts), counts.numel(), ptr(overflow))
 
 
+AUG_MASK_SIDE = 28
+AUG_MASK_REC_BYTES = 32
+
+
+def _instance_map(instances, has_mask, offsets):
+    """(ptr, n, H, W) of an instance map: a CUDA int16 / uint16 tensor (n, H, W), dense (the uint16 bits of TileBank.instances)"""
+    require_gpu(instances)
+    assert instances.dtype in (torch.int16, torch.uint16) and instances.dim() == 3 and instances.is_contiguous(), 'instance map: 16-bit (n, H, W), dense'
+    assert instances.shape[0] == offsets.shape[0] - 1, 'instance map: one plane per tile of the bank'
+    assert has_mask.dtype == torch.uint8 and has_mask.is_contiguous() and has_mask.is_cuda and has_mask.dim() == 1
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous()
+    return (instances.data_ptr(),) + tuple(instances.shape)
+
+
+def _mask_workspace(ws, n_cells, pitch):
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.is_cuda and 1 <= pitch <= 0xFFFF
+    return ws.data_ptr(), ws.numel()
+
+
+def augment_mask_workspace_bytes(n_cells, pitch):
+    """bytes of the extents workspace of a batch of n_cells cells whose tiles hold at most `pitch` boxes"""
+    return int(n_cells) * int(pitch) * AUG_MASK_REC_BYTES
+
+
+def augment_mask_extents(instances, bank_boxes, has_mask, offsets, n_boxes, cells, crop, patch, k, img_size, ws, pitch):
+    """Per candidate (cell, object of the cell's tile) the extents record of its warped mask (hdy_augment_mask_extents): member count, umin,
+    umax, vmin, vmax, pixels inside the image — int32 [n_cells][pitch][8] into the uint8 workspace `ws`.  has_mask uint8 (>= n_boxes,);
+    pitch: at least the bank's largest box count per tile.  No synchronisation."""
+    cp, n_cells, rp, B = _cell_table(cells, crop, k)
+    ip, n, H, W = _instance_map(instances, has_mask, offsets)
+    assert bank_boxes.dtype == torch.float32 and bank_boxes.is_contiguous() and bank_boxes.dim() == 2 and bank_boxes.shape[1] == 4
+    assert 0 <= n_boxes <= bank_boxes.shape[0] and has_mask.shape[0] >= n_boxes
+    wp, wbytes = _mask_workspace(ws, n_cells, pitch)
+    _call('hdy_augment_mask_extents', ip, n, H, W, ptr(bank_boxes), ptr(has_mask), ptr(offsets), int(n_boxes), cp, n_cells, rp, B, int(patch), int(k),
+          int(img_size), wp, wbytes, int(pitch))
+    return ws
+
+
+def augment_boxes_masks(bank_boxes, bank_labels, has_mask, offsets, n_boxes, cells, crop, patch, k, img_size, ws, pitch, out_boxes, out_labels,
+                        out_img, out_ref, counts, overflow, total):
+    """augment_boxes for a bank with an instance map (hdy_augment_boxes_masks): a row with has_mask takes the box of its warped mask from the
+    extents workspace and the 0.01 candidate test.  Also writes out_ref int32 (cap, 2) = (cell, object) per row and total int32 (1,) = rows
+    written.  No synchronisation."""
+    cp, n_cells, rp, B = _cell_table(cells, crop, k)
+    cap = out_boxes.shape[0]
+    assert bank_boxes.dtype == torch.float32 and bank_boxes.is_contiguous() and bank_boxes.dim() == 2 and bank_boxes.shape[1] == 4
+    assert bank_labels.dtype == torch.int64 and bank_labels.is_contiguous() and offsets.dtype == torch.int64 and offsets.is_contiguous()
+    assert 0 <= n_boxes <= bank_boxes.shape[0] and bank_labels.shape[0] >= n_boxes and has_mask.shape[0] >= n_boxes
+    assert has_mask.dtype == torch.uint8 and has_mask.is_contiguous() and has_mask.is_cuda
+    assert out_boxes.dtype == torch.float32 and out_boxes.is_contiguous() and tuple(out_boxes.shape) == (cap, 4)
+    assert out_labels.dtype == torch.int64 and out_labels.is_contiguous() and tuple(out_labels.shape) == (cap,)
+    assert out_img.dtype == torch.float32 and out_img.is_contiguous() and tuple(out_img.shape) == (cap,)
+    assert out_ref.dtype == torch.int32 and out_ref.is_contiguous() and tuple(out_ref.shape) == (cap, 2)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and overflow.dtype == torch.int32 and overflow.numel() >= 1
+    assert total.dtype == torch.int32 and total.numel() >= 1
+    wp, wbytes = _mask_workspace(ws, n_cells, pitch)
+    _call('hdy_augment_boxes_masks', ptr(bank_boxes), ptr(bank_labels), ptr(has_mask), ptr(offsets), offsets.shape[0] - 1, int(n_boxes), cp, n_cells,
+          rp, B, int(patch), int(k), int(img_size), wp, wbytes, int(pitch), ptr(out_boxes), ptr(out_labels), ptr(out_img), ptr(out_ref), cap,
+          ptr(counts), counts.numel(), ptr(overflow), ptr(total))
+
+
+def augment_mask_targets(instances, has_mask, offsets, n_boxes, cells, crop, patch, k, img_size, ws, pitch, out_boxes, out_ref, total, out_masks):
+    """The 28 x 28 mask targets of the rows augment_boxes_masks wrote (hdy_augment_mask_targets): out_masks fp32 (cap, 28, 28); rows at or
+    beyond total[0] (read on the device) are not written.  No synchronisation."""
+    cp, n_cells, rp, B = _cell_table(cells, crop, k)
+    ip, n, H, W = _instance_map(instances, has_mask, offsets)
+    cap = out_boxes.shape[0]
+    assert has_mask.shape[0] >= n_boxes >= 0
+    assert out_boxes.dtype == torch.float32 and out_boxes.is_contiguous() and tuple(out_boxes.shape) == (cap, 4)
+    assert out_ref.dtype == torch.int32 and out_ref.is_contiguous() and tuple(out_ref.shape) == (cap, 2)
+    assert total.dtype == torch.int32 and total.numel() >= 1
+    assert out_masks.dtype == torch.float32 and out_masks.is_contiguous() and tuple(out_masks.shape) == (cap, AUG_MASK_SIDE, AUG_MASK_SIDE)
+    wp, wbytes = _mask_workspace(ws, n_cells, pitch)
+    _call('hdy_augment_mask_targets', ip, n, H, W, ptr(has_mask), ptr(offsets), int(n_boxes), cp, n_cells, rp, B, int(patch), int(k), int(img_size),
+          wp, wbytes, int(pitch), ptr(out_boxes), ptr(out_ref), ptr(total), cap, ptr(out_masks), out_masks.numel())
+    return out_masks
+
+
 # ------------------------------------------------------------------------------------------ detection head
 def decode_level(det, anchor_px, stride, out, row_offset, level_id):
     """det: fp32 logits viewed as (B, na, ny, nx, no) with o contiguous (any other strides)."""

@@ -377,14 +377,16 @@ def synth_dense_boxes(n, seed=0):
     return np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32), rng.uniform(0, 1, n).astype(np.float32)
 
 
-def synth_tile_bank(n, size, nc, seed=0, nmin=20, nmax=60):
+def synth_tile_bank(n, size, nc, seed=0, nmin=20, nmax=60, instances=False):
     """A seeded 8-bit tile bank (hd_yolo_amd.augment.TileBank) for the device augmentation, because no real histology tiles ship with the
     project: `n` RGB tiles of size x size, an eosin-pink noisy background with `nmin`..`nmax` haematoxylin-blue elliptical nuclei of 14-34 px
-    per tile, one xyxy box in pixels and a label in 1..nc per nucleus."""
+    per tile, one xyxy box in pixels and a label in 1..nc per nucleus.  With `instances` the bank also carries the instance map of the
+    ellipses (later nuclei overwrite earlier ones, as their pixels do); the tiles, boxes and labels are the same bits either way."""
     import numpy as np
     from hd_yolo_amd.augment import TileBank
     rng = np.random.default_rng(5000 + seed)
     tiles = np.empty((n, size, size, 3), np.uint8)
+    inst = np.full((n, size, size), 0xFFFF, np.uint16) if instances else None
     boxes, labels, offsets = [], [], [0]
     for t in range(n):
         img = np.array([228.0, 182.0, 208.0]) + rng.normal(0, 9, (size, size, 3))
@@ -393,7 +395,7 @@ def synth_tile_bank(n, size, nc, seed=0, nmin=20, nmax=60):
         wh = rng.uniform(14, 34, (m, 2))
         lab = rng.integers(1, nc + 1, m)
         b = np.clip(np.concatenate([c - wh / 2, c + wh / 2], 1), 0, size)
-        for (x1, y1, x2, y2), l in zip(b, lab):
+        for idx, ((x1, y1, x2, y2), l) in enumerate(zip(b, lab)):
             xs, ys = np.arange(int(x1), int(np.ceil(x2))), np.arange(int(y1), int(np.ceil(y2)))
             if not len(xs) or not len(ys):
                 continue
@@ -402,8 +404,10 @@ def synth_tile_bank(n, size, nc, seed=0, nmin=20, nmax=60):
             sel = e <= 1.0
             patch = img[ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1]
             patch[sel] = colour + rng.normal(0, 6, (int(sel.sum()), 3))
+            if instances:
+                inst[t, ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1][sel] = idx
         tiles[t] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
         boxes.append(b.astype(np.float32))
         labels.append(lab.astype(np.int64))
         offsets.append(offsets[-1] + m)
-    return TileBank(tiles, np.concatenate(boxes), np.concatenate(labels), np.asarray(offsets, np.int64))
+    return TileBank(tiles, np.concatenate(boxes), np.concatenate(labels), np.asarray(offsets, np.int64), inst)

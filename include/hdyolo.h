@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 11
+#define HDY_ABI_VERSION 12
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -392,6 +392,67 @@ int hdy_augment_tiles_u8(const unsigned char* bank, long long tile_stride_bytes,
 int hdy_augment_boxes(const float* bank_boxes, const long long* bank_labels, const long long* offsets, int n, int M, const void* cells, int n_cells,
                       const int* crop, int B, int patch, int k, int img_size, float* out_boxes, long long* out_labels, float* out_img, int cap,
                       int* counts, int n_counts, int* overflow, void* stream);
+
+/* ---- instance masks through the device augmentation (csrc/augment_masks.hip) ----------------------------------------------------------
+ * Replaces what the reference's loader does to the masks of detection annotations (metayolo/datasets.py random_projective :329-337, the flips,
+ * the mosaic, the crop, target_to_tensors :482-494).  The reference warps polygons and resizes with cv2 (absent here, unpinned upstream), so
+ * the arithmetic is this library's own, stated here in full; tests/augment_mask_ref.py restates it over the whole canvas, bit for bit.  The
+ * reference's rules are kept: a masked object's box is the box of its warped mask, its candidate test takes 0.01 for 0.1, its target is the
+ * mask cropped to the (integer) box and resized bilinearly to 28 x 28, a mask of fewer than 25 pixels gives a zero target, an object without
+ * a mask keeps the corner box, the 0.1 test and a zero target.
+ *
+ * Instance map: instances uint16 [n][H][W], dense, beside the bank of hdy_augment_tiles_u8 (same n, H, W).  A pixel holds the index w of its
+ * owner among its tile's boxes (bank row offsets[t] + w) or 0xFFFF (background): one owner per pixel.  has_mask uint8 [M]: 1 for a bank row
+ * that owns at least one pixel.  Every pixel (px, py) of an object must lie in its box grown to pixel edges, floor(x1) <= px < ceil(x2) and
+ * alike in y (hd_yolo_amd.augment.TileBank validates it): hdy_augment_mask_extents scans only a canvas region derived from that box.  Cell
+ * table, crop, B, patch, k, img_size: those of the two calls above, and the same limits.  All three entry points are memory-safe for any table
+ * content (a source index outside [0, n), a crop offset out of range, offsets rows negative / decreasing / beyond M own nothing and read
+ * nothing; instance-map reads are bounds-checked like texel reads) and deterministic (no atomics, fixed reduction order).
+ *
+ * Membership: canvas pixel (u, v), integers in [0, patch)^2 in pre-flip canvas coordinates, belongs to the warped mask of object w of cell ci
+ * when, with sx, sy (and sw with the perspective flag) computed from Mi exactly as hdy_augment_tiles_u8 computes them,
+ *   qx = rint(32 sx), qy = rint(32 sy)  (|32 s| > 2^24 or NaN: not a member);  xn = (qx + 16) >> 5, yn = (qy + 16) >> 5 (nearest source pixel)
+ *   0 <= xn < W, 0 <= yn < H, the cell's source tile src is in [0, n), w < 0xFFFF and instances[src][yn][xn] == w.
+ * Image-space mask of (ci, w) at image pixel (ox, oy) of image b: X = ox + crop_x, Y = oy + crop_y; zero unless X / patch == c and Y / patch
+ * == r (the object's cell); else the membership of (u, v) = (X - c patch, Y - r patch) after transpose: swap(u, v); vflip: v = patch - 1 - v;
+ * hflip: u = patch - 1 - u (as the image kernel undoes them).  The image position of canvas pixel (u, v) is the inverse, all integers:
+ *   hflip: u = patch - 1 - u;  vflip: v = patch - 1 - v;  transpose: swap(u, v);  ox = u + c patch - crop_x, oy = v + r patch - crop_y.
+ *
+ * hdy_augment_mask_extents: a candidate is (cell ci, object w) with w < the box count of the cell's source tile (as hdy_augment_boxes counts
+ * it), w < pitch.  For every candidate one record of 8 int32 is written to ws[(ci * pitch + w) * 8 ..] (ws 16-byte aligned; ws_bytes >=
+ * n_cells * pitch * 32 else HDY_EINVAL; 1 <= pitch <= 65535, at least the bank's largest box count per tile):
+ *   [0] count: members over ALL canvas pixels of the cell   [1] umin [2] umax [3] vmin [4] vmax of the members (0 when count == 0)
+ *   [5] area_img: members whose image position lies in [0, img_size)^2   [6] [7] zero
+ * A candidate without has_mask (or with w = 0xFFFF) gets the all-zero record; entries that are no candidate are not written.  The kernel may
+ * scan less than the canvas — the forward-warped box grown to pixel edges, plus a margin — but the definition is the whole canvas.
+ *
+ * hdy_augment_boxes_masks: hdy_augment_boxes with, for a row with has_mask (and w < pitch), the canvas box (umin, vmin, umax + 1, vmax + 1) as
+ * floats from its record, or the zero box when count == 0, in place of the corner box, and 0.01 in place of 0.1 in the candidate test (w1, h1
+ * stay those of the source box).  Everything else — order, flips, offsets, the crop's filter, the clip, x1 < x2 - 10, / img_size, cap,
+ * overflow, counts, the 4096-cell limit — is that entry point's text; a row without a mask goes through it unchanged.  Additional outputs:
+ * out_ref int32 [cap][2] = (ci, w) per written row, total[0] = rows written = min(kept, cap).
+ *
+ * hdy_augment_mask_targets: out_masks fp32 [cap][28][28] (out_elems == cap * 784 else HDY_EINVAL; 16-byte aligned).  One workgroup per row; a
+ * row >= total[0] (read on the device: no host synchronisation) is not written.  A written row is zero when it has no mask, when area_img <
+ * 25, or when its pixel box has w < 1 or h < 1, the pixel box being x1 = rint(out_boxes x1 * img_size) and alike, clamped to [0, img_size],
+ * w = x2 - x1, h = y2 - y1 (a masked row's pixel box is integer: the division and the product move it by less than 1/16).  Otherwise, for
+ * destination (i, j), fp32, every operation rounded on its own:
+ *   fx = (j + 0.5) * (w / 28) - 0.5;  x0 = floor(fx), a = fx - x0;  x0 < 0: x0 = 0, a = 0;  x0 >= w - 1: x0 = w - 1, a = 0;  xb = min(x0 + 1, w - 1)
+ *   the same in y with fy, y0, b, yb (the half-pixel convention of cv2.INTER_LINEAR);  taps m00 = mask(x1 + x0, y1 + y0), m01 = mask(x1 + xb,
+ *   y1 + y0), m10 = mask(x1 + x0, y1 + yb), m11 = mask(x1 + xb, y1 + yb) of the image-space mask (0 or 1)
+ *   out = (m00 (1 - a) + m01 a) (1 - b) + (m10 (1 - a) + m11 a) b.
+ * Not implemented: polygon or RLE input, mask_order other than bilinear, keep_res > 0. */
+int hdy_augment_mask_extents(const uint16_t* instances, int n, int H, int W, const float* bank_boxes, const unsigned char* has_mask,
+                             const long long* offsets, int M, const void* cells, int n_cells, const int* crop, int B, int patch, int k, int img_size,
+                             void* ws, long long ws_bytes, int pitch, void* stream);
+int hdy_augment_boxes_masks(const float* bank_boxes, const long long* bank_labels, const unsigned char* has_mask, const long long* offsets, int n,
+                            int M, const void* cells, int n_cells, const int* crop, int B, int patch, int k, int img_size, const void* ws,
+                            long long ws_bytes, int pitch, float* out_boxes, long long* out_labels, float* out_img, int* out_ref, int cap,
+                            int* counts, int n_counts, int* overflow, int* total, void* stream);
+int hdy_augment_mask_targets(const uint16_t* instances, int n, int H, int W, const unsigned char* has_mask, const long long* offsets, int M,
+                             const void* cells, int n_cells, const int* crop, int B, int patch, int k, int img_size, const void* ws,
+                             long long ws_bytes, int pitch, const float* out_boxes, const int* out_ref, const int* total, int cap, float* out_masks,
+                             long long out_elems, void* stream);
 
 /* ---- detection scoring: AP matching for ragged batches and whole slides (csrc/score.hip) --------------------------------------------
  * Replaces the per-image work of APMeter.add and the matching half of APMeter.ap_per_class (metayolo/models/metrics.py:251-375: five

@@ -162,14 +162,17 @@ def train(hyp, opt, device):
     if with_masks:
         mk.update(nmin=4, nmax=24)                                     # every object carries a 28x28 mask target
     if opt.tile_bank:                                                  # 8-bit tiles + boxes, augmented on the device (metayolo/datasets.py DeviceTiles)
-        assert not with_masks, '--tile-bank carries detection boxes only: mask targets are not supported by the device augmentation'
         from hd_yolo_amd.augment import TileBank
         bank = TileBank.load(opt.tile_bank)
+        if with_masks and bank.instances is None:
+            raise SystemExit(f"--masks --tile-bank: {opt.tile_bank} has no 'instances' array (uint16 (n, H, W): per pixel the index of its object "
+                             'within its tile, 0xFFFF for background), so it carries no mask targets')
         assert bank.nc <= nc, f'--tile-bank holds labels up to {bank.nc}, the model has nc={nc}'
         aug = {k: getattr(opt, k) for k in ('degrees', 'translate', 'scale', 'shear', 'perspective', 'hsv_h', 'hsv_s', 'hsv_v', 'fliplr', 'flipud',
                                             'transpose', 'cval')}
         aug.update(k_mosaic=opt.k_mosaic, patch_size=opt.patch_size or imgsz, img_size=imgsz)
-        loader = DeviceTiles(bank, aug, batch_size, opt.steps_per_epoch, rank=max(RANK, 0), seed=opt.seed, device=device, task=task0)
+        loader = DeviceTiles(bank, aug, batch_size, opt.steps_per_epoch, rank=max(RANK, 0), seed=opt.seed, device=device, task=task0,
+                             masks=with_masks)
     else:
         loader = SyntheticTiles(batch_size, imgsz, nc, opt.steps_per_epoch, rank=max(RANK, 0), seed=opt.seed, device=device, **mk)
     val_loader = SyntheticTiles(batch_size, imgsz, nc, opt.val_batches, rank=0, seed=opt.seed + 99, device=device, task=task0)
@@ -284,7 +287,8 @@ def argument_parser():
     # reference ships no default for them (they come from its hyp yaml), so the defaults below are this project's: the YOLOv5 scratch values
     # where one exists, a 2 x 2 mosaic of img-size cells, a mid-grey border.
     p.add_argument('--tile-bank', default='', help='.npz tile bank (tiles uint8 (n,H,W,3), boxes float32 xyxy px, labels int64 1..nc, offsets int64 '
-                                                   '(n+1)): train on it with device-side augmentation instead of synthetic tiles')
+                                                   '(n+1); for --masks also instances uint16 (n,H,W)): train on it with device-side augmentation '
+                                                   'instead of synthetic tiles')
     p.add_argument('--k-mosaic', type=int, default=2, help='mosaic side k: every image is a random crop of k x k augmented cells')
     p.add_argument('--patch-size', type=int, default=0, help='side of a mosaic cell in pixels (0: img-size)')
     p.add_argument('--degrees', type=float, default=0.0)
