@@ -15,6 +15,7 @@ hot path.  Timing brackets exactly what the reference brackets (
 synchronisation on both sides because HIP launches are asynchronous.
 
     python evaluation.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--weights w.pt] [--slide 2048 [--u8] [--min-tissue 0.05] [--score] [--masks --label-map]]
+    (--score with --masks --label-map also scores the synthetic sets as segmentations: score_slide_masks, mask mAP@.5)
 """
 import argparse
 import os
@@ -320,8 +321,6 @@ def score_slide(result, truth, iouv=None, ignore=(-100, -1), info=None):
     order, and the results are un-permuted.  Returns APMeter.ap_per_class's stats dict plus 'match' (int32 per detection: the row of its
     truth, or -1), 'match_iou' (fp32), 'hit' (threshold bits) and 'live', device tensors in the given order.  `info` receives chunks_visited / chunks_total / workspace_bytes."""
     from hd_yolo_amd import ops
-    from metayolo.models.metrics import ap_curves
-    import numpy as np
     iouv = torch.linspace(0.5, 0.95, 10) if iouv is None else iouv
     if result['labels'].dim() != 1 or truth['labels'].dim() != 1:
         raise ValueError('score_slide: multi-label results must be flattened first (val_nuclei.flatten_onehot_objects)')
@@ -336,12 +335,44 @@ def score_slide(result, truth, iouv=None, ignore=(-100, -1), info=None):
     inv[op] = torch.arange(n, device=dev)
     hit, live, match, miou = hit[inv], live[inv], match[inv], miou[inv]
     match = torch.where(match >= 0, ot[match.clamp_min(0).to(torch.int64)].to(torch.int32), match) if m else match
+    stats = _slide_stats(hit, live, ps, pl, tl, iouv, ignore)
+    stats.update(match=match, match_iou=miou, hit=hit, live=live)
+    return stats
+
+
+def _slide_stats(hit, live, ps, pl, tl, iouv, ignore):
+    """APMeter.ap_per_class's stats dict from the device's per-detection hit bits and live flags (one copy of each compact array)"""
+    from metayolo.models.metrics import ap_curves
+    import numpy as np
     thr = np.asarray(iouv.tolist() if hasattr(iouv, 'tolist') else list(iouv), dtype=np.float32)
     bits, keep = hit.cpu().numpy().view(np.uint16), live.cpu().numpy().astype(bool)
     flags = ((bits[:, None] >> np.arange(len(thr), dtype=np.uint16)[None]) & 1).astype(bool)
-    stats = ap_curves(flags[keep], ps.cpu().numpy()[keep], pl.cpu().numpy().astype(np.int64)[keep], tl.cpu().numpy().astype(np.int64), thr,
-                      [int(v) for v in (ignore or ())])
-    stats.update(match=match, match_iou=miou, hit=hit, live=live)
+    return ap_curves(flags[keep], ps.cpu().numpy()[keep], pl.cpu().numpy().astype(np.int64)[keep], tl.cpu().numpy().astype(np.int64), thr,
+                     [int(v) for v in (ignore or ())])
+
+
+@torch.no_grad()
+def score_slide_masks(result, truth, iouv=None, ignore=(-100, -1)):
+    """Scores one task's whole-slide segmentation on mask IoU: `result` as inference_on_slide(..., compute_masks=True, label_map=True) returns it
+    ({'label_map' int32 (H, W) with -1 background and else the owning row, 'scores', 'labels'}) against the slide's annotation
+    ({'label_map' int32 (H, W) with negative background and else the object's row, 'labels'}), all device tensors.  Both sides are disjoint, so
+    the mask IoU of every overlapping pair comes from one streaming pass over the two maps (ops.label_overlap: no dense (n_true, n_pred, H * W)
+    product as in the reference's get_mask_ious) and the matching of APMeter from one more call (ops.mask_ap_match).  Returns score_slide's
+    stats dict ('match' is the row of the matched object or -1) plus 'pred_area', 'true_area' (int32 pixels per row) and 'pairs' ((n, 3) int64:
+    detection, object, shared pixels), device tensors, from which a caller can form Dice / PQ / AJI.  One device-to-host read before the
+    curves (the overlap status)."""
+    from hd_yolo_amd import ops
+    iouv = torch.linspace(0.5, 0.95, 10) if iouv is None else iouv
+    if result['labels'].dim() != 1 or truth['labels'].dim() != 1:
+        raise ValueError('score_slide_masks: multi-label results must be flattened first (val_nuclei.flatten_onehot_objects)')
+    if 'label_map' not in result or 'label_map' not in truth:
+        raise ValueError("score_slide_masks: both sides need a 'label_map' (inference_on_slide(..., compute_masks=True, label_map=True))")
+    ps, pl = result['scores'].detach().float().reshape(-1), result['labels'].detach()
+    tl = truth['labels'].detach().to(ps.device)
+    pairs, pa, ta = ops.label_overlap(result['label_map'], truth['label_map'].to(ps.device), len(ps), len(tl))
+    hit, live, match, miou = ops.mask_ap_match(pairs, pa, ta, ps, pl, tl, iouv, ignore=ignore)
+    stats = _slide_stats(hit, live, ps, pl, tl, iouv, ignore)
+    stats.update(match=match, match_iou=miou, hit=hit, live=live, pred_area=pa, true_area=ta, pairs=pairs)
     return stats
 
 
@@ -420,6 +451,22 @@ def main():
             torch.cuda.synchronize()
             print(f'score: {len(ps)} detections x {len(tl)} truths, mAP@.5 {float(st["ap"][:, 0].mean()):.4f}, chunk pairs visited / total '
                   f'{info["chunks_visited"]} / {info["chunks_total"]} ({info["chunks_visited"] / max(info["chunks_total"], 1):.4f}) in {(time.time() - t0) * 1e3:.1f} ms')
+            if opt.masks and opt.label_map:
+                # the same synthetic sets as segmentations: one fixed disc pasted into every box (no rasteriser of its own), detections in
+                # descending score order so that the best one owns a contested pixel
+                from hd_yolo_amd import ops
+                yy, xx = torch.meshgrid(torch.arange(28, device=device), torch.arange(28, device=device), indexing='ij')
+                disc = (((yy - 13.5) ** 2 + (xx - 13.5) ** 2) <= 13.5 ** 2).float()
+                order = torch.sort(ps, descending=True, stable=True)[1]
+                size = (opt.slide, opt.slide)
+                truth_map = ops.paste_label_map(disc.expand(len(tl), 28, 28), tb, size)
+                pred_map = ops.paste_label_map(disc.expand(len(ps), 28, 28), pb[order], size)
+                torch.cuda.synchronize()
+                t0 = time.time()
+                sm = score_slide_masks({'label_map': pred_map, 'scores': ps[order], 'labels': pl[order]}, {'label_map': truth_map, 'labels': tl})
+                torch.cuda.synchronize()
+                print(f'mask score: {len(ps)} detections x {len(tl)} truths on a {opt.slide} x {opt.slide} label map, {len(sm["pairs"])} overlapping pairs, '
+                      f'mask mAP@.5 {float(sm["ap"][:, 0].mean()):.4f} in {(time.time() - t0) * 1e3:.1f} ms')
 
 
 if __name__ == '__main__':

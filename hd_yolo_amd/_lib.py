@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HDY_LIB: load another build of the same ABI (kernel A/B experiments); it must still sit under csrc/build/
 LIB_PATH = os.path.join(_HERE, 'csrc', 'build', os.path.basename(os.environ.get('HDY_LIB', 'libhdyolo_hip.so')))
 
-ABI_VERSION = 12                  # = HDY_ABI_VERSION of the include/hdyolo.h that SIGNATURES below was written for (tests/test_abi.py holds the two together)
+ABI_VERSION = 13                  # = HDY_ABI_VERSION of the include/hdyolo.h that SIGNATURES below was written for (tests/test_abi.py holds the two together)
 F32, BF16 = 0, 1
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2      # status codes (include/hdyolo.h); positive = hipError_t
 PACK_FWD, PACK_DGRAD, PACK_STEM = 0, 1, 2
@@ -124,6 +124,10 @@ SIGNATURES = {
     'hdy_paste_masks': (_I, [_P, _I, _I, _I, _P, _P, _L, _I, _I, _P]),
     'hdy_paste_label_map': (_I, [_P, _I, _I, _I, _P, _F, _I, _I, _P, _L, _I, _I, _P]),
     'hdy_label_areas': (_I, [_P, _L, _P, _I, _P]),
+    'hdy_label_overlap_workspace_bytes': (_Z, [_L]),
+    'hdy_label_overlap': (_I, [_P, _P, _L, _L, _I, _P, _P, _I, _I, _P, _P, _P, _Z, _L, _P, _P]),
+    'hdy_mask_ap_match_workspace_bytes': (_Z, [_I, _I]),
+    'hdy_mask_ap_match': (_I, [_P, _Z, _L, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _F, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'hdy_roi_align_fwd': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _F, _I, _I, _I, _P, _I, _P]),
     'hdy_roi_align_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _F, _I, _I, _I, _I, _P]),
     'hdy_relu_bwd': (_I, [_P, _P, _P, _L, _I, _P]),

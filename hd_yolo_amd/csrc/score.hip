@@ -26,7 +26,7 @@
 // Workspace (hdy_ap_match_workspace_bytes, a function of the three counts alone; MINC = 64, the smallest chunk):
 //   header 64 B {chunk pairs visited u64, chunk pairs total u64} | blk_off int[B + 1] | chk_off int[B + 1]
 //   | chunk box float4[ceil(true_capacity / MINC) + B] | chunk flag int[same] | claim u64[true_capacity]
-#include "common.h"
+#include "ap_common.h"
 #include "hdyolo.h"
 
 namespace {
@@ -106,11 +106,7 @@ __device__ __forceinline__ bool finite4(const float4& b) {
     return fabsf(b.x) <= 3.4028234664e38f && fabsf(b.y) <= 3.4028234664e38f && fabsf(b.z) <= 3.4028234664e38f && fabsf(b.w) <= 3.4028234664e38f;
 }
 
-__device__ __forceinline__ bool ignored(const Args& a, long long label) {
-    bool ig = false;
-    for (int k = 0; k < a.n_ign; ++k) ig |= a.ign[k] == label;
-    return ig;
-}
+__device__ __forceinline__ bool ignored(const Args& a, long long label) { return ap_ignored(a.ign, a.n_ign, label); }
 
 // min / max of (x1, y1, x2, y2) and OR of a flag over the wave
 __device__ __forceinline__ void wave_box(float& x1, float& y1, float& x2, float& y2, int& flag) {
@@ -312,7 +308,7 @@ __global__ __launch_bounds__(PRED_BLOCK) void match_kernel(const Args a) {
         a.live[me.p] = touched ? 1 : 0;
         if (best >= 0) {
             const unsigned row = (unsigned)(a.prow ? a.prow[me.p] : me.p);
-            atomicMin(&a.claim[best], ((u64)desc_key(a.ps[me.p]) << 32) | row);
+            atomicMin(&a.claim[best], ap_claim_key(a.ps[me.p], row));
         }
     }
     if (threadIdx.x == 0 && visited) atomicAdd(&a.hdr->visited, (u64)visited);
@@ -324,22 +320,7 @@ __global__ __launch_bounds__(PRED_BLOCK) void resolve_kernel(const Args a) {
     const Mine me = locate(a);
     if (!me.active) return;
     const int p = me.p;
-    const int best = a.match[p];
-    const float iou = a.miou[p];
-    const bool touched = a.live[p] != 0;
-    bool matched = false;
-    if (best >= 0) {
-        const unsigned row = (unsigned)(a.prow ? a.prow[p] : p);
-        const u64 key = ((u64)desc_key(a.ps[p]) << 32) | row;
-        matched = a.claim[best] == key && a.pl[p] == a.tl[best];
-    }
-    unsigned bits = 0;
-    if (matched)
-        for (int j = 0; j < a.n_iou; ++j) bits |= (iou >= a.iouv[j] ? 1u : 0u) << j;
-    a.hit[p] = (unsigned short)bits;
-    a.live[p] = (touched && !matched) ? 0 : 1;
-    a.match[p] = matched ? best : -1;
-    a.miou[p] = matched ? iou : 0.f;
+    ap_resolve(p, (unsigned)(a.prow ? a.prow[p] : p), a.ps, a.pl, a.tl, a.claim, a.iouv, a.n_iou, a.hit, a.live, a.match, a.miou);
 }
 
 }  // namespace

@@ -1,7 +1,9 @@
 """Detection metrics for the validation entry point (reference: metayolo/models/metrics.py:19-84 ap_per_class,
 :86-110 compute_ap, :251-408 APMeter).  APMeter is host-side numpy and keeps the reference's matching rules and stats dictionary
 (pinned by tests/golden/apmeter.npz); DeviceAPMeter does the same matching on the device (csrc/score.hip) for batches and whole
-slides, and shares the curve arithmetic (ap_curves)."""
+slides, and shares the curve arithmetic (ap_curves).  Mask IoU: get_mask_ious defines the name the reference's APMeter.add calls without
+defining it (metrics.py:275; the function is utils_nucls.py:480-489), for the host meter's iou_type='masks'; on the device
+DeviceAPMeter.add_batch_masks scores label maps (csrc/mask_score.hip)."""
 import numpy as np
 import torch
 
@@ -96,6 +98,17 @@ def summarize_precision_recall(stats_list, labels_text):
     return out
 
 
+def get_mask_ious(a, b):
+    """Mask IoU of every pair, (len(a), len(b)) fp32: a, b (n, H, W) masks on the host.  The reference's utils_nucls.get_mask_ious (:480-489)
+    builds the dense (n_a, n_b, H * W) product; this is the same quotient inter / (sum(a + b) - inter + 1e-8) with the two sums taken as
+    one matrix product and two row sums.  For 0 / 1 masks below 2^24 pixels every sum is an exact integer in fp32 whatever its order, so
+    the result is bit-identical to the reference's (tests/golden/mask_ap.npz); soft masks agree to rounding."""
+    a, b = a.detach().float().cpu().flatten(1), b.detach().float().cpu().flatten(1)
+    inter = a @ b.T
+    union = (a.sum(1)[:, None] + b.sum(1)[None]) - inter + 1e-8
+    return inter / union
+
+
 def ap_curves(hit, scores, y_pred, y_true, iouv, ignore, eps=1e-16):
     """Precision / recall / AP curves from per-prediction hit flags: the second half of APMeter.ap_per_class, shared with DeviceAPMeter.
     hit (n, n_iou) bool, scores / y_pred (n,) of the predictions that stay in the curves, y_true (n_true,), ignore a list of labels."""
@@ -146,6 +159,7 @@ class APMeter:
     truths are removed from the precision/recall curves.  Returns the reference's stats dict:
     'labels', 'counts', 'px', 'py' (n_cls, 1000), 'ap' (n_cls, n_iou), 'p', 'r', 'f1' (n_cls, 1000).
     Host-side numpy with a dense IoU matrix per image: for tiles.  DeviceAPMeter computes the same on the device.
+    add(..., iou_type='masks') with dense 0 / 1 'masks' on both sides takes the IoU from get_mask_ious instead of the boxes.
     Tie rule: equal scores inside one image are ranked by torch.sort, whose order among ties is unspecified; DeviceAPMeter ranks the lower
     row first.  This is the one place the two meters may differ."""
 
@@ -177,13 +191,17 @@ class APMeter:
         return int(sum(len(v) for v in self._ious))
 
     def add(self, output, target, iou_type='boxes'):
-        if iou_type == 'masks' and 'masks' in output and 'masks' in target:
-            raise NotImplementedError('mask IoU: the reference calls get_mask_ious here (metrics.py:275), a function its metrics module neither defines nor imports')
         scores, order = torch.sort(output['scores'].detach().float().cpu(), descending=True)
-        boxes = output['boxes'].detach().float().cpu()[order]
         labels = output['labels'].detach().cpu()[order]
-        tboxes, tlabels = target['boxes'].detach().float().cpu(), target['labels'].detach().cpu()
-        iou = box_iou(boxes, tboxes).numpy() if len(boxes) and len(tboxes) else np.zeros((len(boxes), len(tboxes)), np.float32)
+        tlabels = target['labels'].detach().cpu()
+        n_pred, n_true = len(scores), len(tlabels)
+        if not (n_pred and n_true):
+            iou = np.zeros((n_pred, n_true), np.float32)
+        elif iou_type == 'masks' and 'masks' in output and 'masks' in target:
+            # dense 0 / 1 masks (n, H, W) or (n, 1, H, W) on both sides, as the reference intends (metrics.py:274-275)
+            iou = get_mask_ious(output['masks'].detach().cpu()[order], target['masks'].detach().cpu()).numpy()
+        else:
+            iou = box_iou(output['boxes'].detach().float().cpu()[order], target['boxes'].detach().float().cpu()).numpy()
         pi, ti = np.nonzero(iou >= self.iouv.min())
         v = iou[pi, ti]
         o = np.argsort(-v, kind='stable')
@@ -193,8 +211,8 @@ class APMeter:
         self._y_true.append(tlabels.numpy().astype(np.int64))
         self._y_pred.append(labels.numpy().astype(np.int64))
         self._scores.append(scores.numpy())
-        self.n_pred += len(boxes)
-        self.n_true += len(tboxes)
+        self.n_pred += n_pred
+        self.n_true += n_true
 
     def ap_per_class(self, iouv=None, ignore=(-100, -1), eps=1e-16):
         # thresholds compare in fp32, as with the torch.linspace the reference's caller passes (val_nuclei.py:56)
@@ -279,6 +297,44 @@ class DeviceAPMeter:
         true_off = i32([len(t['labels']) for t in targets], dev)
         hit, live, _, _ = ops.ap_match(boxes, scores, labels, pred_off, tboxes, tlabels, true_off, self.iouv, ignore=self.ignore, info=info)
         self._batches.append((scores.detach().float().reshape(-1), labels.detach().reshape(-1).to(torch.int64), hit, live, pred_off, tlabels, true_off))
+        self._host_cache = None
+
+    def add_batch_masks(self, outputs, targets, size, threshold=0.5, max_pairs=None):
+        """A batch scored on mask IoU (ops.label_overlap + ops.mask_ap_match, csrc/mask_score.hip).  `outputs`: per-image dicts with 'boxes',
+        'scores', 'labels' and 'masks' (R, 1, M, M), rows in descending score order as the model delivers them (the mask paste gives a pixel
+        to the lowest row that covers it); `targets`: per-image dicts with 'labels' and 'instances', an (H, W) = size map holding the index of
+        the object that owns each pixel (uint16 with 0xFFFF background, as the tile bank stores it, or int32 with negative background).  Per
+        image one ops.paste_label_map into its slice of a (B, H, W) map, then one overlap launch over the batch with per-image row bases and
+        one matching call.  Instances are disjoint on both sides by construction.  One device-to-host read per batch (the overlap status).
+        max_pairs sizes the overlap's pair table (ops.label_overlap; default: from the row counts), for batches whose instances fragment into
+        more overlapping pairs than that holds.  A 16-bit map is refused once the batch has more than 65535 truths (0xFFFF would be a row).
+        Results are stored as add_batch stores them."""
+        from ... import ops
+        if not len(outputs):
+            return
+        if len(targets) != len(outputs):
+            raise ValueError(f'DeviceAPMeter: {len(outputs)} images of predictions, {len(targets)} of truths')
+        if outputs[0]['labels'].dim() != 1:
+            raise ValueError('DeviceAPMeter: multi-label outputs must be flattened by the caller (val_nuclei.flatten_onehot_objects)')
+        H, W = int(size[0]), int(size[1])
+        dev = outputs[0]['scores'].device
+        i32 = lambda counts: torch.tensor(np.concatenate(([0], np.cumsum(counts))), dtype=torch.int32, device=dev)   # noqa: E731
+        pred_off, true_off = i32([len(o['scores']) for o in outputs]), i32([len(t['labels']) for t in targets])
+        n_true = int(sum(len(t['labels']) for t in targets))
+        pred_map = torch.empty((len(outputs), H, W), dtype=torch.int32, device=dev)
+        true_map = torch.empty((len(outputs), H, W), dtype=torch.int32, device=dev)
+        for i, (o, t) in enumerate(zip(outputs, targets)):
+            ops.paste_label_map(o['masks'], o['boxes'], (H, W), threshold=threshold, out=pred_map[i])
+            inst = t['instances']
+            if tuple(inst.shape) != (H, W):
+                raise ValueError(f"DeviceAPMeter: 'instances' of image {i} is {tuple(inst.shape)}, the canvas {(H, W)}")
+            true_map[i] = ops._label_map_i32('add_batch_masks', inst.to(dev), 'instances', n_true)
+        scores = torch.cat([o['scores'].detach().float().reshape(-1) for o in outputs])
+        labels = torch.cat([o['labels'].detach().reshape(-1).to(torch.int64) for o in outputs])
+        tlabels = torch.cat([t['labels'].detach().reshape(-1).to(torch.int64) for t in targets]).to(dev)
+        pairs, pa, ta = ops.label_overlap(pred_map, true_map, scores.numel(), tlabels.numel(), seg=(pred_off[:-1], true_off[:-1]), max_pairs=max_pairs)
+        hit, live, _, _ = ops.mask_ap_match(pairs, pa, ta, scores, labels, tlabels, self.iouv, ignore=self.ignore)
+        self._batches.append((scores, labels, hit, live, pred_off, tlabels, true_off))
         self._host_cache = None
 
     def _host(self):

@@ -1069,12 +1069,12 @@ AP_PRED_BLOCK, AP_TRUE_CHUNK = 256, 256      # HDY_AP_PRED_BLOCK / HDY_AP_TRUE_C
 AP_MAX_IOU, AP_MAX_IGNORE = 16, 4
 
 
-def _i32(t, name):
+def _i32(t, name, who='ap_match'):
     if t is None:
         return None
     require_gpu(t)
     if t.dtype != torch.int32:
-        raise _lib.HdyError(f'ap_match: {name} must be int32, got {t.dtype}')
+        raise _lib.HdyError(f'{who}: {name} must be int32, got {t.dtype}')
     return t.contiguous()
 
 
@@ -1161,16 +1161,20 @@ def paste_masks(masks, boxes, size, padding=1):
     return out
 
 
-def paste_label_map(masks, boxes, size, window=None, threshold=0.5, padding=1):
+def paste_label_map(masks, boxes, size, window=None, threshold=0.5, padding=1, out=None):
     """One int32 label map of the (H, W) = size canvas, or of its window (x0, y0, w, h) (hdy_paste_label_map): -1 = background, otherwise the
     lowest row whose pasted mask (as paste_masks computes it) is >= threshold at the pixel — rows in descending score order, as the slide NMS
-    leaves them, give every pixel to its best detection.  One launch for all rows, no host synchronisation; the map may pass 2^31 entries."""
+    leaves them, give every pixel to its best detection.  One launch for all rows, no host synchronisation; the map may pass 2^31 entries.
+    out: a contiguous int32 (h, w) tensor to draw into (a slice of a batch of maps) instead of a new one."""
     m, b, R, M = _paste_inputs('paste_label_map', masks, boxes, padding)
     H, W = int(size[0]), int(size[1])
     x0, y0, w, h = (0, 0, W, H) if window is None else (int(v) for v in window)
     if H < 1 or W < 1 or w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
         raise _lib.HdyError(f'paste_label_map: window {(x0, y0, w, h)} is not a non-empty part of the {H} x {W} canvas')
-    out = torch.empty((h, w), dtype=torch.int32, device=m.device)
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.int32, device=m.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (h, w) or not out.is_contiguous() or out.device != m.device:
+        raise _lib.HdyError(f'paste_label_map: out must be a contiguous int32 ({h}, {w}) tensor on {m.device}')
     _lib.call('hdy_paste_label_map', ptr(m) if R else None, R, M, int(padding), ptr(b) if R else None, float(threshold), x0, y0, out.data_ptr(),
               out.numel(), h, w, stream_ptr())
     return out
@@ -1187,6 +1191,127 @@ def label_areas(label_map, R):
     if R:
         _lib.call('hdy_label_areas', ptr(lm) if lm.numel() else None, lm.numel(), areas.data_ptr(), R, stream_ptr())
     return areas
+
+
+# ------------------------------------------------------------------------------------------ mask scoring (csrc/mask_score.hip)
+OVERLAP_MIN_SLOTS, OVERLAP_MAX_SLOTS = 64, 1 << 30      # HDY_OVERLAP_MAX_SLOTS (include/hdyolo.h)
+
+
+def _pow2_at_least(n, lo=OVERLAP_MIN_SLOTS):
+    s = lo
+    while s < n:
+        s <<= 1
+    return s
+
+
+def _label_map_i32(who, t, name, rows):
+    """an int32 label map as it is; the tile bank's 16-bit instance map (uint16, or the same bits as int16) widened, 0xFFFF staying 65535:
+    background only while the `rows` it is scored against (all segments together) do not pass 65535, so more rows are refused"""
+    require_gpu(t)
+    if t.dtype == torch.int32:
+        return t.contiguous()
+    if t.dtype in (torch.uint16, torch.int16) and rows > 0xFFFF:
+        raise _lib.HdyError(f'{who}: a 16-bit {name} marks background with 0xFFFF, which is a row once there are {rows} > 65535 of them: pass an '
+                            f'int32 map with negative background')
+    if t.dtype == torch.uint16:
+        return t.contiguous().view(torch.int16).to(torch.int32).bitwise_and_(0xFFFF)
+    if t.dtype == torch.int16:
+        return t.to(torch.int32).bitwise_and_(0xFFFF)
+    raise _lib.HdyError(f'{who}: {name} must be int32 or a 16-bit instance map, got {t.dtype}')
+
+
+def _overlap_table(slots, dev):
+    """keys uint64 [slots] | counts uint32 [slots] in one buffer (include/hdyolo.h): the buffer and its two views"""
+    buf = torch.empty((slots * 3 // 2,), dtype=torch.int64, device=dev)
+    return buf, buf[:slots], buf[slots:].view(torch.int32)
+
+
+def label_overlap(pred_map, true_map, n_pred, n_true, seg=None, max_pairs=None):
+    """The overlap of two label maps of equal shape as a sparse contingency table (hdy_label_overlap): returns (pairs, pred_area, true_area),
+    pairs an (n, 3) int64 device tensor of (p, t, shared entries > 0) sorted by (p, t), the areas int32 entry counts per row.  pred_map int32
+    (-1 background, as paste_label_map leaves it), true_map int32 or the tile bank's uint16 instance map; a label that is negative or not below
+    n_pred / n_true is background.  seg = (pred_base, true_base), int32 device tensors of n_seg entries: the maps are n_seg equal segments along
+    their first dimension (a batch of tile maps) and segment s's non-negative labels are shifted by the bases, so tile-local rows become rows of
+    the concatenated arrays.  max_pairs sizes the table (default: from n_pred + n_true; a power of two of at least twice the pairs is taken).
+    One read (the status pair), after which the table is compacted and sorted on the device; HdyError when the table was too small."""
+    who = 'label_overlap'
+    n_pred, n_true = int(n_pred), int(n_true)
+    if n_pred < 0 or n_true < 0:
+        raise _lib.HdyError(f'{who}: negative row count')
+    pm, tm = _label_map_i32(who, pred_map, 'pred_map', n_pred), _label_map_i32(who, true_map, 'true_map', n_true)
+    if pm.shape != tm.shape:
+        raise _lib.HdyError(f'{who}: the maps disagree in shape: {tuple(pm.shape)} and {tuple(tm.shape)}')
+    dev = pm.device
+    n_seg, seg_elems, pbase, tbase = 0, 0, None, None
+    if seg is not None:
+        pbase, tbase = _i32(seg[0], 'pred_base', who), _i32(seg[1], 'true_base', who)
+        n_seg = pbase.numel()
+        if n_seg < 1 or tbase.numel() != n_seg or pm.dim() < 1 or pm.shape[0] != n_seg:
+            raise _lib.HdyError(f'{who}: seg bases must both hold one entry per segment (the first dimension of the maps)')
+        seg_elems = pm.numel() // n_seg
+    slots = _pow2_at_least(2 * int(max_pairs) if max_pairs is not None else 4 * (n_pred + n_true), 8 if max_pairs is not None else OVERLAP_MIN_SLOTS)
+    if slots > OVERLAP_MAX_SLOTS:
+        raise _lib.HdyError(f'{who}: a table of {slots} slots passes {OVERLAP_MAX_SLOTS}')
+    buf, keys, counts = _overlap_table(slots, dev)
+    parea = torch.empty((n_pred,), dtype=torch.int32, device=dev)
+    tarea = torch.empty((n_true,), dtype=torch.int32, device=dev)
+    status = torch.empty((2,), dtype=torch.int32, device=dev)
+    _lib.call('hdy_label_overlap', ptr(pm) if pm.numel() else None, ptr(tm) if tm.numel() else None, pm.numel(), seg_elems, n_seg, ptr(pbase),
+              ptr(tbase), n_pred, n_true, ptr(parea) if n_pred else None, ptr(tarea) if n_true else None, buf.data_ptr(), _nbytes(buf), slots,
+              status.data_ptr(), stream_ptr())
+    n, overflow = status.tolist()                                   # the one read
+    if overflow:
+        raise _lib.HdyError(f'{who}: the pair table of {slots} slots is full ({overflow} inserts failed): pass a larger max_pairs')
+    skeys, order = torch.sort(keys)                                 # unused slots hold -1 and sort first
+    skeys, cnt = skeys[slots - n:], counts[order[slots - n:]]
+    pairs = torch.stack([skeys >> 32, skeys & 0xFFFFFFFF, cnt.to(torch.int64)], 1)
+    return pairs, parea, tarea
+
+
+def mask_ap_match(pairs, pred_area, true_area, pred_scores, pred_labels, true_labels, iouv, ignore=(-100, -1), pair_iou=0.5, pred_row=None,
+                  true_row=None):
+    """ops.ap_match with the IoU of instance masks (hdy_mask_ap_match): pairs / pred_area / true_area as label_overlap returns them, scores,
+    labels and the optional pred_row / true_row one per row of the concatenated arrays (rows of different images never share a pair, so there
+    are no offsets).  IoU = float(inter) / float(area_p + area_t - inter).  Returns hit (16 threshold bits in an int16), live (uint8), match
+    (int32 truth row or -1) and match_iou (fp32), one entry per prediction.  No host synchronisation."""
+    who = 'mask_ap_match'
+    require_gpu(pred_scores)
+    dev = pred_scores.device
+    ps = pred_scores.detach().float().reshape(-1).contiguous()
+    pl = pred_labels.detach().reshape(-1).to(torch.int64).contiguous()
+    tl = true_labels.detach().reshape(-1).to(torch.int64).contiguous().to(dev)
+    NP, NT = ps.numel(), tl.numel()
+    pa, ta = _i32(pred_area, 'pred_area', who), _i32(true_area, 'true_area', who)
+    if not (pl.numel() == NP == pa.numel() and ta.numel() == NT):
+        raise _lib.HdyError(f'{who}: scores, labels and areas disagree in length')
+    pred_row, true_row = _i32(pred_row, 'pred_row', who), _i32(true_row, 'true_row', who)
+    if (pred_row is not None and pred_row.numel() != NP) or (true_row is not None and true_row.numel() != NT):
+        raise _lib.HdyError(f'{who}: pred_row / true_row must have one entry per row')
+    require_gpu(pairs)
+    if pairs.dim() != 2 or pairs.shape[1] != 3 or pairs.dtype != torch.int64:
+        raise _lib.HdyError(f'{who}: pairs must be an (n, 3) int64 tensor, got {pairs.dtype} {tuple(pairs.shape)}')
+    n = pairs.shape[0]
+    slots = _pow2_at_least(n)
+    buf, keys, counts = _overlap_table(slots, dev)                  # the kernel walks every slot, so the compacted pairs are a table as they are
+    keys[:n] = (pairs[:, 0] << 32) | pairs[:, 1]
+    keys[n:] = -1
+    counts[:n] = pairs[:, 2].to(torch.int32)
+    counts[n:] = 0
+    thr = [float(v) for v in (iouv.tolist() if hasattr(iouv, 'tolist') else iouv)]
+    ign = [int(v) for v in (ignore or ())]
+    c_thr = (ctypes.c_float * max(1, len(thr)))(*thr)
+    c_ign = (ctypes.c_longlong * max(1, len(ign)))(*ign)
+    hit = torch.empty((NP,), dtype=torch.int16, device=dev)
+    live = torch.empty((NP,), dtype=torch.uint8, device=dev)
+    match = torch.empty((NP,), dtype=torch.int32, device=dev)
+    miou = torch.empty((NP,), dtype=torch.float32, device=dev)
+    wsb = _lib.query('hdy_mask_ap_match_workspace_bytes', NP, NT)
+    ws = torch.empty(((wsb + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    _lib.call('hdy_mask_ap_match', buf.data_ptr(), _nbytes(buf), slots, ptr(pa) if NP else None, ptr(ta) if NT else None, ptr(ps) if NP else None,
+              ptr(pl) if NP else None, ptr(pred_row), NP, ptr(tl) if NT else None, ptr(true_row), NT, c_thr, len(thr), float(pair_iou), c_ign,
+              len(ign), ptr(hit) if NP else None, ptr(live) if NP else None, ptr(match) if NP else None, ptr(miou) if NP else None, ws.data_ptr(),
+              _nbytes(ws), stream_ptr())
+    return hit, live, match, miou
 
 
 # ------------------------------------------------------------------------------------------ mask branch primitives (row f2)

@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 12
+#define HDY_ABI_VERSION 13
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -527,6 +527,49 @@ int hdy_paste_masks(const float* masks, int R, int M, int padding, const float* 
 int hdy_paste_label_map(const float* masks, int R, int M, int padding, const float* boxes, float threshold, int x0, int y0, int* map,
                         long long map_elems, int h, int w, void* stream);
 int hdy_label_areas(const int* map, long long map_elems, int* areas, int R, void* stream);
+
+/* ---- mask scoring: label-map overlap and the AP matching on mask IoU (csrc/mask_score.hip) ----------------------------------------------
+ * Replaces get_mask_ious (utils_nucls.py:480-489: a dense (n_true, n_pred, H * W) product of 0 / 1 float masks) and the mask branch of
+ * APMeter.add (metrics.py:270-275, which calls that name without defining it) for instances that are DISJOINT on each side: predictions as a
+ * label map (hdy_paste_label_map: -1 background, else the owning row) and truths as an instance map (the tile bank's uint16 map widened to
+ * int32, or a slide map).  Mask IoU is then a sparse contingency count between two integer images: one streaming pass, integer-exact.
+ *
+ * hdy_label_overlap: pred_map, true_map int32 [elems] (64-bit count: a slide map may pass 2^31 entries), each read exactly once.  With
+ * n_seg > 0 the maps are n_seg segments of seg_elems entries (elems = n_seg * seg_elems exactly; a batch of tile maps) and pred_base[s] /
+ * true_base[s] (int32 [n_seg], ON THE DEVICE) are added to the non-negative labels of segment s, so tile-local rows become rows of the
+ * concatenated arrays; n_seg = 0: one segment, no bases (both may be NULL).  A label that is negative, or outside [0, n_pred) / [0, n_true)
+ * after the base, is background: any map content is memory-safe, and 0xFFFF of a widened uint16 map needs no rewrite while n_true <= 65535.
+ *   pred_area[p] = entries whose prediction label is p; true_area[t] alike (int32, zeroed by the call);
+ *   for every (p, t) that share at least one entry, inter(p, t) = the number of shared entries, in one slot of `table`:
+ *     table = keys uint64 [slots] | counts uint32 [slots]; a used slot holds key = (p << 32 | t) and count = inter > 0, an unused one
+ *     key = ~0 and count = 0.  slots is a power of two <= HDY_OVERLAP_MAX_SLOTS; table_bytes >= hdy_label_overlap_workspace_bytes(slots)
+ *     (0 = slots invalid), 16-byte aligned.  The call initialises the table itself.  Which slot a pair occupies depends on arrival
+ *     order; the SET of (p, t, inter) does not (integer adds), and that set is the result.
+ *   status int32 [2] on the device = {pairs stored, inserts that found the table full}.  With status[1] != 0 the table is incomplete (areas
+ *   are still exact); nothing is ever written outside the table.  The caller reads status once, when it wants to.
+ *
+ * hdy_mask_ap_match: the five rules of hdy_ap_match above, word for word, for ONE set of rows (rows of different images never share a pair, so
+ * no offsets are needed), with rule 1's IoU taken from the table:
+ *   union = area_p + area_t - inter in int64;  iou = float(inter) / float(union), one IEEE division of the two conversions
+ * which is bit-identical to get_mask_ious on 0 / 1 fp32 masks while the counts stay below 2^24 (its "+ 1e-8" vanishes in fp32 once the union
+ * is >= 1); above that each conversion rounds once, to nearest.  Rule 2: highest IoU, tie lowest truth row; rule 3: highest score, tie lower
+ * prediction row; pred_row / true_row (int32, non-negative, distinct among rows that can meet; may be NULL) replace the positions.
+ * table / slots as hdy_label_overlap left them, pred_area / true_area its areas; pred_scores fp32, labels int64; iouv (n_iou in [1, 16]),
+ * pair_iou in (0, 1] and ignore (n_ignore in [0, 4]) are HOST values read before the call returns.  Outputs, one per prediction: hit (uint16
+ * bits), live (uint8), match (int32 truth row or -1), match_iou (fp32).  Slots whose rows are out of range are skipped: any table content is
+ * memory-safe.  workspace: 16-byte aligned, hdy_mask_ap_match_workspace_bytes(n_pred, n_true) (0 = a negative count), travels with its size.
+ * Both: no allocation, no synchronisation, everything on `stream`; outputs are a pure function of the inputs (integer adds and 64-bit atomic
+ * minima / maxima of distinct keys: no dependence on arrival order).  All argument checks are made before any launch: HDY_EINVAL + message. */
+#define HDY_OVERLAP_MAX_SLOTS (1LL << 30)
+size_t hdy_label_overlap_workspace_bytes(long long slots);
+int hdy_label_overlap(const int* pred_map, const int* true_map, long long elems, long long seg_elems, int n_seg, const int* pred_base,
+                      const int* true_base, int n_pred, int n_true, int* pred_area, int* true_area, void* table, size_t table_bytes,
+                      long long slots, int* status, void* stream);
+size_t hdy_mask_ap_match_workspace_bytes(int n_pred, int n_true);
+int hdy_mask_ap_match(const void* table, size_t table_bytes, long long slots, const int* pred_area, const int* true_area, const float* pred_scores,
+                      const long long* pred_labels, const int* pred_row, int n_pred, const long long* true_labels, const int* true_row, int n_true,
+                      const float* iouv, int n_iou, float pair_iou, const long long* ignore, int n_ignore, unsigned short* hit, unsigned char* live,
+                      int* match, float* match_iou, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- mask branch primitives ------------------------------------------------------------
  * hdy_roi_align_fwd/bwd replace torchvision.ops.roi_align as the reference calls it (metayolo/models/yolo_head.py:243 on ground
