@@ -160,8 +160,10 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
 
     slide, on the GPU: (3, H, W) float in 0..1, or the slide as readers deliver it — uint8 (H, W, 3) RGB or (H, W, 4) RGBA (alpha ignored)
     with interleaved pixels and any row stride, so a crop of a larger slide is a view.  The 8-bit slide is never converted as a whole:
-    tiles are gathered straight into the network's input buffer (pixel / 255, correctly rounded), and for single-label headers without
-    masks the detections stay on the device until the merge — one read of a device cursor per slide, none per batch.
+    tiles are gathered straight into the network's input buffer (pixel / 255, correctly rounded), and for single-label headers the
+    detections stay on the device until the merge — one read of a device cursor per slide, none per batch; with compute_masks each batch's
+    masks are made in compacted order beside the append (Detect.masks_device: one read of the batch's counts, which size the mask head's
+    launches) and joined once at the end (HDY_DEVICE_MASKS=0: the per-tile Python merge).
     min_tissue > 0 (8-bit slides only; not in the reference): tiles with fewer than min_tissue * tile * tile pixels that are not
     background are skipped, a pixel being background when min(R, G, B) >= background.  0.0 keeps every tile and launches nothing.
     label_map=True (with compute_masks, on a model with a mask branch; not in the reference, which pastes per image: val_nuclei.py:169-176):
@@ -255,25 +257,43 @@ def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_t
         origins = ops.slide_origins(table, dev) if len(table) else None
     n = len(table)
     headers = inner.headers
-    on_device = not any(h.multi_label for h in headers.values()) and not (compute_masks and any(getattr(h, 'nc_masks', 0) > 0 for h in headers.values()))
+    want_masks = bool(compute_masks) and any(getattr(h, 'nc_masks', 0) > 0 for h in headers.values())
+    # masks travel beside the append (Detect.masks_device, one compact tensor per batch); HDY_DEVICE_MASKS=0, several headers (the plan's mask
+    # branch belongs to an only header) or a slide without tiles keep the Python merge
+    dev_masks = want_masks and len(headers) == 1 and n > 0 and all(h.device_masks_on() for h in headers.values())
+    on_device = not any(h.multi_label for h in headers.values()) and (not want_masks or dev_masks)
     if on_device:
         # slide-wide arrays per task, tiles x max_det rows (an exact upper bound), and a device cursor: every batch appends behind it
-        acc = {}
+        acc, mask_parts = {}, {}
         for task_id, h in headers.items():
             cap = max(n, 1) * int(h.nms_params['max_det'])
             acc[task_id] = (torch.empty((cap, 4), dtype=torch.float32, device=dev), torch.empty((cap,), dtype=torch.float32, device=dev),
                             torch.empty((cap,), dtype=torch.int64, device=dev), torch.zeros((2,), dtype=torch.int32, device=dev))
         for i in range(0, n, batch_size):
             count = min(batch_size, n - i)                               # the last, smaller chunk runs at its own size
-            _, outputs = model.forward_tiles(slide, origins, i, count, (tile, tile), compute_masks=False, device_outputs=True)
-            for task_id, (boxes, scores, labels, n_keep) in outputs.items():
+            _, outputs = model.forward_tiles(slide, origins, i, count, (tile, tile), compute_masks=dev_masks, device_outputs=True)
+            for task_id, (boxes, scores, labels, n_keep, masks) in outputs.items():
                 ops.slide_append(boxes, scores, labels, n_keep, origins, i, *acc[task_id])
+                if masks is not None:                                    # the batch's compact masks, in the order the append wrote its rows
+                    mask_parts.setdefault(task_id, []).append(masks)
         merged = {}
         for task_id, (boxes, scores, labels, cursor) in acc.items():
             rows, overflow = cursor.tolist()                             # the one device-to-host read of the slide (per task)
             if overflow:
                 raise RuntimeError(f'inference_on_slide: the detections of task {task_id!r} passed the capacity of {len(scores)} rows')
             merged[task_id] = {'boxes': boxes[:rows], 'labels': labels[:rows], 'scores': scores[:rows]}
+            if dev_masks:
+                parts = mask_parts.get(task_id, [])
+                made = sum(len(m) for m in parts)
+                if made != rows:
+                    raise RuntimeError(f'inference_on_slide: task {task_id!r} has {rows} detections and {made} masks')
+                # keys as the Python merge leaves them on a slide without detections: zero-row masks with label_map (_zero_row_masks), none without
+                # (Detect.merge_outputs looks at the first tile); storage is what the batches produced, joined once
+                if parts:
+                    merged[task_id]['masks'] = torch.cat(parts)
+                elif label_map:
+                    M = headers[task_id].mask_output_size
+                    merged[task_id]['masks'] = boxes.new_zeros((0, 1, M, M), dtype=torch.float32)
     else:
         # multi-label rows and masks keep the Python merge; their tiles still come from the 8-bit slide
         per_task = {}

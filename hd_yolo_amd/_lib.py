@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HDY_LIB: load another build of the same ABI (kernel A/B experiments); it must still sit under csrc/build/
 LIB_PATH = os.path.join(_HERE, 'csrc', 'build', os.path.basename(os.environ.get('HDY_LIB', 'libhdyolo_hip.so')))
 
-ABI_VERSION = 13                  # = HDY_ABI_VERSION of the include/hdyolo.h that SIGNATURES below was written for (tests/test_abi.py holds the two together)
+ABI_VERSION = 14                  # = HDY_ABI_VERSION of the include/hdyolo.h that SIGNATURES below was written for (tests/test_abi.py holds the two together)
 F32, BF16 = 0, 1
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2      # status codes (include/hdyolo.h); positive = hipError_t
 PACK_FWD, PACK_DGRAD, PACK_STEM = 0, 1, 2
@@ -129,6 +129,8 @@ SIGNATURES = {
     'hdy_mask_ap_match_workspace_bytes': (_Z, [_I, _I]),
     'hdy_mask_ap_match': (_I, [_P, _Z, _L, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _F, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'hdy_roi_align_fwd': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _F, _I, _I, _I, _P, _I, _P]),
+    'hdy_roi_align_levels_fwd': (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    'hdy_mask_rows': (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _L, _P]),
     'hdy_roi_align_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _F, _I, _I, _I, _I, _P]),
     'hdy_relu_bwd': (_I, [_P, _P, _P, _L, _I, _P]),
     'hdy_cast_store': (_I, [_P, _P, _I, _L, _I, _I, _I, _P]),

@@ -6,6 +6,9 @@
 // row/column interpolates with itself.  Output is NHWC [R][P][P][C] so the head's convolutions consume it directly.
 // Forward: an HBM-bound gather, one lane per (roi, bin, 8- or 4-channel vector).  The backward accumulates into an fp32 image
 // (bf16 has no atomic add and rois overlap), privatised per roi in LDS; hdy_cast_store then writes the plan's gradient buffer.
+// Inference over a batch's detections: roi_align_levels_kernel does the same gather for every kept row of the padded NMS result from the level
+// that produced it, in compacted order (reference: multiscale_roi_align, yolo_head.py:279-299), and mask_rows_kernel picks each row's mask
+// channel behind the head (:346-351).
 #include "common.h"
 #include "hdyolo.h"
 
@@ -71,6 +74,32 @@ __device__ __forceinline__ RoiGeom roi_geom(const float* roi, float scale, int P
     return g;
 }
 
+// One output bin of one roi for one channel vector: the average of S x S bilinear samples (acc zeroed by the caller; `feat` is the roi's image).
+// Shared by the single-level and the multi-level kernel, so both give the same bits for the same roi.
+template <typename T>
+__device__ __forceinline__ void roi_bin(const T* __restrict__ feat, int ldf, int H, int W, const RoiGeom& g, int ph, int pw, int c0, int S,
+                                        float* acc) {
+    constexpr int VE = RT<T>::VE;
+    for (int iy = 0; iy < S; ++iy) {
+        const float y = g.y0 + (float)ph * g.bin_h + ((float)iy + 0.5f) * g.bin_h / (float)S;
+        for (int ix = 0; ix < S; ++ix) {
+            const float x = g.x0 + (float)pw * g.bin_w + ((float)ix + 0.5f) * g.bin_w / (float)S;
+            const Sample s = sample_at(y, x, H, W);
+            if (!s.ok) continue;
+            float a[VE], b[VE], c[VE], d[VE];
+            ld_vec<T>(feat + ((size_t)s.y0 * W + s.x0) * ldf + c0, a);
+            ld_vec<T>(feat + ((size_t)s.y0 * W + s.x1) * ldf + c0, b);
+            ld_vec<T>(feat + ((size_t)s.y1 * W + s.x0) * ldf + c0, c);
+            ld_vec<T>(feat + ((size_t)s.y1 * W + s.x1) * ldf + c0, d);
+#pragma unroll
+            for (int i = 0; i < VE; ++i) acc[i] += s.w00 * a[i] + s.w01 * b[i] + s.w10 * c[i] + s.w11 * d[i];
+        }
+    }
+    const float inv = 1.0f / (float)(S * S);
+#pragma unroll
+    for (int i = 0; i < VE; ++i) acc[i] *= inv;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void roi_align_kernel(const T* __restrict__ feat, int ldf, int B, int H, int W, int C, const float* __restrict__ rois,
                                                         int R, float scale, int P, int S, int aligned, T* __restrict__ out) {
@@ -88,28 +117,101 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const T* __restrict__ fe
     float acc[VE];
 #pragma unroll
     for (int i = 0; i < VE; ++i) acc[i] = 0.f;
-    if (g.b >= 0 && g.b < B) {
-        for (int iy = 0; iy < S; ++iy) {
-            const float y = g.y0 + (float)ph * g.bin_h + ((float)iy + 0.5f) * g.bin_h / (float)S;
-            for (int ix = 0; ix < S; ++ix) {
-                const float x = g.x0 + (float)pw * g.bin_w + ((float)ix + 0.5f) * g.bin_w / (float)S;
-                const Sample s = sample_at(y, x, H, W);
-                if (!s.ok) continue;
-                const size_t base = (size_t)g.b * H * W;
-                float a[VE], b[VE], c[VE], d[VE];
-                ld_vec<T>(feat + (base + (size_t)s.y0 * W + s.x0) * ldf + vc * VE, a);
-                ld_vec<T>(feat + (base + (size_t)s.y0 * W + s.x1) * ldf + vc * VE, b);
-                ld_vec<T>(feat + (base + (size_t)s.y1 * W + s.x0) * ldf + vc * VE, c);
-                ld_vec<T>(feat + (base + (size_t)s.y1 * W + s.x1) * ldf + vc * VE, d);
+    if (g.b >= 0 && g.b < B) roi_bin<T>(feat + (size_t)g.b * H * W * ldf, ldf, H, W, g, ph, pw, vc * VE, S, acc);
+    st_vec<T>(out + (((size_t)r * P + ph) * P + pw) * C + vc * VE, acc);
+}
+
+// Multi-level form over the padded NMS rows of a batch (Detect.masks_device): one lane per (compacted row, bin, channel vector).  Every
+// workgroup rebuilds the prefix of n_keep in LDS (B <= 1024 counts, a scan over 256 partial sums), a lane finds its image by bisection, its
+// padded row is b * max_det + (row - prefix[b]), and the row's level picks one of the by-value level records.  Rows at or behind
+// min(out_rows, SUM n_keep) are not written; padded rows >= n_keep[b] are never read.  No atomics.
+constexpr int LEVELS_MAX = 8;
+constexpr int LEVELS_MAX_B = 1024;
+struct RoiLevels { hdy_roi_level lv[LEVELS_MAX]; };
+
+template <typename T>
+__global__ __launch_bounds__(256) void roi_align_levels_kernel(RoiLevels L, int nl, int C, const float* __restrict__ boxes, const float* __restrict__ level,
+                                                               int nex, const int* __restrict__ n_keep, int B, int max_det, int P, int S, int aligned,
+                                                               T* __restrict__ out, int out_rows) {
+    constexpr int VE = RT<T>::VE;
+    __shared__ int pre[LEVELS_MAX_B + 1];            // pre[b] = rows of the images before b
+    __shared__ int part[256];
+    {
+        const int t = threadIdx.x;
+        int n4[4], s = 0;
 #pragma unroll
-                for (int i = 0; i < VE; ++i) acc[i] += s.w00 * a[i] + s.w01 * b[i] + s.w10 * c[i] + s.w11 * d[i];
-            }
+        for (int i = 0; i < 4; ++i) {
+            const int b = 4 * t + i;
+            const int n = b < B ? n_keep[b] : 0;
+            n4[i] = n < 0 ? 0 : (n > max_det ? max_det : n);
+            s += n4[i];
         }
-        const float inv = 1.0f / (float)(S * S);
+        part[t] = s;
+        __syncthreads();
+        const int nt = (B + 3) >> 2;                // threads that hold counts; the partial sums behind them are never used
+        for (int off = 1; off < nt; off <<= 1) {    // inclusive scan of the partial sums
+            const int v = t >= off ? part[t - off] : 0;
+            __syncthreads();
+            part[t] += v;
+            __syncthreads();
+        }
+        int run = part[t] - s;
+        if (t == 0) pre[0] = 0;
 #pragma unroll
-        for (int i = 0; i < VE; ++i) acc[i] *= inv;
+        for (int i = 0; i < 4; ++i) {
+            run += n4[i];
+            if (4 * t + i < B) pre[4 * t + i + 1] = run;
+        }
+        __syncthreads();
+    }
+    const int total = pre[B];
+    const int rows = total < out_rows ? total : out_rows;
+    const int VC = C / VE;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)rows * P * P * VC) return;
+    const int vc = (int)(idx % VC);
+    long long q = idx / VC;
+    const int pw = (int)(q % P);
+    q /= P;
+    const int ph = (int)(q % P);
+    const int r = (int)(q / P);
+    int lo = 0, hi = B - 1;                          // the image b with pre[b] <= r < pre[b + 1]
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pre[mid + 1] <= r) lo = mid + 1;
+        else hi = mid;
+    }
+    const size_t src = (size_t)lo * max_det + (r - pre[lo]);
+    const float lf = level[src * nex];
+    const int l = (lf > -1.0f && lf < (float)nl) ? (int)lf : -1;       // NaN and infinities fail the comparison
+    float acc[VE];
+#pragma unroll
+    for (int i = 0; i < VE; ++i) acc[i] = 0.f;
+    if (l >= 0) {
+        const T* feat = nullptr;
+        int H = 1, W = 1, ldf = 0;
+        float scale = 0.f;
+#pragma unroll
+        for (int k = 0; k < LEVELS_MAX; ++k)         // a select chain: a lane-dependent index into the by-value records would go through scratch
+            if (k == l) { feat = (const T*)L.lv[k].feat; H = L.lv[k].H; W = L.lv[k].W; ldf = L.lv[k].ldf; scale = L.lv[k].spatial_scale; }
+        const f32x4 bx = *(const f32x4*)(boxes + src * 4);
+        const float roi[5] = {(float)lo, bx[0], bx[1], bx[2], bx[3]};
+        const RoiGeom g = roi_geom(roi, scale, P, aligned);
+        roi_bin<T>(feat + (size_t)lo * H * W * ldf, ldf, H, W, g, ph, pw, vc * VE, S, acc);
     }
     st_vec<T>(out + (((size_t)r * P + ph) * P + pw) * C + vc * VE, acc);
+}
+
+// out[r][y][x] = vals[r][y][x][mask_indices[max(labels[r], 0)]], zeros for a negative or out-of-range index (Detect.attach_masks' channel choice)
+__global__ __launch_bounds__(256) void mask_rows_kernel(const float* __restrict__ vals, int ldv, int K, const long long* __restrict__ labels,
+                                                        const int* __restrict__ mask_indices, int n_idx, long long n, int MM, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long r = i / MM;
+    long long lab = labels[r];
+    lab = lab < 0 ? 0 : lab;
+    const int idx = lab < n_idx ? mask_indices[lab] : -1;
+    out[i] = (idx >= 0 && idx < K) ? vals[(size_t)i * ldv + idx] : 0.f;
 }
 
 // Backward, privatised per roi and WITHOUT scatter: the bilinear weights of a sample factor into a row weight and a column weight, and
@@ -259,7 +361,61 @@ int hdy_roi_align_fwd(const void* feat, int ldf, int B, int H, int W, int C, con
     else
         hipLaunchKernelGGL(roi_align_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)feat, ldf, B, H, W, C, rois, R,
                            spatial_scale, P, sampling_ratio, aligned, (float*)out);
+    hdy_note_dispatch("roi_align");
     HDY_LAUNCH_CHECK("roi_align_fwd");
+    return HDY_OK;
+}
+
+int hdy_roi_align_levels_fwd(const hdy_roi_level* levels, int nl, int C, const float* boxes, const float* level, int nex, const int* n_keep, int B,
+                             int max_det, int P, int sampling_ratio, int aligned, void* out, int out_rows, int dtype, void* stream) {
+    HDY_ARG(levels && boxes && level && n_keep && out, "roi_align_levels_fwd: null pointer");
+    HDY_ARG(nl >= 1 && nl <= LEVELS_MAX, "roi_align_levels_fwd: %d levels (1 .. %d)", nl, LEVELS_MAX);
+    HDY_ARG(B >= 1 && B <= LEVELS_MAX_B, "roi_align_levels_fwd: batch of %d images (1 .. %d)", B, LEVELS_MAX_B);
+    HDY_ARG(dtype == HDY_BF16 || dtype == HDY_F32, "roi_align_levels_fwd: dtype %d", dtype);
+    const int VE = dtype == HDY_BF16 ? 8 : 4;
+    HDY_ARG(C > 0 && C % VE == 0, "roi_align_levels_fwd: C = %d is not a multiple of the %d-channel vector", C, VE);
+    HDY_ARG(P >= 1 && max_det >= 1 && out_rows >= 0 && nex >= 1 && sampling_ratio >= 1, "roi_align_levels_fwd: bad sizes (P %d, max_det %d, out_rows %d, nex %d, sampling_ratio %d)",
+            P, max_det, out_rows, nex, sampling_ratio);
+    HDY_ARG(((((uintptr_t)out) | ((uintptr_t)boxes)) & 15) == 0, "roi_align_levels_fwd: out / boxes are not 16-byte aligned");
+    RoiLevels L;
+    for (int l = 0; l < LEVELS_MAX; ++l) {
+        if (l < nl) {
+            L.lv[l] = levels[l];
+            HDY_ARG(L.lv[l].feat && L.lv[l].H > 0 && L.lv[l].W > 0 && L.lv[l].ldf >= C && ROI_ARGS_OK(C, L.lv[l].ldf, VE, L.lv[l].feat),
+                    "roi_align_levels_fwd: level %d: null / misaligned features, bad size or channel pitch", l);
+        } else {
+            L.lv[l] = hdy_roi_level{nullptr, 1, 1, 0, 0.f};
+        }
+    }
+    if (out_rows == 0) return HDY_OK;
+    const long long n = (long long)out_rows * P * P * (C / VE);
+    HDY_ARG((n + 255) / 256 <= 0x7fffffffLL, "roi_align_levels_fwd: %d rows are more than one launch covers", out_rows);
+    const int grid = (int)((n + 255) / 256);
+    if (dtype == HDY_BF16)
+        hipLaunchKernelGGL(roi_align_levels_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, L, nl, C, boxes, level, nex, n_keep, B, max_det,
+                           P, sampling_ratio, aligned, (bf16_t*)out, out_rows);
+    else
+        hipLaunchKernelGGL(roi_align_levels_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, L, nl, C, boxes, level, nex, n_keep, B, max_det,
+                           P, sampling_ratio, aligned, (float*)out, out_rows);
+    hdy_note_dispatch("roi_align_levels");
+    HDY_LAUNCH_CHECK("roi_align_levels_fwd");
+    return HDY_OK;
+}
+
+int hdy_mask_rows(const float* vals, int ldv, int K, const long long* labels, const int* mask_indices, const int* mask_indices_host, int n_idx, int R,
+                  int M, float* out, long long out_elems, void* stream) {
+    HDY_ARG(vals && labels && mask_indices && out, "mask_rows: null pointer");
+    HDY_ARG(K >= 1 && ldv >= K && n_idx >= 1 && R >= 0 && M >= 1, "mask_rows: bad sizes (K %d, ldv %d, n_idx %d, R %d, M %d)", K, ldv, n_idx, R, M);
+    HDY_ARG(out_elems == (long long)R * M * M, "mask_rows: out holds %lld elements, the call writes %lld", out_elems, (long long)R * M * M);
+    if (mask_indices_host)
+        for (int i = 0; i < n_idx; ++i) HDY_ARG(mask_indices_host[i] < K, "mask_rows: mask_indices[%d] = %d with %d mask channels", i, mask_indices_host[i], K);
+    if (R == 0) return HDY_OK;
+    const long long n = out_elems;
+    HDY_ARG((n + 255) / 256 <= 0x7fffffffLL, "mask_rows: %d rows are more than one launch covers", R);
+    hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vals, ldv, K, labels, mask_indices, n_idx, n,
+                       M * M, out);
+    hdy_note_dispatch("mask_rows");
+    HDY_LAUNCH_CHECK("mask_rows");
     return HDY_OK;
 }
 

@@ -244,7 +244,7 @@ class DeviceAPMeter:
     """APMeter with the matching on the device (ops.ap_match, csrc/score.hip): no pair list, no sort, no dense IoU matrix on the host.
 
     add_batch(outputs, targets): `outputs` is what Model.forward delivers for one task of a batch, a list of per-image dicts
-    {'boxes', 'scores', 'labels'} of device tensors, or the compacted (boxes, scores, labels, n_keep) tuple of device_outputs=True;
+    {'boxes', 'scores', 'labels'} of device tensors, or the compacted (boxes, scores, labels, n_keep[, masks]) tuple of device_outputs=True;
     `targets` a list of per-image dicts {'boxes', 'labels'}.  The batch is concatenated on the device, matched in one call, and its result
     tensors stay on the device: no device-to-host read per image or per batch.  add(output, target) is a batch of one.
     ap_per_class() copies the compact arrays (scores, labels, hit bits, live flags) to the host once and returns APMeter's stats dict through
@@ -276,7 +276,7 @@ class DeviceAPMeter:
         from ... import ops
         i32 = lambda counts, dev: torch.tensor(np.concatenate(([0], np.cumsum(counts))), dtype=torch.int32, device=dev)   # noqa: E731
         if isinstance(outputs, tuple):
-            boxes, scores, labels, n_keep = outputs
+            boxes, scores, labels, n_keep = outputs[:4]          # (a fifth element: the batch's compact masks, not scored here)
             dev = boxes.device
             pred_off = torch.zeros((n_keep.numel() + 1,), dtype=torch.int32, device=dev)
             pred_off[1:] = torch.cumsum(n_keep.to(torch.int32), 0)

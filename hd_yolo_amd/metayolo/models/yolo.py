@@ -85,8 +85,11 @@ class Model(nn.Module):
         """Eval forward of tiles [first, first + count) of an 8-bit slide that lives on the device (uint8 (H, W, 3 | 4), see ops.slide_u8;
         origins: int32 [n][2] device table of (x0, y0), ops.slide_origins; tile = (th, tw)): the batch is gathered straight into the plan's
         input buffer, on the SAME plan a float (count, 3, th, tw) tensor would run.  Returns what forward returns, or, with device_outputs,
-        (losses, {task: (boxes, scores, labels, n_keep)}) — the batch's compacted detections and the device `n_keep`, no synchronisation
-        (Detect.compute_outputs_device).  No reference counterpart: the reference's loaders hand float tiles to Model.forward."""
+        (losses, {task: (boxes, scores, labels, n_keep, masks)}) — the batch's compacted detections and the device `n_keep`
+        (Detect.compute_outputs_device).  masks is None and nothing is synchronised unless compute_masks is set and the task's header has a
+        mask branch: then it is the batch's compact (total, 1, M, M) masks (None for a batch without detections), for one read of n_keep per
+        batch in place of the 1 + nl synchronisations of the per-image form.  No reference counterpart: the reference's loaders hand float
+        tiles to Model.forward."""
         if self.training:
             raise RuntimeError('Model.forward_tiles is eval-only: training batches come from a loader through Model.forward')
         dtype = _engine.compute_dtype(self, slide)
@@ -96,7 +99,9 @@ class Model(nn.Module):
         outputs, at = {}, 0
         for task_id, header in self.headers.items():
             nl = len(header.m)
-            outputs[task_id] = header.compute_outputs_device(header.decode_all(dets[at:at + nl]))
+            # (the mask branch of a plan belongs to its only header, as in _forward_headers)
+            mask_ctx = (self._eng(), plan, dtype) if compute_masks and getattr(header, 'nc_masks', 0) > 0 and len(self.headers) == 1 else None
+            outputs[task_id] = header.compute_outputs_device(header.decode_all(dets[at:at + nl]), mask_ctx)
             at += nl
         return {}, outputs
 

@@ -239,15 +239,61 @@ class Detect(nn.Module):
         results = [{'boxes': b, 'scores': s, 'labels': l} for b, s, l in
                    zip(boxes_c[:total].split(n_keep), scores_c[:total].split(n_keep), labels_c[:total].split(n_keep))]
         if compute_masks and sum(n_keep) > 0 and not self.multi_label:
-            self.attach_masks(results, res, n_keep, features)
+            if self.device_masks_on():
+                # one multi-level roi_align launch, the head, one channel-choice launch; an image without detections gets no 'masks' key
+                for r, m in zip(results, self.masks_device(res, labels_c, total, features).split(n_keep)):
+                    if len(m):
+                        r['masks'] = m
+            else:
+                self.attach_masks(results, res, n_keep, features)
         return results
 
-    def compute_outputs_device(self, flat):
-        """compute_outputs without its synchronisation: (boxes (bs * max_det, 4), scores, labels, n_keep int32 (bs,)) on the device, the
-        batch's detections compacted (image b's rows start at n_keep[0] + .. + n_keep[b - 1]; rows past the total are scratch).  For callers
-        that keep going on the device (the whole-slide append, ops.slide_append)."""
+    @staticmethod
+    def device_masks_on():
+        """HDY_DEVICE_MASKS=0 keeps attach_masks (per-level nonzero / roi_align / cat and a per-image channel pick) as the second implementation"""
+        import os
+        return os.environ.get('HDY_DEVICE_MASKS', '1') != '0'
+
+    def compute_outputs_device(self, flat, mask_ctx=None):
+        """compute_outputs for callers that keep going on the device (the whole-slide append, ops.slide_append): (boxes (bs * max_det, 4), scores,
+        labels, n_keep int32 (bs,), masks), the batch's detections compacted (image b's rows start at n_keep[0] + .. + n_keep[b - 1]; rows past
+        the total are scratch).  Without mask_ctx (or on a head without a mask branch, or a multi-label one) masks is None and nothing is
+        synchronised.  With mask_ctx = (engine, plan, dtype), masks is the (total, 1, M, M) fp32 tensor of the batch in the same compacted order
+        (None when the batch has no detection), at the price of ONE read of n_keep per batch: the mask head's launches are sized by the row
+        count on the host.  That read replaces the 1 + nl synchronisations of compute_outputs + attach_masks (n_keep, then one nonzero() per
+        level)."""
         res, boxes_c, scores_c, labels_c = self._outputs_device(flat)
-        return boxes_c, scores_c, labels_c, res['n_keep']
+        masks = None
+        if mask_ctx is not None and self.nc_masks > 0 and not self.multi_label:
+            total = sum(res['n_keep'].tolist())            # the one D2H sync of the batch
+            if total > 0:
+                masks = self.masks_device(res, labels_c, total, mask_ctx)
+        return boxes_c, scores_c, labels_c, res['n_keep'], masks
+
+    def masks_device(self, res, labels_c, total, mask_ctx):
+        """attach_masks for the whole batch on three device steps: ops.roi_align_levels over the padded NMS rows (each detection from the level
+        that produced it, compacted order) -> Mask R-CNN head -> sigmoid -> ops.mask_rows (the channel of the detection's mask label, zeros for
+        a negative one).  res: nms_batched's result, labels_c: det_outputs' compacted labels, total = sum(n_keep) on the host.
+        -> (total, 1, M, M) fp32, bit-identical to attach_masks' rows (reference: yolo_head.py:320-353, :279-299)."""
+        from ...maskhead import MaskHeadRun
+        engine, plan, dtype = mask_ctx
+        dev = res['boxes'].device
+        feats = plan.mask_features()
+        scales = [1.0 / self._stride_cached(l) for l in range(self.nl)]
+        x = _ops.roi_align_levels(feats, scales, res, total, self.mask_output_size // 2, 2, self.aligned)
+        logits = MaskHeadRun(self.seg_h, dtype).forward(x)                                            # (R, 28, 28, nc_masks) fp32
+        table, host = self._mask_index_table(dev)
+        return _ops.mask_rows(logits.sigmoid(), labels_c[:total], table, host)
+
+    def _mask_index_table(self, dev):
+        """self.mask_indices as an int32 device table and a host list, made once per device and buffer version (the .tolist() is a sync)"""
+        buf = self.mask_indices
+        key = (str(dev), id(buf), buf._version)
+        cache = self.__dict__.setdefault('_mask_idx', {})
+        if cache.get('key') != key:
+            host = [int(v) for v in buf.tolist()]
+            cache['key'], cache['t'] = key, (torch.tensor(host, dtype=torch.int32, device=dev), host)
+        return cache['t']
 
     def _outputs_device(self, flat):
         conf = self.nms_params['conf_thres']

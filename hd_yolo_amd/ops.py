@@ -1326,6 +1326,65 @@ def roi_align(feat, rois, spatial_scale, P, sampling_ratio=2, aligned=False):
     return out
 
 
+class _RoiLevel(ctypes.Structure):
+    """hdy_roi_level (include/hdyolo.h)"""
+    _fields_ = [('feat', ctypes.c_void_p), ('H', ctypes.c_int), ('W', ctypes.c_int), ('ldf', ctypes.c_int), ('spatial_scale', ctypes.c_float)]
+
+
+ROI_LEVELS_MAX, ROI_LEVELS_MAX_B = 8, 1024           # hdy_roi_align_levels_fwd (include/hdyolo.h)
+
+
+def roi_align_levels(feats, scales, res, out_rows, P, sampling_ratio=2, aligned=False, out=None):
+    """Multi-level roi_align over a batch's detections in one launch (hdy_roi_align_levels_fwd).  feats: per level an NHWC (B, H, W, C) map
+    (possibly a pitched view; one C and dtype), scales: per level spatial_scale; res: nms_batched's result — padded boxes (B, max_det, 4), the
+    level id as column 0 of 'extra', the device n_keep.  -> (out_rows, P, P, C) NHWC in compacted order (image b's rows at
+    n_keep[0] + .. + n_keep[b - 1]); out_rows is a host value, normally sum(n_keep); rows behind the device total are left unwritten.
+    out: a contiguous (out_rows, P, P, C) tensor of the maps' dtype to write into instead of a new one."""
+    boxes, extra, n_keep = res['boxes'], res['extra'], res['n_keep']
+    require_gpu(boxes)
+    nl = len(feats)
+    assert nl == len(scales) and 1 <= nl <= ROI_LEVELS_MAX, f'{nl} levels, {len(scales)} scales (1 .. {ROI_LEVELS_MAX} levels)'
+    B, max_det = boxes.shape[:2]
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.shape[2] == 4
+    assert extra.dtype == torch.float32 and extra.dim() == 3 and tuple(extra.shape[:2]) == (B, max_det) and extra.shape[2] >= 1 \
+        and extra.stride(2) == 1 and extra.stride(0) == max_det * extra.stride(1), f'level column of the NMS result: {extra.shape} {extra.stride()}'
+    assert n_keep.dtype == torch.int32 and n_keep.is_contiguous() and n_keep.numel() == B and 1 <= B <= ROI_LEVELS_MAX_B
+    dtype, C = feats[0].dtype, feats[0].shape[3]
+    table = (_RoiLevel * nl)()
+    for l, f in enumerate(feats):
+        fp, n, h, w, c, ldf = nhwc(f)
+        assert f.dtype == dtype and c == C and n >= B and f.device == boxes.device, f'level {l}: {f.dtype} {tuple(f.shape)} for a batch of {B}, C = {C}'
+        table[l] = _RoiLevel(fp, h, w, ldf, float(scales[l]))
+    if out is None:
+        out = torch.empty((int(out_rows), P, P, C), dtype=dtype, device=boxes.device)
+    else:
+        assert out.dtype == dtype and tuple(out.shape) == (int(out_rows), P, P, C) and out.is_contiguous() and out.device == boxes.device
+    _lib.call('hdy_roi_align_levels_fwd', ctypes.cast(table, ctypes.c_void_p), nl, C, boxes.data_ptr(), extra.data_ptr(), extra.stride(1),
+              n_keep.data_ptr(), B, max_det, P, sampling_ratio, int(aligned), out.data_ptr(), int(out_rows), dcode(dtype), stream_ptr())
+    return out
+
+
+def mask_rows(vals, labels, mask_indices, host_indices=None):
+    """vals fp32 (R, M, M, K) channels-last (possibly a channel-slice view: pitch >= K), labels int64 (R,), mask_indices int32 device table ->
+    (R, 1, M, M) fp32: vals[r, :, :, mask_indices[max(labels[r], 0)]], zeros where that index is negative (hdy_mask_rows).  host_indices: the
+    same table as a sequence of ints on the host, if the caller has it: an index >= K is then refused before the launch."""
+    vp, R, M, M2, K, ldv = nhwc(vals)
+    require_gpu(labels)
+    require_gpu(mask_indices)
+    assert vals.dtype == torch.float32 and M == M2, f'{vals.dtype} {tuple(vals.shape)}'
+    assert labels.dtype == torch.int64 and labels.dim() == 1 and labels.numel() == R and (R <= 1 or labels.stride(0) == 1)
+    assert mask_indices.dtype == torch.int32 and mask_indices.dim() == 1 and mask_indices.is_contiguous() and mask_indices.numel() >= 1
+    host = None
+    if host_indices is not None:
+        assert len(host_indices) == mask_indices.numel()
+        host = (ctypes.c_int * len(host_indices))(*[int(v) for v in host_indices])
+    out = torch.empty((R, 1, M, M), dtype=torch.float32, device=vals.device)
+    if R:
+        _lib.call('hdy_mask_rows', vp, ldv, K, labels.data_ptr(), mask_indices.data_ptr(), ctypes.cast(host, ctypes.c_void_p) if host else None,
+                  mask_indices.numel(), R, M, out.data_ptr(), out.numel(), stream_ptr())
+    return out
+
+
 def roi_align_bwd(dout, shape, rois, spatial_scale, sampling_ratio=2, aligned=False, into=None):
     """Scatter dout (R, P, P, C) into an fp32 image (B, H, W, C) (`into`, accumulated, or a fresh zero image)."""
     B, H, W, C = shape

@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 13
+#define HDY_ABI_VERSION 14
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -582,6 +582,36 @@ int hdy_roi_align_fwd(const void* feat, int ldf, int B, int H, int W, int C, con
                       int sampling_ratio, int aligned, void* out, int dtype, void* stream);
 int hdy_roi_align_bwd(const void* dout, float* dfeat_f32, int B, int H, int W, int C, const float* rois, int R, float spatial_scale, int P,
                       int sampling_ratio, int aligned, int dtype, void* stream);
+/* hdy_roi_align_levels_fwd replaces multiscale_roi_align over a batch's detections (yolo_head.py:279-299, as compute_outputs calls it at
+ * :320-353): per level `levels == l` -> nonzero -> roi_align -> cat -> reorder becomes ONE launch on the padded NMS result as hdy_nms_batched
+ * leaves it.  levels: nl in [1, 8] records ON THE HOST, read before the call returns and passed to the kernel by value; level l is an NHWC map
+ * [B][H][W][ldf] of C channels (C and dtype shared by all levels; ldf >= C, both multiples of the 16-byte vector: 4 fp32 / 8 bf16 channels).
+ * boxes fp32 [B][max_det][4] xyxy in input pixels; level: the level id of each padded row as an fp32 value, row pitch nex floats (column 0 of
+ * the NMS `extra` block); n_keep int32 [B] on the device, B in [1, 1024], each count clamped to [0, max_det].
+ * out NHWC [out_rows][P][P][C] in COMPACTED order: image b's rows start at n_keep[0] + .. + n_keep[b - 1] and use image b of every map; the
+ * kernel derives that prefix itself (as hdy_slide_append and hdy_det_outputs do), without atomics.  Row values: exactly hdy_roi_align_fwd on
+ * the roi (b, box) with the level's map and spatial_scale — the two kernels share one device function, so the bits agree.  A row whose level
+ * is not finite or not in [0, nl) is written as zeros (the rule of hdy_roi_align_fwd for an image index out of range).  Padded rows
+ * >= n_keep[b] are scratch and never read.  Exactly min(out_rows, SUM n_keep) rows are written, nothing behind them.
+ * HDY_EINVAL before any launch: null pointers (a level's map included), nl outside 1..8, B outside 1..1024, C not a multiple of the vector
+ * width, P < 1, max_det < 1, nex < 1, out_rows < 0, misaligned out / boxes / maps.  out_rows == 0 launches nothing.
+ *
+ * hdy_mask_rows is the channel choice that follows the mask head (yolo_head.py:346-351: `masks[arange, mask_labels][:, None]`, rows with a
+ * negative mask label zeroed), for all rows at once: vals fp32 [R][M][M] with channel pitch ldv >= K (the head's sigmoid), labels int64 [R],
+ * mask_indices int32 [n_idx] on the device;  out fp32 [R][1][M][M] contiguous, out_elems = R * M * M exactly (else HDY_EINVAL):
+ *   idx = mask_indices[max(labels[r], 0)];  out[r] = vals[r][:][:][idx], or zeros when idx < 0.
+ * Pure data movement: the values are copied bit for bit.  mask_indices_host (may be NULL): the same table on the host; with it an idx >= K is
+ * HDY_EINVAL before the launch.  Whatever the host cannot see (a label >= n_idx, an idx >= K in a device-only table) writes a row of zeros:
+ * the kernel never reads out of range. */
+typedef struct hdy_roi_level {
+    const void* feat;
+    int H, W, ldf;
+    float spatial_scale;
+} hdy_roi_level;
+int hdy_roi_align_levels_fwd(const hdy_roi_level* levels, int nl, int C, const float* boxes, const float* level, int nex, const int* n_keep, int B,
+                             int max_det, int P, int sampling_ratio, int aligned, void* out, int out_rows, int dtype, void* stream);
+int hdy_mask_rows(const float* vals, int ldv, int K, const long long* labels, const int* mask_indices, const int* mask_indices_host, int n_idx, int R,
+                  int M, float* out, long long out_elems, void* stream);
 int hdy_relu_bwd(const void* dz, const void* y, void* du, long long n, int dtype, void* stream);
 int hdy_cast_store(const float* src, void* dst, int ldd, long long M, int C, int accumulate, int dtype, void* stream);
 

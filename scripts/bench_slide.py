@@ -4,7 +4,14 @@
     python scripts/bench_slide.py --slide 20000 [--grid-min 0]                synthetic slide -> evaluation.inference_on_slide
     python scripts/bench_slide.py --slide 20000 --u8 [--min-tissue 0.05]      the same from a synthetic 8-bit (H, W, 3) slide (tile gather + device merge)
     python scripts/bench_slide.py --slide-ab 8000 20000 [--out profiles/slide_u8_ab.txt]   float path vs 8-bit path on the same pixels
+    python scripts/bench_slide.py --masks-ab 2560 5120 [--out profiles/slide_masks_ab.txt]   masks of an 8-bit slide: device mask rows vs HDY_DEVICE_MASKS=0
     python scripts/bench_slide.py --once 262144                               one nms_grid call (for a kernel trace of its own)
+
+--masks-ab: the synthetic mask model of `evaluation.py --masks` (tiny variant, one mask class, fp32, conf_thres 0.05) on a synthetic 8-bit slide
+per size; evaluation.inference_on_slide(..., compute_masks=True, label_map=True) with the device mask rows (Detect.masks_device, the masks
+beside the device append) against HDY_DEVICE_MASKS=0 (Detect.attach_masks per batch and the Python merge: the path before the switch
+existed), alternating in one process after a warm-up of each side that builds the plans.  Wall time around each call between device
+synchronisations; the results of the two sides are compared with torch.equal before anything is timed.
 
 --slide-ab: per size one random 8-bit slide on the device and three ways through evaluation.inference_on_slide, alternating, after a warm-up of
 each: "float" = the float path fed table[v] as float CHW already on the device (its best case), "convert + float" = the same with the
@@ -192,6 +199,62 @@ def slide_ab(opt):
     print(text)
 
 
+def masks_ab(opt):
+    import evaluation
+    from metayolo.models.yolo import Deploy, Model
+    dev = torch.device('cuda', 0)
+    cfg = synth.make_cfg('n', 2)
+    cfg['headers'][0][3][3] = 1                                           # one mask class: the mask model of evaluation.py --masks
+    mm = Model(cfg, synth.make_hyp(conf_thres=0.05))
+    mm.load_state_dict(synth.mask_state_dict(mm), strict=False)
+    dep = Deploy(mm.to(dev).eval())
+    lines = ['command: python ' + ' '.join(sys.argv),
+             f'device: {torch.cuda.get_device_name(0)}; mask model (yolov5n, one mask class, fp32), tile {opt.tile}, overlap {opt.overlap}, batch {opt.batch_size}, '
+             f'compute_masks + label_map; times in ms, median [min .. max] over {opt.repeats} repeats, sides alternating',
+             f'{"slide":>7s} {"tiles":>6s} {"batches":>7s} {"kept":>8s}  {"side":24s} {"ms / slide":>34s}  {"ms / batch (median)":>20s}']
+    sides = {'HDY_DEVICE_MASKS=0 (old)': '0', 'device mask rows (new)': '1'}
+    verdicts = []
+    for S in opt.masks_ab:
+        slide = (synth.synth_images(1, S, seed=5)[0] * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().to(dev)
+        kw = dict(tile=min(opt.tile, S), overlap=opt.overlap, batch_size=opt.batch_size, compute_masks=True, label_map=True)
+
+        def run(flag):
+            os.environ['HDY_DEVICE_MASKS'] = flag
+            return evaluation.inference_on_slide(dep, slide, **kw)
+
+        first = {k: run(flag) for k, flag in sides.items()}               # plans, packings, allocator
+        old, new = (first[k]['det'] for k in sides)
+        assert sorted(old) == sorted(new) and all(torch.equal(old[k], new[k]) for k in old), 'the two sides differ'
+        kept = len(new['boxes'])
+        del first, old, new
+        rec = {k: [] for k in sides}
+        for _ in range(opt.repeats):
+            for k, flag in sides.items():
+                torch.cuda.synchronize()
+                t0 = time.time()
+                out = run(flag)
+                torch.cuda.synchronize()
+                rec[k].append((time.time() - t0) * 1e3)
+                del out
+        tiles = len(evaluation.slide_rois(S, S, kw['tile'], opt.overlap))
+        batches = -(-tiles // opt.batch_size)
+        for k, v in rec.items():
+            lines.append(f'{S:7d} {tiles:6d} {batches:7d} {kept:8d}  {k:24s} {stats(v):>34s}  {statistics.median(v) / batches:20.3f}')
+        o, n = rec['HDY_DEVICE_MASKS=0 (old)'], rec['device mask rows (new)']
+        verdicts.append(statistics.median(n) <= statistics.median(o))
+        lines.append(f'{"":7s} new median <= old median: {"yes" if verdicts[-1] else "no"}; new slowest < old fastest: {"yes" if max(n) < min(o) else "no"}')
+        print('\n'.join(lines[-3:]), flush=True)
+        del slide
+        torch.cuda.empty_cache()
+    os.environ.pop('HDY_DEVICE_MASKS', None)
+    text = '\n'.join(lines) + '\n'
+    if opt.out:
+        os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
+        with open(opt.out, 'w') as f:
+            f.write(text)
+    print(text)
+
+
 def slide(opt):
     evaluation, deployed, merge, dev = _slide_setup(opt)
     S = opt.slide
@@ -234,6 +297,7 @@ if __name__ == '__main__':
     ap.add_argument('--u8', action='store_true', help='--slide: a synthetic 8-bit (S, S, 3) slide from the seed, through the tile gather and the device merge')
     ap.add_argument('--min-tissue', type=float, default=0.0, help='--slide --u8: skip tiles with less than this fraction of non-background pixels')
     ap.add_argument('--slide-ab', type=int, nargs='*', default=[], help='sizes for the float path vs 8-bit path comparison')
+    ap.add_argument('--masks-ab', type=int, nargs='*', default=[], help='sizes for the device mask rows vs HDY_DEVICE_MASKS=0 comparison on 8-bit slides')
     ap.add_argument('--once', type=int, default=0)
     ap.add_argument('--repeats', type=int, default=9)
     ap.add_argument('--old-max', type=int, default=140000, help='largest set the one-workgroup kernel is timed on repeatedly')
@@ -251,6 +315,8 @@ if __name__ == '__main__':
         ab(opt)
     if opt.slide_ab:
         slide_ab(opt)
+    if opt.masks_ab:
+        masks_ab(opt)
     if opt.slide:
         slide(opt)
     if opt.once:
