@@ -10,6 +10,14 @@ NHWC buffers; forward and backward are replays of two launch lists.  What the tr
   * fusion      C3's cv1 and cv2 (two 1x1 convs on the same input) become ONE conv with K = 2c_ (train mode);
                 BN statistics come out of the conv kernel's epilogue as per-tile slabs; normalise+SiLU(+residual)
                 is one streaming pass; in eval mode BN is folded into the conv epilogue (scale/shift/SiLU/residual).
+  * forward     replay in trace order: one emitter per unit kind (_fwd_conv / _fwd_pool / _fwd_up / _fwd_det) appends to the
+                record list.  An eval ConvUnit is one launch (BN through the bn_eval table, or the bias of a BN-folded model); a
+                training ConvUnit's BatchNorm forward is _bn_fwd_mode(u) ('sync' / 'pair' / 'single' / 'frozen'): one
+                _bn_fwd_<mode> emitter each, all ending in the one apply pass _bn_fwd_apply.  A unit's geometry (hin, win, M,
+                pack kind, stem_hw) is fixed when it is traced.
+  * memory      _allocate: activation storage; per-unit buffers, one allocator per unit kind (_alloc_conv / _alloc_det /
+                _alloc_pool), each telling a _Scratch what the shared scratch buffers must hold; those buffers; gradient
+                storage, which mirrors activation storage (concat members share, a shortcut input aliases the block output).
   * backward    reverse replay: [BN+SiLU backward -> dy] -> wgrad -> dgrad, gradients of multiply-consumed tensors are
                 accumulated in the dgrad epilogue (no add kernels); the Bottleneck shortcut aliases gradient storage.
                 _mark_needs_grad says which tensors get a gradient, then one emitter per unit kind (_bwd_det / _bwd_up /
@@ -73,13 +81,18 @@ class Val:
 
 
 class ConvUnit:
-    def __init__(self, mods, x, res, outs, stem):
+    def __init__(self, mods, x, res, outs, stem, hin, win):
+        """hin, win: the extent the convolution reads (the image's for the stem, x's otherwise)"""
         self.mods, self.x, self.res, self.outs, self.stem = mods, x, res, outs, stem
         c = mods[0].conv
         self.k, self.s, self.p = c.kernel_size[0], c.stride[0], c.padding[0]
         self.Ks = [m.conv.out_channels for m in mods]
         self.K = sum(self.Ks)
         self.C = c.in_channels
+        self.hin, self.win = hin, win
+        self.M = outs[0].n * outs[0].h * outs[0].w          # output pixels
+        self.pack_kind = ops.PACK_STEM if stem else ops.PACK_FWD
+        self.stem_hw = (hin, win) if stem else None
         self.has_bn = hasattr(mods[0], 'bn')
         # torchvision-style FrozenBatchNorm2d put in place by Model.freeze (utils_torch.freeze_bn): constant scale / shift in training too
         self.frozen = self.has_bn and type(mods[0].bn).__name__ == 'FrozenBatchNorm2d'
@@ -92,6 +105,7 @@ class DetUnit:
         self.conv, self.x, self.level = conv, x, level
         self.K = conv.out_channels
         self.Kp = (self.K + 7) // 8 * 8
+        self.M = x.n * x.h * x.w
 
 
 class PoolUnit:
@@ -102,6 +116,19 @@ class PoolUnit:
 class UpUnit:
     def __init__(self, x, out):
         self.x, self.out = x, out
+
+
+class _Scratch:
+    """What the shared scratch buffers have to hold, as the per-unit allocators report it: the largest request for each (elements or
+    bytes, whichever that buffer is sized in) and the widest ConvUnit."""
+
+    def __init__(self):
+        self.stats = self.dy = self.wg = self.bnws = self.f1 = 1
+        self.kmax = 0
+
+    def add(self, **sizes):
+        for k, n in sizes.items():
+            setattr(self, k, max(getattr(self, k), n))
 
 
 class _BackwardList:
@@ -222,6 +249,9 @@ class Plan:
         # replayed with one call (the eager lists are ~350 / ~450 launches per step for yolov5s)
         self._graphs = {'fwd': None, 'bwd': None}
         self._runs = {'fwd': 0, 'bwd': 0}
+        self._progs = {}                # 'fwd' / 'bwd' -> ops.Program of that list, compiled at its first replay
+        self._bn_running = None         # bn_running()'s list, built at its first call
+        self._pack_stream = None        # PACK_SIDE: the stream the weight re-pack runs on
 
     # ------------------------------------------------------------------ tracing
     def _val(self, n, h, w, c, name):
@@ -250,7 +280,7 @@ class Plan:
             self._use(res)
         ho, wo = ops.out_dim(h, k, s, p), ops.out_dim(w, k, s, p)
         outs = [self._val(n, ho, wo, m.conv.out_channels, 'conv') for m in mods]
-        u = ConvUnit(mods, x, res, outs, stem)
+        u = ConvUnit(mods, x, res, outs, stem, h, w)
         self.units.append(u)
         if res is not None and self.training:
             if res.cat is not None or res.parts is not None:
@@ -395,7 +425,18 @@ class Plan:
         return f(shape, dtype=dtype or self.dtype, device=self.device)
 
     def _allocate(self):
-        dt = self.dtype
+        self._alloc_activations()
+        need = _Scratch()
+        alloc = {ConvUnit: self._alloc_conv, DetUnit: self._alloc_det, PoolUnit: self._alloc_pool}
+        for u in self.units:
+            if type(u) in alloc:
+                alloc[type(u)](u, need)
+        if self.training:
+            self._alloc_det_grads()
+            self._alloc_scratch(need)
+            self._alloc_gradients()
+
+    def _alloc_activations(self):
         for v in self.vals:
             if v.parts is not None or v.cat is None:
                 v.buf = self._new(v.n, v.h, v.w, v.c)
@@ -403,82 +444,72 @@ class Plan:
             if v.cat is not None:
                 v.buf = v.cat.buf
         self.prep = self._new(self.B, self.H + 4, self.W + 4, 4)
-        f32 = torch.float32
-        max_stats = max_dy = max_wg = max_bnws = max_f1 = 1
-        for u in self.units:
-            if isinstance(u, ConvUnit):
-                o = u.outs[0]
-                M = o.n * o.h * o.w
-                kind = ops.PACK_STEM if u.stem else ops.PACK_FWD
-                u.wp = ops.pack_alloc(u.K, u.C, u.k, u.k, u.s, u.p, kind, dt, self.device)
-                u.scale, u.shift = self._new(u.K, dtype=f32), self._new(u.K, dtype=f32)
-                if self.training:
-                    if not u.has_bn:
-                        raise _lib.HdyError('training a fused (BN-folded) model is not supported: build the model unfused')
-                    u.yraw = self._new(o.n, o.h, o.w, u.K)
-                    hin, win = (self.H, self.W) if u.stem else (u.x.h, u.x.w)
-                    if u.frozen:
-                        u.mean = u.invstd = None
-                        u.mtiles = 0
-                    else:
-                        u.mean, u.invstd = self._new(u.K, dtype=f32), self._new(u.K, dtype=f32)
-                        u.mtiles = ops.stat_slabs(o.n, hin, win, u.C, u.K, u.k, u.k, u.s, u.p, dt)
-                    max_stats = max(max_stats, u.mtiles * 2 * u.K)
-                    max_dy = max(max_dy, M * u.K)
-                    wgb = ops.wgrad_ws_bytes(o.n, hin, win, u.C, u.K, u.k, u.k, u.s, u.p, dt, stem=u.stem)
-                    max_wg = max(max_wg, wgb)
-                    max_bnws = max(max_bnws, ops.bn_bwd_ws_floats(M, u.K))
-                    if self._fusable_1x1(u):
-                        max_f1 = max(max_f1, ops.fused_1x1_ws_bytes(M, u.C, u.K))
-                    if not u.stem:
-                        u.wpd = ops.pack_alloc(u.K, u.C, u.k, u.k, u.s, u.p, ops.PACK_DGRAD, dt, self.device)
-            elif isinstance(u, DetUnit):
-                x = u.x
-                u.wp = ops.pack_alloc(u.K, x.c, 1, 1, 1, 0, ops.PACK_FWD, dt, self.device)
-                u.logits = self._new(x.n, x.h, x.w, u.Kp, dtype=f32, zero=True)
-                if self.training:
-                    M = x.n * x.h * x.w
-                    u.wpd = ops.pack_alloc(u.Kp, x.c, 1, 1, 1, 0, ops.PACK_DGRAD, dt, self.device)
-                    wgb = ops.wgrad_ws_bytes(x.n, x.h, x.w, x.c, u.Kp, 1, 1, 1, 0, dt)
-                    max_wg = max(max_wg, wgb)
-                    max_bnws = max(max_bnws, ops.bn_bwd_ws_floats(M, u.Kp))
-            elif isinstance(u, PoolUnit):
-                if self.training:
-                    a = u.x
-                    u.idx = [self._new(a.n, a.h, a.w, a.c, dtype=torch.uint8) for _ in range(3)]
+
+    def _alloc_conv(self, u, need):
+        dt, f32, o = self.dtype, torch.float32, u.outs[0]
+        u.wp = ops.pack_alloc(u.K, u.C, u.k, u.k, u.s, u.p, u.pack_kind, dt, self.device)
+        u.scale, u.shift = self._new(u.K, dtype=f32), self._new(u.K, dtype=f32)
         if not self.training:
             return
+        if not u.has_bn:
+            raise _lib.HdyError('training a fused (BN-folded) model is not supported: build the model unfused')
+        u.yraw = self._new(o.n, o.h, o.w, u.K)
+        if u.frozen:
+            u.mean = u.invstd = None
+            u.mtiles = 0
+        else:
+            u.mean, u.invstd = self._new(u.K, dtype=f32), self._new(u.K, dtype=f32)
+            u.mtiles = ops.stat_slabs(o.n, u.hin, u.win, u.C, u.K, u.k, u.k, u.s, u.p, dt)
+        need.add(stats=u.mtiles * 2 * u.K, dy=u.M * u.K, bnws=ops.bn_bwd_ws_floats(u.M, u.K), kmax=u.K,
+                 wg=ops.wgrad_ws_bytes(o.n, u.hin, u.win, u.C, u.K, u.k, u.k, u.s, u.p, dt, stem=u.stem))
+        if self._fusable_1x1(u):
+            need.add(f1=ops.fused_1x1_ws_bytes(u.M, u.C, u.K))
+        if not u.stem:
+            u.wpd = ops.pack_alloc(u.K, u.C, u.k, u.k, u.s, u.p, ops.PACK_DGRAD, dt, self.device)
+
+    def _alloc_det(self, u, need):
+        x, dt = u.x, self.dtype
+        u.wp = ops.pack_alloc(u.K, x.c, 1, 1, 1, 0, ops.PACK_FWD, dt, self.device)
+        u.logits = self._new(x.n, x.h, x.w, u.Kp, dtype=torch.float32, zero=True)
+        if self.training:
+            u.wpd = ops.pack_alloc(u.Kp, x.c, 1, 1, 1, 0, ops.PACK_DGRAD, dt, self.device)
+            need.add(wg=ops.wgrad_ws_bytes(x.n, x.h, x.w, x.c, u.Kp, 1, 1, 1, 0, dt), bnws=ops.bn_bwd_ws_floats(u.M, u.Kp))
+
+    def _alloc_pool(self, u, need):
+        if self.training:
+            a = u.x
+            u.idx = [self._new(a.n, a.h, a.w, a.c, dtype=torch.uint8) for _ in range(3)]
+
+    def _alloc_det_grads(self):
         # logits gradients of all levels live in one flat buffer (one scale launch, one owner)
-        sizes = [u.x.n * u.x.h * u.x.w * u.Kp for u in self.det_units]
+        sizes = [u.M * u.Kp for u in self.det_units]
         self.gdet_flat = self._new(max(sum(sizes), 1), zero=True)
         off = 0
         for u, n in zip(self.det_units, sizes):
             u.gdet = self.gdet_flat[off:off + n].view(u.x.n, u.x.h, u.x.w, u.Kp)
             off += n
-        self.loss_out = self._new(4, dtype=f32, zero=True)
+        self.loss_out = self._new(4, dtype=torch.float32, zero=True)
         self.loss_call = None
-        self.stats = self._new(max_stats, dtype=f32)
+
+    def _alloc_scratch(self, need):
+        f32 = torch.float32
+        self.stats = self._new(need.stats, dtype=f32)
         # BN-backward output of the layer in flight; a small ring, so that the weight-gradient kernels of the previous layers
         # (side stream) may still be reading theirs while the main stream moves on
-        self.dy_ring = [self._new(max_dy) for _ in range(DY_RING if SIDE_WGRAD else 1)]
-        self.wg_ws = self._new(max_wg // 4 + 16, dtype=f32)
-        self.wg_ws_main = self._new(max_wg // 4 + 16, dtype=f32) if (FORK_MIN_PIXELS > 0 and SIDE_WGRAD) else self.wg_ws
-        kmax = max(u.K for u in self.units if isinstance(u, ConvUnit))
-        self.bn_c12 = self._new(2, kmax, dtype=f32)     # c1 / c2 of the unit in flight
-        self.f1_ws = self._new(max_f1 // 4 + 16, dtype=f32)      # weight-gradient slabs of the fused 1x1 backward (main stream: not shared with wg_ws)
-        self.bn_ws = self._new(max_bnws, dtype=f32)
-        self.fin_ws = self._new(32 * 2 * kmax, dtype=torch.float64)
-        self.sync_sums = self._new(2 * kmax + 1, dtype=torch.float64) if self.sync else None
+        self.dy_ring = [self._new(need.dy) for _ in range(DY_RING if SIDE_WGRAD else 1)]
+        self.wg_ws = self._new(need.wg // 4 + 16, dtype=f32)
+        self.wg_ws_main = self._new(need.wg // 4 + 16, dtype=f32) if (FORK_MIN_PIXELS > 0 and SIDE_WGRAD) else self.wg_ws
+        self.bn_c12 = self._new(2, need.kmax, dtype=f32)     # c1 / c2 of the unit in flight
+        self.f1_ws = self._new(need.f1 // 4 + 16, dtype=f32)      # weight-gradient slabs of the fused 1x1 backward (main stream: not shared with wg_ws)
+        self.bn_ws = self._new(need.bnws, dtype=f32)
+        self.fin_ws = self._new(32 * 2 * need.kmax, dtype=torch.float64)
+        self.sync_sums = self._new(2 * need.kmax + 1, dtype=torch.float64) if self.sync else None
+
+    def _alloc_gradients(self):
         # gradient storage mirrors activation storage
-        for v in self.vals:
-            if v.parts is not None or v.cat is None:
-                v.gbuf = None       # allocated below unless aliased
         for v in reversed(self.vals):
-            if v.cat is not None:
-                continue
-            if v.galias is not None and v.parts is None:
-                continue
-            v.gbuf = self._new(v.n, v.h, v.w, v.c)
+            if v.cat is None and (v.galias is None or v.parts is not None):
+                v.gbuf = self._new(v.n, v.h, v.w, v.c)
         for v in self.vals:
             if v.cat is not None:
                 v.gbuf, v.goff = v.cat.gbuf, v.off
@@ -499,89 +530,104 @@ class Plan:
 
     # ------------------------------------------------------------------ forward
     def _compile_forward(self):
+        emit = {ConvUnit: self._fwd_conv, PoolUnit: self._fwd_pool, UpUnit: self._fwd_up, DetUnit: self._fwd_det}
         recs = []
-        t = self.training
         for u in self.units:
-            if isinstance(u, ConvUnit):
-                x = self.prep if u.stem else u.x.t()
-                stem_hw = (self.H, self.W) if u.stem else None
-                kind = ops.PACK_STEM if u.stem else ops.PACK_FWD
-                o0 = u.outs[0]
-                if t:
-                    wb = u.mods[1].conv.weight if len(u.mods) > 1 else None
-                    self.packs.add(u.mods[0].conv.weight, wb, u.s, u.p, kind, u.wp)
-                    M = o0.n * o0.h * o0.w
-                    stats = None if u.frozen else self.stats[:u.mtiles * 2 * u.K].view(u.mtiles, 2, u.K)
-                    recs.append(ops.rec_conv_fwd(x, u.wp, u.yraw, u.K, u.k, u.k, u.s, u.p, stats=stats, stem_hw=stem_hw))
-                    if self.sync and not u.frozen:
-                        # SyncBatchNorm: slabs -> [SUM | SUM2 | count] in fp64, all-reduced, then the usual finalize from the global sums
-                        buf = self.sync_sums[:2 * u.K + 1]
-                        recs.append(ops.rec_bn_slab_sums(stats, u.mtiles, u.K, M, buf))
-                        recs.append(self._sync_call(buf))
-                        pair_fwd = len(u.mods) == 2 and u.res is None
-                        k0 = 0
-                        for i, (m, o) in enumerate(zip(u.mods, u.outs)):
-                            K = m.conv.out_channels
-                            recs.append(ops.rec_bn_finalize_sums(buf, u.K, k0, K, K, self._bn(m), None, u.scale[k0:], u.shift[k0:], u.mean[k0:], u.invstd[k0:],
-                                                                 eps=m.bn.eps, momentum=m.bn.momentum))
-                            if not pair_fwd:
-                                res = u.res.t() if u.res is not None else None
-                                recs.append(ops.rec_bn_act_fwd(u.yraw[..., k0:k0 + K], u.scale[k0:k0 + K], u.shift[k0:k0 + K], o.t(), res=res, act=u.act))
-                            k0 += K
-                        if pair_fwd:
-                            recs.append(ops.rec_bn_act_fwd_pair(u.yraw, u.scale, u.shift, u.outs[0].t(), u.outs[1].t(), act=u.act))
-                        continue
-                    if len(u.mods) == 2 and not u.frozen and u.res is None:
-                        # the C3 pair: per-channel BatchNorm over the whole 2c-wide raw tensor in one finalize + one apply pass
-                        Ka = u.mods[0].conv.out_channels
-                        assert u.mods[0].bn.eps == u.mods[1].bn.eps and u.mods[0].bn.momentum == u.mods[1].bn.momentum
-                        recs.append(ops.rec_bn_finalize_pair(stats, u.mtiles, u.K, Ka, M, self._bn(u.mods[0]), self._bn(u.mods[1]), u.scale, u.shift,
-                                                             u.mean, u.invstd, eps=u.mods[0].bn.eps, momentum=u.mods[0].bn.momentum, ws=self.fin_ws))
-                        recs.append(ops.rec_bn_act_fwd_pair(u.yraw, u.scale, u.shift, u.outs[0].t(), u.outs[1].t(), act=u.act))
-                        continue
-                    k0 = 0
-                    for m, o in zip(u.mods, u.outs):
-                        K = m.conv.out_channels
-                        g, b, rm, rv = self._bn(m)
-                        if u.frozen:
-                            recs.append(ops.rec_bn_eval_coeffs(g, b, rm, rv, u.scale[k0:k0 + K], u.shift[k0:k0 + K], eps=m.bn.eps))
-                        else:
-                            recs.append(ops.rec_bn_finalize(stats[:, :, k0:], u.mtiles, K, M, g, b, rm, rv, u.scale[k0:], u.shift[k0:],
-                                                            u.mean[k0:], u.invstd[k0:], stats_ld=u.K, ws=self.fin_ws))
-                        res = u.res.t() if u.res is not None else None
-                        recs.append(ops.rec_bn_act_fwd(u.yraw[..., k0:k0 + K], u.scale[k0:k0 + K], u.shift[k0:k0 + K], o.t(), res=res, act=u.act))
-                        k0 += K
-                else:
-                    m, o = u.mods[0], u.outs[0]
-                    self.packs.add(m.conv.weight, None, u.s, u.p, kind, u.wp)
-                    if u.has_bn:
-                        g, b, rm, rv = self._bn(m)
-                        self.bn_eval.add(g, b, rm, rv, u.scale, u.shift, eps=m.bn.eps)
-                        scale, shift = u.scale, u.shift
-                    else:
-                        scale, shift = None, m.conv.bias
-                    res = u.res.t() if u.res is not None else None
-                    recs.append(ops.rec_conv_fwd(x, u.wp, o.t(), u.K, u.k, u.k, u.s, u.p, scale=scale, shift=shift, act=u.act, stem_hw=stem_hw,
-                                                 res=res))
-            elif isinstance(u, PoolUnit):
-                idx = u.idx if t else None
-                recs.append(ops.rec_sppf_pool_fwd(u.x.t(), u.outs[0].t(), u.outs[1].t(), u.outs[2].t(), idx))
-            elif isinstance(u, UpUnit):
-                recs.append(ops.rec_upsample_fwd(u.x.t(), u.out.t()))
-            elif isinstance(u, DetUnit):
-                self.packs.add(u.conv.weight, None, 1, 0, ops.PACK_FWD, u.wp)
-                recs.append(ops.rec_conv_fwd(u.x.t(), u.wp, u.logits[..., :u.K], u.K, 1, 1, 1, 0, shift=u.conv.bias))
+            emit[type(u)](recs, u)
         return recs
+
+    def _fwd_pool(self, recs, u):
+        recs.append(ops.rec_sppf_pool_fwd(u.x.t(), u.outs[0].t(), u.outs[1].t(), u.outs[2].t(), u.idx if self.training else None))
+
+    def _fwd_up(self, recs, u):
+        recs.append(ops.rec_upsample_fwd(u.x.t(), u.out.t()))
+
+    def _fwd_det(self, recs, u):
+        self.packs.add(u.conv.weight, None, 1, 0, ops.PACK_FWD, u.wp)
+        recs.append(ops.rec_conv_fwd(u.x.t(), u.wp, u.logits[..., :u.K], u.K, 1, 1, 1, 0, shift=u.conv.bias))
+
+    def _fwd_conv(self, recs, u):
+        (self._fwd_conv_train if self.training else self._fwd_conv_eval)(recs, u, self.prep if u.stem else u.x.t())
+
+    def _fwd_conv_eval(self, recs, u, x):
+        """one launch: BatchNorm folded into the epilogue's scale / shift through the bn_eval table, or (a BN-folded model) the bias alone"""
+        m, o = u.mods[0], u.outs[0]
+        self.packs.add(m.conv.weight, None, u.s, u.p, u.pack_kind, u.wp)
+        if u.has_bn:
+            self.bn_eval.add(*self._bn(m), u.scale, u.shift, eps=m.bn.eps)
+            scale, shift = u.scale, u.shift
+        else:
+            scale, shift = None, m.conv.bias
+        res = u.res.t() if u.res is not None else None
+        recs.append(ops.rec_conv_fwd(x, u.wp, o.t(), u.K, u.k, u.k, u.s, u.p, scale=scale, shift=shift, act=u.act, stem_hw=u.stem_hw, res=res))
+
+    def _fwd_conv_train(self, recs, u, x):
+        """the raw convolution, leaving per-tile statistics slabs unless the BatchNorm is frozen, then the BatchNorm forward of _bn_fwd_mode(u)"""
+        wb = u.mods[1].conv.weight if len(u.mods) > 1 else None
+        self.packs.add(u.mods[0].conv.weight, wb, u.s, u.p, u.pack_kind, u.wp)
+        stats = None if u.frozen else self.stats[:u.mtiles * 2 * u.K].view(u.mtiles, 2, u.K)
+        recs.append(ops.rec_conv_fwd(x, u.wp, u.yraw, u.K, u.k, u.k, u.s, u.p, stats=stats, stem_hw=u.stem_hw))
+        getattr(self, '_bn_fwd_' + self._bn_fwd_mode(u))(recs, u, stats)
+
+    def _bn_fwd_mode(self, u):
+        """How a training ConvUnit's scale / shift come about: 'sync' (slabs -> fp64 sums -> all-reduce -> one finalize per module), 'pair' (the
+        C3 pair: one finalize over the whole 2c-wide raw tensor), 'single' (one finalize per module), 'frozen' (constant coefficients from the
+        running statistics, no slabs)."""
+        if self.sync and not u.frozen:
+            return 'sync'
+        if self._pair_apply(u):
+            return 'pair'
+        return 'frozen' if u.frozen else 'single'
+
+    @staticmethod
+    def _pair_apply(u):
+        """two live modules share the raw tensor and nothing is added: both halves are normalised in one pass"""
+        return len(u.mods) == 2 and not u.frozen and u.res is None
+
+    def _bn_fwd_apply(self, recs, u, coeffs=None):
+        """The normalise + activation (+ residual) pass behind the coefficient records coeffs(m, k0, K) of the modules: one pass over both halves
+        behind both records for a pair, else every module's record followed by its own pass."""
+        pair = self._pair_apply(u)
+        res = u.res.t() if u.res is not None else None
+        for m, o, ch in self._channels(u):
+            if coeffs is not None:
+                recs.append(coeffs(m, ch.start, ch.stop - ch.start))
+            if not pair:
+                recs.append(ops.rec_bn_act_fwd(u.yraw[..., ch], u.scale[ch], u.shift[ch], o.t(), res=res, act=u.act))
+        if pair:
+            recs.append(ops.rec_bn_act_fwd_pair(u.yraw, u.scale, u.shift, u.outs[0].t(), u.outs[1].t(), act=u.act))
+
+    # One emitter per mode.  The per-module coefficient records take open-ended slices [k0:] of the unit's K-wide vectors (the kernels write K
+    # of them from there on).
+    def _bn_fwd_sync(self, recs, u, stats):
+        buf = self.sync_sums[:2 * u.K + 1]              # [SUM | SUM2 | count]
+        recs.append(ops.rec_bn_slab_sums(stats, u.mtiles, u.K, u.M, buf))
+        recs.append(self._sync_call(buf))
+        self._bn_fwd_apply(recs, u, lambda m, k0, K: ops.rec_bn_finalize_sums(
+            buf, u.K, k0, K, K, self._bn(m), None, u.scale[k0:], u.shift[k0:], u.mean[k0:], u.invstd[k0:], eps=m.bn.eps, momentum=m.bn.momentum))
+
+    def _bn_fwd_pair(self, recs, u, stats):
+        ma, mb = u.mods
+        assert ma.bn.eps == mb.bn.eps and ma.bn.momentum == mb.bn.momentum
+        recs.append(ops.rec_bn_finalize_pair(stats, u.mtiles, u.K, ma.conv.out_channels, u.M, self._bn(ma), self._bn(mb), u.scale, u.shift,
+                                             u.mean, u.invstd, eps=ma.bn.eps, momentum=ma.bn.momentum, ws=self.fin_ws))
+        self._bn_fwd_apply(recs, u)
+
+    def _bn_fwd_single(self, recs, u, stats):
+        self._bn_fwd_apply(recs, u, lambda m, k0, K: ops.rec_bn_finalize(
+            stats[:, :, k0:], u.mtiles, K, u.M, *self._bn(m), u.scale[k0:], u.shift[k0:], u.mean[k0:], u.invstd[k0:], stats_ld=u.K, ws=self.fin_ws))
+
+    def _bn_fwd_frozen(self, recs, u, stats):
+        self._bn_fwd_apply(recs, u, lambda m, k0, K: ops.rec_bn_eval_coeffs(*self._bn(m), u.scale[k0:k0 + K], u.shift[k0:k0 + K], eps=m.bn.eps))
 
     def _replay(self, key, recs):
         if not USE_GRAPHS:
             if not ops.USE_EXEC:
                 return ops.run(recs)
             # the list is static: compiled once into words for hdy_exec_run (one C call per stretch between host callbacks) and replayed
-            progs = self.__dict__.setdefault('_progs', {})
-            prog = progs.get(key)
+            prog = self._progs.get(key)
             if prog is None or prog.records is not recs or prog.nrec != len(recs):
-                prog = progs[key] = ops.Program(recs)
+                prog = self._progs[key] = ops.Program(recs)
             return prog.run()
         g = self._graphs[key]
         if g is None:
@@ -600,7 +646,7 @@ class Plan:
 
     def bn_running(self):
         """running_mean / running_var of every live BatchNorm: the training forward writes them through raw pointers"""
-        if getattr(self, '_bn_running', None) is None:
+        if self._bn_running is None:
             self._bn_running = [t for u in self.units if isinstance(u, ConvUnit) and u.has_bn and not u.frozen for m in u.mods
                                 for t in (m.bn.running_mean, m.bn.running_var)]
         return self._bn_running
@@ -642,7 +688,7 @@ class Plan:
             # the per-step weight re-pack (one launch, ~50 us of gathers at yolov5s) depends on the optimizer's update, not on the images: it runs on a
             # second stream beside the input conversion (an HBM stream of ~90 us) and joins in front of the first convolution
             main = torch.cuda.current_stream(self.device)
-            if self.__dict__.get('_pack_stream') is None:
+            if self._pack_stream is None:
                 self._pack_stream = torch.cuda.Stream(device=self.device)
             self._pack_stream.wait_stream(main)
             with torch.cuda.stream(self._pack_stream):
@@ -753,7 +799,7 @@ class Plan:
         b.add(ops.rec_colsum(u.gdet, tmp, self.bn_ws))
         b.add(ops.rec_copy_f32(tmp[:u.K], b.grad(u.conv.bias)))                                # Kp-padded column sums -> the bias gradient
         gw = b.grad(u.conv.weight)
-        b.wgrad(lambda ws: ops.rec_conv_wgrad(x.t(), u.gdet, gw, None, 1, 1, 1, 0, ws), pixels=x.n * x.h * x.w)
+        b.wgrad(lambda ws: ops.rec_conv_wgrad(x.t(), u.gdet, gw, None, 1, 1, 1, 0, ws), pixels=u.M)
         if not x.needs_grad:
             return
         self.packs.add(u.conv.weight, None, 1, 0, ops.PACK_DGRAD, u.wpd, K=u.Kp)
@@ -870,8 +916,7 @@ class Plan:
     def _bwd_conv(self, b, u):
         if not u.outs[0].needs_grad:
             return
-        o0 = u.outs[0]
-        M = o0.n * o0.h * o0.w
+        o0, M = u.outs[0], u.M
         consumer, mode = self._bn_bwd_mode(u, b)
         dy = slot = None
         if consumer == 'dy':
@@ -905,14 +950,13 @@ class Plan:
                 else:
                     b.add(mk(None))
             return
-        stem_hw = (self.H, self.W) if u.stem else None
         ga = b.grad(u.mods[0].conv.weight)          # (logged for frozen filters too: the record behind them bounds their range's mark)
         gb = b.grad(u.mods[1].conv.weight) if len(u.mods) > 1 else None
         if consumer == 'fused_stem':
-            b.wgrad(lambda ws: ops.rec_conv_wgrad_stem_fused(x, o0.gread(), u.yraw, u.scale, u.shift, u.mean, u.invstd, c1, c2, stem_hw, ga, None, ws))
+            b.wgrad(lambda ws: ops.rec_conv_wgrad_stem_fused(x, o0.gread(), u.yraw, u.scale, u.shift, u.mean, u.invstd, c1, c2, u.stem_hw, ga, None, ws))
             return
         if want_w:
-            b.wgrad(lambda ws: ops.rec_conv_wgrad(x, dy, ga, gb, u.k, u.k, u.s, u.p, ws, stem_hw=stem_hw), pixels=M, reads_slot=slot)
+            b.wgrad(lambda ws: ops.rec_conv_wgrad(x, dy, ga, gb, u.k, u.k, u.s, u.p, ws, stem_hw=u.stem_hw), pixels=M, reads_slot=slot)
         if want_x:
             b.add_producer(xv, 'dgrad', lambda st: ops.rec_conv_dgrad(dy, u.wpd, xv.g(), u.k, u.k, u.s, u.p, accumulate=acc, stats=st),
                            self._dgrad_slabs(xv, u.K, u.k, u.s, u.p))
@@ -994,12 +1038,11 @@ class Plan:
             for q in self.tap_params:
                 self.grad_store.view_of(q).zero_()
         self.tap_grads_ready = False
+        pre = []
         if gdets is None:
             if scale is not None:
                 ops.scale_inplace(self.gdet_flat, scale.reshape(-1)[:1].float().contiguous())
-            pre = []
         else:
-            pre = []
             for u, g in zip(self.det_units, gdets):
                 if g is None:
                     u.gdet.zero_()

@@ -20,6 +20,9 @@ over the knobs nothing else in the suite moves: HDY_DY_RING 1 / 2 / 4, HDY_FORK_
 frozen backbone, SyncBatchNorm lists (static only).  Two negative controls show that the checks can fail: the ring's joins deleted (a and c
 see it), the two weight-gradient workspaces made one (a sees it).
 
+The forward list of the same plans is checked as a list: every ConvUnit's records are the sequence its Plan._bn_fwd_mode stands for, every
+pointer is covered by a tensor its record keeps alive (what makes replaying a stored list safe), and compiling again gives the same list.
+
 The mask branch is left out (compute_masks=False): roi_align's backward scatters with global atomics and is not bit-reproducible from run to
 run; its records hold no forks.  The engines here carry no bucket hooks (single process), so a mark does not wait for the side stream and the
 late order does not flush at marks; schedule_ref.late(side, plan) does, and tests/test_schedule_host.py covers that."""
@@ -116,6 +119,17 @@ class Built:
                 return self.plan._compile_backward()
         finally:
             packs.descs, packs.blocks, packs.keep, packs.table = saved
+
+    def rebuilt_forward(self):
+        """the forward list compiled again from the plan as it stands now (the pack table's and the BN-eval table's entries, which compiling
+        appends to, put back)"""
+        packs, bn = self.plan.packs, self.plan.bn_eval
+        saved = (list(packs.descs), packs.blocks, list(packs.keep), packs.table), (list(bn.descs), list(bn.keep), bn.table)
+        try:
+            with self.knobs():
+                return self.plan._compile_forward()
+        finally:
+            (packs.descs, packs.blocks, packs.keep, packs.table), (bn.descs, bn.keep, bn.table) = saved
 
     def targets(self):
         t = synth.synth_targets(BATCH, self.size, self.nc, nmin=self.boxes[0], nmax=self.boxes[1], seed=5)       # the model clamps them in place: fresh every step
@@ -214,6 +228,73 @@ def test_sync_batchnorm_lists_are_race_free(case):
     found = S.conflicts(b.plan.bwd)
     assert found == [], '\n'.join(map(repr, found[:10]))
     assert S.early_marks(b.plan.bwd, b.eng.store.cur) == []
+
+
+# ------------------------------------------------------------------------------------------ the forward list
+UNIT_HEADS = ('hdy_conv_fwd', 'hdy_sppf_pool_fwd', 'hdy_upsample2x_fwd')      # every unit's first forward record, and no other record of a unit
+COEFFS = {'single': 'hdy_bn_finalize', 'frozen': 'hdy_bn_eval_coeffs', 'sync': 'hdy_bn_finalize_sums'}
+FWD_SEEN = {}                                   # case id -> {(mode, apply symbol)} of the plans checked so far
+
+
+def forward_symbols(mode, u):
+    """the symbols Plan._bn_fwd_mode's answer stands for: the convolution, then the coefficients and the apply pass — one pass over both
+    halves when two live modules share the raw tensor and nothing is added, else one per module behind that module's coefficients"""
+    n = len(u.mods)
+    if mode == 'pair':
+        return ['hdy_conv_fwd', 'hdy_bn_finalize_pair', 'hdy_bn_act_fwd_pair']
+    head = ['hdy_conv_fwd'] + (['hdy_bn_slab_sums', '@call'] if mode == 'sync' else [])
+    if mode == 'sync' and n == 2 and u.res is None:
+        return head + [COEFFS[mode]] * n + ['hdy_bn_act_fwd_pair']
+    return head + [COEFFS[mode], 'hdy_bn_act_fwd'] * n
+
+
+def check_forward_modes(b):
+    plan = b.plan
+    starts = [i for i, r in enumerate(plan.fwd) if r[0] in UNIT_HEADS]
+    assert len(starts) == len(plan.units) and starts[0] == 0
+    seen = set()
+    for u, i, j in zip(plan.units, starts, starts[1:] + [len(plan.fwd)]):
+        if type(u).__name__ != 'ConvUnit':
+            continue
+        assert arg(plan.fwd[i], 'y') == u.yraw.data_ptr(), 'not this unit\'s convolution'
+        mode, got = plan._bn_fwd_mode(u), [r[0] for r in plan.fwd[i:j]]
+        assert (mode == 'frozen') == u.frozen and (mode == 'sync') == (b.case.sync and not u.frozen), (mode, u.frozen)
+        assert mode != 'pair' or (len(u.mods) == 2 and u.res is None)
+        assert got == forward_symbols(mode, u), (mode, got)
+        seen.add((mode, got[-1]))
+    FWD_SEEN[case_id(b.case)] = seen
+    S.canonical(plan.fwd)                       # raises for a pointer that no tensor the record keeps alive covers
+
+
+def test_forward_records_follow_the_mode(built):
+    check_forward_modes(built)
+
+
+@pytest.mark.parametrize('case', SYNC_CASES, ids=case_id)
+def test_forward_records_follow_the_mode_with_sync_batchnorm(case):
+    check_forward_modes(Built(case))
+
+
+def test_every_forward_mode_and_both_pair_applies_occur():
+    for case in CASES + SYNC_CASES:             # (the two tests above have been over all of them when the whole module runs)
+        if case_id(case) not in FWD_SEEN:
+            check_forward_modes(Built(case))
+    seen = set().union(*(FWD_SEEN[case_id(c)] for c in CASES + SYNC_CASES))
+    assert {m for m, _ in seen} == {'sync', 'pair', 'single', 'frozen'}, seen
+    assert ('pair', 'hdy_bn_act_fwd_pair') in seen and ('sync', 'hdy_bn_act_fwd_pair') in seen, seen
+
+
+def test_every_forward_pointer_is_accounted_for(built):
+    assert len(S.canonical(built.plan.fwd)) == len(built.plan.fwd)
+
+
+def test_compiling_the_forward_again_changes_nothing(built):
+    """every case: an fp32 and two bf16 models among them"""
+    plan = built.plan
+    packs, bn_eval = len(plan.packs.descs), len(plan.bn_eval.descs)
+    again = built.rebuilt_forward()
+    assert again is not plan.fwd and S.canonical(again) == S.canonical(plan.fwd)
+    assert (len(plan.packs.descs), len(plan.bn_eval.descs)) == (packs, bn_eval)
 
 
 # ------------------------------------------------------------------------------------------ b. marks
