@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y
             for (int i = 0; i < VE; ++i) {
                 float u = v[i] * sc[i] + sh[i];
                 if (ACT == 1) u = fast_silu(u);
-                else if (ACT == 2) u = fmaxf(u, 0.0f);
+                else if (ACT == 2) u = u < 0.0f ? 0.0f : u;          // not fmaxf: a NaN must come out as NaN, as from F.relu
                 if (RES) u += r[i];
                 v[i] = u;
             }

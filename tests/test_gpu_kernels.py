@@ -375,7 +375,8 @@ def test_stem_conv(shape, dtype):
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
-# the last three shapes take the one-launch cooperative backward in bf16 (units in registers only / row tail / registers + LDS)
+# every shape runs the three-launch backward (reduce, finalize, apply); a one-launch cooperative form was measured and not adopted (csrc/bn_act.hip).
+# One statistics slab and one column chunk here; more slabs, wider layers and the other activations: tests/test_gpu_bn_direct.py
 @pytest.mark.parametrize('shape', [(2, 20, 20, 64), (3, 9, 7, 48), (1, 4, 4, 512), (16, 40, 40, 64), (5, 37, 40, 256), (48, 40, 40, 256)])
 def test_bn_silu_fwd_bwd(shape, dtype):
     N, H, W, K = shape
