@@ -505,7 +505,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv_deep_kernel(const ConvArgs p) {
                                 for (int r = 0; r < 4; ++r) {
                                     v[r] = v[r] * sc[r] + sh[r];
                                     if (EPI == 2) v[r] = v[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[r]));
-                                    else if (EPI == 3) v[r] = fmaxf(v[r], 0.0f);
+                                    else if (EPI == 3) v[r] = v[r] < 0.0f ? 0.0f : v[r];                // not fmaxf: a NaN stays NaN, as from F.relu
                                 }
                             }
                             union { bf16x4 h; unsigned u[2]; } o;

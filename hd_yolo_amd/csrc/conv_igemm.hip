@@ -429,7 +429,7 @@ __global__ __launch_bounds__(2 * BM, (BM == 256 || BN == 128 || STAT) ? 2 : (BN 
                                     v[r] = acc[a][b][r];
                                     if (AFF) v[r] = v[r] * sc[r] + sh[r];
                                     if (ACT == 1) v[r] = v[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[r]));   // SiLU; 1 ulp, then bf16
-                                    else if (ACT == 2) v[r] = fmaxf(v[r], 0.0f);
+                                    else if (ACT == 2) v[r] = v[r] < 0.0f ? 0.0f : v[r];                 // not fmaxf: a NaN stays NaN, as from F.relu
                                 }
                                 bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
                                 *(bf16x4*)(scratch + row * ROWB + ((slot ^ skey(row)) << 3)) = o;
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(2 * BM, (BM == 256 || BN == 128 || STAT) ? 2 : (BN 
                     if (kc < p.K) {
                         if (affine) v = COEF_LDS ? v * coef[kc - n0] + coef[BN + kc - n0] : v * sc_reg[r] + sh_reg[r];
                         if (p.act == 1) v = silu_f(v);
-                        else if (p.act == 2) v = fmaxf(v, 0.0f);
+                        else if (p.act == 2) v = v < 0.0f ? 0.0f : v;         // not fmaxf: a NaN stays NaN, as from F.relu
                     }
                     v4[r] = v;
                 }

@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
                     const float dy = (relu && u <= 0.f) ? 0.f : d[i];
                     v[i] = k0[i] * dy - k1[i] - ((v[i] - mu[i]) * rs[i]) * k2[i];
                 } else {
-                    v[i] = relu ? fmaxf(u, 0.f) : u;
+                    v[i] = (relu && u < 0.f) ? 0.f : u;                 // not fmaxf: a NaN must come out as NaN, as from F.relu
                 }
             }
             *(i32x4*)(y + m * ldy + c) = pack<T>(v);

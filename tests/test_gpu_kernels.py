@@ -253,6 +253,50 @@ def test_conv_eval_epilogue_with_residual(case):
     assert_close(from_dev_nhwc(y), ref, TOL[dt] * 2, f'{want} epilogue with residual')
 
 
+RELU_NAN_CASES = [
+    # (N, H, W, C, K, R, arithmetic type, expected family, options): one per ReLU epilogue (shapes of RES_CASES)
+    (2, 20, 20, 96, 96, 3, torch.bfloat16, 'igemm_128x128x2', {}),                     # bf16 rows staged through LDS: the template's ACT == 2
+    (2, 20, 20, 48, 48, 1, torch.float32, 'igemm_', {}),                               # fp32 rows: the direct-store epilogue, p.act == 2
+    (3, 40, 40, 128, 128, 3, torch.bfloat16, 'deep_256x128', {'HDY_NO_CONV3X3_C128': 1, 'HDY_DEEP_MIN_TILES': 1}),
+]
+
+
+@pytest.mark.parametrize('case', RELU_NAN_CASES, ids=[f'{c[7]}-{c[3]}x{c[4]}k{c[5]}-{"bf16" if c[6] == torch.bfloat16 else "fp32"}' for c in RELU_NAN_CASES])
+def test_conv_relu_epilogue_lets_nan_through(case):
+    """y = ReLU(scale * conv + shift) with NaN, +Inf and -Inf in three entries of `shift`: those output channels are all NaN (F.relu keeps a NaN;
+    fmaxf(v, 0) would return 0), all +Inf and all 0; every other channel equals the run with a finite shift bit for bit."""
+    from contextlib import ExitStack
+    N, H, W, C, K, R, dt, want, opts = case
+    pad = R // 2
+    x = q(rnd((N, C, H, W), 41), dt)
+    w = rnd((K, C, R, R), 42, (3.0 / (C * R * R)) ** 0.5)
+    sc, sh = rnd((K,), 43).abs() + 0.5, rnd((K,), 44)
+    bad = sh.clone()
+    k_nan, k_pinf, k_ninf = 1, K // 2 + 3, K - 2
+    bad[k_nan], bad[k_pinf], bad[k_ninf] = float('nan'), float('inf'), float('-inf')
+    xd = to_dev_nhwc(x, dt)
+    outs = []
+    with ExitStack() as es:
+        for k, v in opts.items():
+            es.enter_context(_lib.option(k, v))
+        wp = ops.pack_alloc(K, C, R, R, 1, pad, ops.PACK_FWD, dt, DEV)
+        ops.run([ops.rec_pack(w.to(DEV), None, 1, pad, ops.PACK_FWD, wp)])
+        for shift in (sh, bad):
+            y = torch.full((N, H, W, K), 7.0, dtype=dt, device=DEV)
+            _lib.dispatch_log(reset=True)
+            ops.run([ops.rec_conv_fwd(xd, wp, y, K, R, R, 1, pad, scale=sc.to(DEV), shift=shift.to(DEV), act=ops.ACT_RELU)])
+            torch.cuda.synchronize()
+            log = _lib.dispatch_log(reset=True)
+            assert any(n.startswith(want) for n in log), log
+            outs.append(y.float().cpu())
+    good, got = outs
+    assert torch.isfinite(good).all() and (good >= 0).all() and (good == 0).any() and (good > 0).any()
+    assert torch.isnan(got[..., k_nan]).all(), 'a NaN pre-activation came out of the ReLU as a number'
+    assert (got[..., k_pinf] == float('inf')).all() and (got[..., k_ninf] == 0).all()
+    rest = [k for k in range(K) if k not in (k_nan, k_pinf, k_ninf)]
+    assert torch.equal(got[..., rest], good[..., rest])
+
+
 DEEP_CASES = [
     # N, H, W, C, K, R, stride, pad — shapes of the deep-pipelined kernel (C % 64 == 0, K >= 128), small enough for a CPU reference
     (2, 20, 20, 128, 128, 3, 1, 1),      # 4 row tiles, the last one 32 rows; every tile has border pixels
