@@ -36,6 +36,8 @@ SIGNATURES = {
     'hdy_bn_bwd_coeffs_sums': (_I, [_P, _I, _P, _P, _P]),
     'hdy_sgd_blocks': (_I, [_L]),
     'hdy_sgd_step': (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    'hdy_opt_blocks': (_I, [_L]),
+    'hdy_opt_step': (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _F, _F, _P]),
     'hdy_version': (_I, []),
     'hdy_fastdiv_magic': (_I, [ctypes.c_uint, _P, _P]),
     'hdy_conv_out_dim': (_I, [_I, _I, _I, _I]),
@@ -154,6 +156,16 @@ class SgdDesc(ctypes.Structure):
     """mirror of hdy_sgd_desc (include/hdyolo.h)"""
     _fields_ = [('p', c_void_p), ('g', c_void_p), ('buf', c_void_p), ('n', c_longlong), ('group', c_int), ('first', c_int), ('first_block', c_int),
                 ('pad_', c_int)]
+
+
+OPT_SGD, OPT_ADAM, OPT_ADAMW = 0, 1, 2      # HDY_OPT_* (include/hdyolo.h)
+OPT_MAX_SLOTS, OPT_HYPER = 16, 8
+
+
+class OptDesc(ctypes.Structure):
+    """mirror of hdy_opt_desc (include/hdyolo.h)"""
+    _fields_ = [(n, c_void_p) for n in ('p', 'g', 'm', 'v', 'ema')] + [('n', c_longlong), ('slot', c_int), ('first', c_int), ('first_block', c_int),
+                                                                      ('pad_', c_int)]
 
 
 class StatReq(ctypes.Structure):

@@ -93,7 +93,7 @@ const Entry TABLE[] = {
     E(hdy_nms_grid_begin), E(hdy_nms_grid_round), E(hdy_nms_grid_finish), E(hdy_slide_tiles_u8), E(hdy_slide_append), E(hdy_slide_tissue_u8),
     E(hdy_augment_tiles_u8), E(hdy_augment_boxes), E(hdy_augment_mask_extents), E(hdy_augment_boxes_masks), E(hdy_augment_mask_targets),
     E(hdy_ap_match), E(hdy_paste_masks), E(hdy_paste_label_map), E(hdy_label_areas),
-    E(hdy_label_overlap), E(hdy_mask_ap_match), E(hdy_roi_align_levels_fwd), E(hdy_mask_rows),
+    E(hdy_label_overlap), E(hdy_mask_ap_match), E(hdy_roi_align_levels_fwd), E(hdy_mask_rows), E(hdy_opt_step),
 };
 #undef E
 constexpr int NTABLE = (int)(sizeof(TABLE) / sizeof(TABLE[0]));

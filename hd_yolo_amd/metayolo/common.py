@@ -24,6 +24,7 @@ class ModelEMA:
         src = de_parallel(model)
         eng = src.__dict__.pop('_hdy_engine', None)       # plans hold device buffers: never deep-copy them
         self.ema = deepcopy(src).eval()
+        self.src = src                                    # hd_yolo_amd.optim's step(ema=self) averages this model's entries in the optimizer's launch
         if eng is not None:
             object.__setattr__(src, '_hdy_engine', eng)
         self.updates = updates

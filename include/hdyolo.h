@@ -723,6 +723,40 @@ int hdy_sgd_blocks(long long n);
 int hdy_sgd_step(const hdy_sgd_desc* table_device, int ndesc, int total_blocks, const float* lr, const float* momentum, const float* dampening,
                  const float* weight_decay, int ngroups, int nesterov, void* stream);
 
+/* ---- SGD | Adam | AdamW and the weight EMA in one launch (reference: train.py:228-233 the three optimizers, :249 / :480 ModelEMA.update after
+ * every optimizer step, metayolo/common.py:128-155).  Same scheme as hdy_sgd_step: a device table of descriptors, first_block = running sum
+ * of hdy_opt_blocks(n), a block owns 4096 consecutive elements of one row.  A row: fp32 parameter p; gradient g or NULL; first state m (SGD
+ * momentum buffer / Adam exp_avg) or NULL; second state v (Adam exp_avg_sq) or NULL; EMA destination or NULL; first = m / v are
+ * uninitialised: written, not read (as from zeros for Adam, buf = g' for SGD).  g == NULL: an EMA-only row — p, m, v are not written, ema is
+ * updated from p (BatchNorm running statistics, frozen and gradient-less parameters).  A row with g and ema both NULL is a caller error
+ * (nothing is written for it).  16-byte accesses when all of a row's pointers are 16-byte aligned and n % 4 == 0, scalar ones otherwise.
+ *   algo: one of HDY_OPT_* for the whole table.  SGD: the arithmetic of hdy_sgd_step.  Adam / AdamW: torch.optim.adam's single-tensor path,
+ *     AdamW: p *= 1 - lr*wd;  Adam: g += wd*p;  m += (g - m)*(1 - beta1);  v = beta2*v + (1 - beta2)*g*g;
+ *     p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),  bc1 = 1 - beta1^step, bc2 = 1 - beta2^step,
+ *     with fused multiply-adds and correctly rounded division and square root.
+ *   hyper: HOST array of nslots (<= HDY_OPT_MAX_SLOTS) rows of HDY_OPT_HYPER floats, passed by value to the kernel; a slot is one (parameter
+ *     group, step count) pair and a row names its slot.  SGD: {lr, weight_decay, momentum, dampening};  Adam / AdamW: {lr / bc1,
+ *     Adam: weight_decay | AdamW: 1 - lr*weight_decay, 1 - beta1, beta2, 1 - beta2, sqrt(bc2), eps}, each computed in double and rounded once.
+ *   has_ema != 0: rows with an EMA destination get ema = ema_decay * ema + ema_one_minus_decay * (the parameter value just written, or p
+ *     itself on an EMA-only row); has_ema == 0: the ema column is ignored.  nesterov: SGD only. */
+#define HDY_OPT_MAX_SLOTS 16
+#define HDY_OPT_HYPER 8
+#define HDY_OPT_SGD 0
+#define HDY_OPT_ADAM 1
+#define HDY_OPT_ADAMW 2
+typedef struct hdy_opt_desc {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* ema;
+    long long n;
+    int slot, first, first_block, pad_;
+} hdy_opt_desc;
+int hdy_opt_blocks(long long n);
+int hdy_opt_step(const hdy_opt_desc* table_device, int ndesc, int total_blocks, int algo, int nesterov, const float* hyper, int nslots, int has_ema,
+                 float ema_decay, float ema_one_minus_decay, void* stream);
+
 /* ---- launch-list executor (csrc/exec.hip): one call issues a whole precomputed list of launches on two streams — a plan's forward or backward
  * list, whose pointers, shapes and order are fixed (no reference counterpart: the order is the one PyTorch's autograd engine gives the same work,
  * train.py:472).  program = 64-bit words, per item [op][nargs][arg 0]..[arg nargs-1]:

@@ -33,7 +33,7 @@ os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')               # before the HIP r
 os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
 import torch
 import torch.distributed as dist
-from torch.optim import SGD, Adam, AdamW, lr_scheduler
+from torch.optim import lr_scheduler
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -64,13 +64,13 @@ def build_optimizer(model, hyp, name):
             g_bn.append(m.weight)
         elif hasattr(m, 'weight') and isinstance(m.weight, torch.nn.Parameter):
             g_w.append(m.weight)
+    from hd_yolo_amd import optim as fused                     # torch.optim's updates and state layouts, one launch for all tensors (+ the EMA)
     if name == 'Adam':
-        opt = Adam(g_bn, lr=hyp['lr0'], betas=(hyp['momentum'], 0.999))
+        opt = fused.Adam(g_bn, lr=hyp['lr0'], betas=(hyp['momentum'], 0.999))
     elif name == 'AdamW':
-        opt = AdamW(g_bn, lr=hyp['lr0'], betas=(hyp['momentum'], 0.999))
+        opt = fused.AdamW(g_bn, lr=hyp['lr0'], betas=(hyp['momentum'], 0.999))
     else:
-        from hd_yolo_amd.optim import SGD as FusedSGD          # torch.optim.SGD's update and state layout, one launch for all tensors
-        opt = FusedSGD(g_bn, lr=hyp['lr0'], momentum=hyp['momentum'], nesterov=True)
+        opt = fused.SGD(g_bn, lr=hyp['lr0'], momentum=hyp['momentum'], nesterov=True)
     opt.add_param_group({'params': g_w, 'weight_decay': hyp['weight_decay']})
     opt.add_param_group({'params': g_b})
     return opt
@@ -210,10 +210,8 @@ def train(hyp, opt, device):
             loss = sum(v['det_loss'] + (v['mask_loss'] if with_masks and 'mask_loss' in v else 0.0) for v in losses.values())   # train.py:459-462
             loss.backward()
             if ni - last_opt_step >= accumulate:
-                optimizer.step()
+                optimizer.step(ema=ema)                        # train.py:478-480 `optimizer.step(); ema.update(model)` in one launch (ema is None off rank 0)
                 optimizer.zero_grad(set_to_none=True)
-                if ema:
-                    ema.update(model)
                 last_opt_step = ni
             if RANK in (-1, 0) and (i % opt.log_every == 0 or i == nb - 1):
                 for task_id, v in losses.items():
