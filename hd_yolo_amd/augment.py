@@ -10,7 +10,9 @@ import math
 
 import numpy as np
 
-CELL_BYTES = 864                       # HDY_AUG_CELL_BYTES (include/hdyolo.h): 24 words + three 256-byte tables
+from . import _header
+
+CELL_BYTES = _header.read().constants['HDY_AUG_CELL_BYTES']      # 24 words + three 256-byte tables
 F_HFLIP, F_VFLIP, F_TRANSPOSE, F_HSV, F_PERSP = 1, 2, 4, 8, 16
 MAX_K = 8
 MAX_CELLS = 4096                       # B * k * k of one hdy_augment_boxes call

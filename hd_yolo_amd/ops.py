@@ -98,7 +98,7 @@ class SideStream:
 
 
 # ------------------------------------------------------------------------------------------ compiled launch lists (csrc/exec.hip)
-EXEC_FORK, EXEC_JOIN = 0xF0F0F0F0, 0xF0F0F0F1
+EXEC_FORK, EXEC_JOIN = _lib.CONSTANTS['HDY_EXEC_FORK'], _lib.CONSTANTS['HDY_EXEC_JOIN']
 USE_EXEC = os.environ.get('HDY_EXEC', '1') != '0'        # HDY_EXEC=0: every list through the Python loop below (A/B, debugging)
 _M64 = (1 << 64) - 1
 
@@ -179,7 +179,8 @@ class Program:
             op = lib.hdy_exec_op(name.encode())
             types = _lib.SIGNATURES[name][1]
             if op < 0 or len(args) != len(types) - 1:
-                raise _lib.HdyError(f'{name} cannot be listed for hdy_exec_run ({len(args)} arguments recorded, {len(types) - 1} expected)')
+                raise _lib.HdyError(f'{name} cannot be listed for hdy_exec_run ({len(args)} arguments recorded, {len(types) - 1} expected: '
+                                    f'{", ".join(p for p, _ in _lib.PARAMS[name][:-1])})')
             return [op, len(args)] + [_word(v, t) for v, t in zip(args, types)]
 
         def flush():
@@ -448,8 +449,7 @@ class BnEvalTable:
         if not self.descs:
             return
         if self.table is None:
-            raw = b''.join(bytes(d) for d in self.descs)
-            self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
+            self.table = _lib.device_table(self.descs, self.device)
             self.seen = None
         if skip_unchanged and not ALWAYS_REPACK:
             now = _versions(self.keep)
@@ -490,8 +490,7 @@ class PackTable:
         if not self.descs:
             return
         if self.table is None:
-            raw = b''.join(bytes(d) for d in self.descs)
-            self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
+            self.table = _lib.device_table(self.descs, self.device)
             self.seen = None
         if skip_unchanged and not ALWAYS_REPACK:
             now = _versions(self.keep[0::3] + self.keep[1::3])
@@ -791,7 +790,7 @@ def slide_tissue(slide, origins, th, tw, background=220):
 
 
 # ------------------------------------------------------------------------------------------ training augmentation from an 8-bit tile bank
-AUG_CELL_BYTES = 864
+AUG_CELL_BYTES = _lib.CONSTANTS['HDY_AUG_CELL_BYTES']
 
 
 def _tile_bank_u8(tiles):
@@ -820,7 +819,7 @@ def _cell_table(cells, crop, k):
 
 def augment_tiles(tiles, cells, crop, out, patch, k, cval):
     """The augmented batch (hdy_augment_tiles_u8): `out` (B, 3, S, S) fp32 / bf16 contiguous, from the bank `tiles`, the device cell table
-    uint8 (B * k * k, 864) and crop offsets int32 (B, 2) that hd_yolo_amd.augment.cell_tables packs.  No synchronisation."""
+    uint8 (B * k * k, AUG_CELL_BYTES) and crop offsets int32 (B, 2) that hd_yolo_amd.augment.cell_tables packs.  No synchronisation."""
     bp, stride, pitch, pb, n, H, W = _tile_bank_u8(tiles)
     cp, n_cells, rp, B = _cell_table(cells, crop, k)
     require_gpu(out)
@@ -994,7 +993,7 @@ NMS_GRID_MIN = 32768            # nms(): sets of at least this many boxes take t
 #                                 0 = never.  The smallest measured size from which the new path's slowest repeat beats the one-workgroup
 #                                 kernel's fastest at that and every larger measured size, over ALL three set families of
 #                                 profiles/nms_grid_ab.txt; slide-like sets alone cross at 2048, tile-density sets at 8192
-NMS_GRID_MAX = 1 << 24          # HDY_NMS_GRID_MAX_M (include/hdyolo.h)
+NMS_GRID_MAX = _lib.CONSTANTS['HDY_NMS_GRID_MAX_M']
 NMS_GRID_FIRST_ROUNDS = 12      # rounds enqueued before the first look at the undecided counter (random and slide-like sets need 4-10)
 
 
@@ -1065,7 +1064,7 @@ def nms(boxes, scores, iou_thres, max_det=None):
 
 
 # ------------------------------------------------------------------------------------------ detection scoring (csrc/score.hip)
-AP_PRED_BLOCK, AP_TRUE_CHUNK = 256, 256      # HDY_AP_PRED_BLOCK / HDY_AP_TRUE_CHUNK (include/hdyolo.h): predictions per workgroup, truths per chunk
+AP_PRED_BLOCK, AP_TRUE_CHUNK = _lib.CONSTANTS['HDY_AP_PRED_BLOCK'], _lib.CONSTANTS['HDY_AP_TRUE_CHUNK']      # predictions per workgroup, truths per chunk
 AP_MAX_IOU, AP_MAX_IGNORE = 16, 4
 
 
@@ -1125,7 +1124,7 @@ def ap_match(pred_boxes, pred_scores, pred_labels, pred_off, true_boxes, true_la
 
 
 # ------------------------------------------------------------------------------------------ mask paste (csrc/paste.hip)
-PASTE_MIN_M, PASTE_MAX_M = 2, 62             # HDY_PASTE_MIN_M / HDY_PASTE_MAX_M (include/hdyolo.h)
+PASTE_MIN_M, PASTE_MAX_M = _lib.CONSTANTS['HDY_PASTE_MIN_M'], _lib.CONSTANTS['HDY_PASTE_MAX_M']
 
 
 def _paste_inputs(who, masks, boxes, padding):
@@ -1194,7 +1193,7 @@ def label_areas(label_map, R):
 
 
 # ------------------------------------------------------------------------------------------ mask scoring (csrc/mask_score.hip)
-OVERLAP_MIN_SLOTS, OVERLAP_MAX_SLOTS = 64, 1 << 30      # HDY_OVERLAP_MAX_SLOTS (include/hdyolo.h)
+OVERLAP_MIN_SLOTS, OVERLAP_MAX_SLOTS = 64, _lib.CONSTANTS['HDY_OVERLAP_MAX_SLOTS']
 
 
 def _pow2_at_least(n, lo=OVERLAP_MIN_SLOTS):
@@ -1326,11 +1325,7 @@ def roi_align(feat, rois, spatial_scale, P, sampling_ratio=2, aligned=False):
     return out
 
 
-class _RoiLevel(ctypes.Structure):
-    """hdy_roi_level (include/hdyolo.h)"""
-    _fields_ = [('feat', ctypes.c_void_p), ('H', ctypes.c_int), ('W', ctypes.c_int), ('ldf', ctypes.c_int), ('spatial_scale', ctypes.c_float)]
-
-
+_RoiLevel = _lib.RoiLevel
 ROI_LEVELS_MAX, ROI_LEVELS_MAX_B = 8, 1024           # hdy_roi_align_levels_fwd (include/hdyolo.h)
 
 

@@ -115,7 +115,7 @@ class _Fused(torch.optim.Optimizer):
                 dsc.n, dsc.slot, dsc.first, dsc.first_block = p.numel(), slot, int(first), blocks
                 blocks += lib.hdy_opt_blocks(p.numel())
                 key.append((dsc.p or 0, dsc.g or 0, dsc.m or 0, dsc.v or 0, dsc.ema or 0, slot, first))
-            self._otable = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(rows[0][0].device)
+            self._otable = _lib.device_table(descs, rows[0][0].device)
             self._ondesc, self._oblocks = len(rows), blocks
             self.table_builds += 1
             # a table with first-step rows is valid for this step only
@@ -159,8 +159,7 @@ class SGD(_Fused):
             d.p, d.g, d.buf = p.data_ptr(), g.data_ptr(), (buf.data_ptr() if buf is not None else None)
             d.n, d.group, d.first, d.first_block = p.numel(), gi, int(first), blocks
             blocks += lib.hdy_sgd_blocks(p.numel())
-        host = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8)
-        self._table, self._ndesc, self._blocks = host.to(dev), len(rows), blocks
+        self._table, self._ndesc, self._blocks = _lib.device_table(descs, dev), len(rows), blocks
 
     @torch.no_grad()
     def step(self, closure=None, ema=None):

@@ -62,6 +62,13 @@ def prototypes(path=HEADER):
     return _protos[path]
 
 
+def return_types(path=HEADER):
+    """{symbol: the text of its return type}, read the same way: a prototype starts its line with the return type"""
+    text = re.sub(r'/\*.*?\*/', '', open(path).read(), flags=re.S)
+    text = re.sub(r'//[^\n]*', '', text)
+    return {name: ' '.join(ret.split()) for ret, name in re.findall(r'^((?:const )?[a-z_ ]+?\**)\s*\b(hdy_[a-z0-9_]+)\s*\(', text, flags=re.M)}
+
+
 def record(symbol, **kw):
     """A hand-made launch record of `symbol`: parameters by the header's names, tensors for pointers (kept by the record, as ops._rec does),
     everything not named 0 / NULL.  The trailing stream is not part of a record."""

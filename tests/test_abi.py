@@ -1,5 +1,6 @@
 """CPU-side checks of the C-ABI boundary: the library builds for gfx950, loads, and exports every symbol
-include/hdyolo.h declares with a ctypes signature registered in hd_yolo_amd/_lib.py.  No compute calls."""
+include/hdyolo.h declares, each with the ctypes signature hd_yolo_amd/_lib.py derives from that header (declared_symbols below stays an
+independent reading of it).  No compute calls."""
 import os
 import re
 

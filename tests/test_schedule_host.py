@@ -125,15 +125,33 @@ def lib():
     return _lib.load()
 
 
+# what the binding must hold for a type as the header writes it (`const` removed); any pointer but `char*` is c_void_p
+SCALAR_KINDS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'long long': ctypes.c_longlong, 'unsigned long long': ctypes.c_ulonglong,
+                'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double, 'char*': ctypes.c_char_p, 'void': None}
+
+
+def kind_of(ctype):
+    words = ' '.join(w for w in ctype.replace('*', ' * ').split() if w != 'const').replace(' *', '*')
+    return SCALAR_KINDS[words] if words in SCALAR_KINDS else ctypes.c_void_p if words.endswith('*') else words
+
+
 def test_prototypes_agree_with_the_ctypes_signatures(lib):
-    """every entry point a launch list can hold: the header's pointer parameters are the binding's c_void_p parameters, position by position"""
-    protos = S.prototypes()
+    """every function the header declares, read by this file's own reader: the binding's restype and argtypes are the header's types, position
+    by position — pointers as c_void_p (c_char_p for strings), every scalar by its own kind"""
+    protos, returns = S.prototypes(), S.return_types()
+    assert sorted(protos) == sorted(returns) == sorted(_lib.SIGNATURES) and len(protos) >= 112
+    assert kind_of('const float* const*') is ctypes.c_void_p and kind_of('const char *') is ctypes.c_char_p and kind_of('short') == 'short'
+    for name, params in protos.items():
+        restype, types = _lib.SIGNATURES[name]
+        assert kind_of(returns[name]) is restype, (name, returns[name])
+        assert len(params) == len(types), (name, params)
+        assert [p.pointer for p in params] == [t in (ctypes.c_void_p, ctypes.c_char_p) for t in types], (name, params)
+        assert [kind_of(p.ctype) for p in params] == types, (name, params)
+        assert [(p.name, p.const) for p in params] == _lib.PARAMS[name], name
     listed = [n for n in _lib.SIGNATURES if lib.hdy_exec_op(n.encode()) >= 0]
     assert len(listed) >= 40
     for name in listed:
-        params, types = protos[name], _lib.SIGNATURES[name][1]
-        assert len(params) == len(types), (name, params)
-        assert [p.pointer for p in params] == [t in (ctypes.c_void_p, ctypes.c_char_p) for t in types], (name, params)
+        params = protos[name]
         assert params[-1].name == 'stream' and not params[-1].const
     # spot checks of what footprint() relies on: names, const-ness, the request array
     w = {p.name: p for p in protos['hdy_conv_wgrad']}
