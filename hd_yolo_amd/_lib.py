@@ -30,7 +30,7 @@ ACT_NONE, ACT_SILU, ACT_RELU = (CONSTANTS['HDY_ACT_' + n] for n in ('NONE', 'SIL
 OPT_SGD, OPT_ADAM, OPT_ADAMW = (CONSTANTS['HDY_OPT_' + n] for n in ('SGD', 'ADAM', 'ADAMW'))
 OPT_MAX_SLOTS, OPT_HYPER = CONSTANTS['HDY_OPT_MAX_SLOTS'], CONSTANTS['HDY_OPT_HYPER']
 
-PackDesc, BnEvalDesc, SgdDesc = STRUCTS['hdy_pack_desc'], STRUCTS['hdy_bn_eval_desc'], STRUCTS['hdy_sgd_desc']
+PackDesc, BnEvalDesc = STRUCTS['hdy_pack_desc'], STRUCTS['hdy_bn_eval_desc']
 OptDesc, StatReq, RoiLevel = STRUCTS['hdy_opt_desc'], STRUCTS['hdy_stat_req'], STRUCTS['hdy_roi_level']
 
 

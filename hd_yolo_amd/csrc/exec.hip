@@ -89,7 +89,7 @@ const Entry TABLE[] = {
     E(hdy_nms_boxes), E(hdy_roi_align_fwd), E(hdy_roi_align_bwd), E(hdy_relu_bwd), E(hdy_cast_store), E(hdy_det_loss), E(hdy_mask_select),
     E(hdy_det_targets), E(hdy_scale_inplace), E(hdy_groupnorm_fwd), E(hdy_groupnorm_bwd), E(hdy_bilinear_fwd), E(hdy_bilinear_bwd),
     E(hdy_bilinear_bwd_axis), E(hdy_softdice), E(hdy_softdice_wgrad), E(hdy_softmax2d), E(hdy_conv_wgrad_stem_fused), E(hdy_bn_slab_sums),
-    E(hdy_bn_finalize_sums), E(hdy_bn_bwd_coeffs_sums), E(hdy_sgd_step), E(hdy_copy_f32), E(hdy_det_loss_ex),
+    E(hdy_bn_finalize_sums), E(hdy_bn_bwd_coeffs_sums), E(hdy_copy_f32), E(hdy_det_loss_ex),
     E(hdy_nms_grid_begin), E(hdy_nms_grid_round), E(hdy_nms_grid_finish), E(hdy_slide_tiles_u8), E(hdy_slide_append), E(hdy_slide_tissue_u8),
     E(hdy_augment_tiles_u8), E(hdy_augment_boxes), E(hdy_augment_mask_extents), E(hdy_augment_boxes_masks), E(hdy_augment_mask_targets),
     E(hdy_ap_match), E(hdy_paste_masks), E(hdy_paste_label_map), E(hdy_label_areas),

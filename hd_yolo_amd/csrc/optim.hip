@@ -1,20 +1,31 @@
-// SGD with momentum / Nesterov / weight decay over MANY parameter tensors in ONE launch (reference: train.py:208-233 builds
-// torch.optim.SGD(nesterov=True) with three parameter groups and steps it at train.py:478; torch's multi-tensor path is ~25 launches of
-// 5-25 us for yolov5s' 180 tensors).
+// SGD | Adam | AdamW over MANY parameter tensors, plus the weight EMA, in ONE launch: hdy_opt_step (reference: train.py:208-233 builds one of
+// the three optimizers over three parameter groups and steps it at train.py:478; :249 / :480 ModelEMA.update after every step,
+// common.py:128-155; torch's multi-tensor SGD alone is ~25 launches of 5-25 us for yolov5s' 180 tensors).
 //
-//   g' = g + wd * p;   buf = first ? g' : momentum * buf + (1 - dampening) * g';   p -= lr * (nesterov ? g' + momentum * buf : buf)
+// The table.  One device row per tensor (hdy_opt_desc: parameter, gradient, two states, EMA destination, length, slot, first, first block),
+// built once and replayed while no pointer moves.  A block owns 4096 consecutive elements of one tensor and finds its row by binary search over
+// the first-block column.  g == NULL makes an EMA-only row (BatchNorm running statistics, frozen or gradient-less parameters).  The
+// hyper-parameters travel by value, one slot per (parameter group, step count): the warm-up rewrites them every step and the table stays.
+// The algorithm and "the table has EMA destinations" are template parameters: uniform over the launch, otherwise tested per element.
 //
-// A device table of descriptors (pointer triple, length, group, first block) is built once; a block owns 4096 consecutive elements of one
-// tensor and finds its descriptor by binary search over the first-block column.  The per-group hyper-parameters travel by value (the
-// warm-up changes them every step), so the table is replayed unchanged.  Pure HBM streaming: 5 passes of 4 bytes per parameter.
+// The arithmetic.  SGD as torch.optim.SGD, in plain expressions compiled with -ffp-contract=off:
+//   g' = g + wd*p;   buf = first ? g' : momentum*buf + (1 - dampening)*g';   p -= lr * (nesterov ? g' + momentum*buf : buf)
+// Adam as torch.optim.adam's single-tensor path, with explicit fused multiply-adds and correctly rounded division / square root, so the
+// result does not depend on compiler flags:
+//   AdamW: p *= 1 - lr*wd;  Adam: g += wd*p;  m += (g - m)*(1 - beta1);  v = beta2*v + (1 - beta2)*g*g;
+//   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// and the EMA of what was just written: ema = d*ema + (1 - d)*p.
+//
+// Pure HBM streaming: p, g, m (, v, ema) are each read once and p, m (, v, ema) written once.  SGD 20 B per parameter, 28 B with the EMA;
+// Adam 28 B, 36 B with the EMA; 12 B per EMA-only entry.
 #include "common.h"
 #include "hdyolo.h"
 
 namespace {
 
-constexpr int SGD_BLOCK_ELEMS = 4096;
+constexpr int OPT_BLOCK_ELEMS = 4096;
 
-// the SGD update of one element, shared by sgd_step_kernel and the SGD instantiation of opt_step_kernel (damp = 1 - dampening)
+// one element of SGD (damp = 1 - dampening; has_buf: the row has a momentum buffer)
 __device__ __forceinline__ void sgd_update(float pv, float gv, float bv, float& po, float& bo, float lr, float mom, float damp, float wd, bool has_buf,
                                            int first, int nesterov) {
     if (wd != 0.0f) gv = gv + wd * pv;
@@ -25,60 +36,6 @@ __device__ __forceinline__ void sgd_update(float pv, float gv, float bv, float& 
     po = pv - lr * gv;
 }
 
-struct SgdHyper { float lr[HDY_SGD_MAX_GROUPS], momentum[HDY_SGD_MAX_GROUPS], dampening[HDY_SGD_MAX_GROUPS], wd[HDY_SGD_MAX_GROUPS]; };
-
-__global__ __launch_bounds__(256) void sgd_step_kernel(const hdy_sgd_desc* __restrict__ table, int ndesc, SgdHyper h, int nesterov) {
-    int lo = 0, hi = ndesc - 1;                           // last descriptor whose first_block <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const hdy_sgd_desc d = table[lo];
-    const long long base = (long long)((int)blockIdx.x - d.first_block) * SGD_BLOCK_ELEMS;
-    const float lr = h.lr[d.group], mom = h.momentum[d.group], damp = 1.0f - h.dampening[d.group], wd = h.wd[d.group];
-    float* __restrict__ p = d.p;
-    const float* __restrict__ g = d.g;
-    float* __restrict__ b = d.buf;
-    auto upd = [&](float pv, float gv, float bv, float& po, float& bo) { sgd_update(pv, gv, bv, po, bo, lr, mom, damp, wd, b != nullptr, d.first, nesterov); };
-    const bool vec = (d.n & 3) == 0 && ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)b)) & 15) == 0;
-    if (vec) {
-#pragma unroll
-        for (int r = 0; r < SGD_BLOCK_ELEMS / 1024; ++r) {
-            const long long i = base + (long long)(r * 256 + (int)threadIdx.x) * 4;
-            if (i >= d.n) break;
-            const f32x4 pv = *(const f32x4*)(p + i), gv = *(const f32x4*)(g + i);
-            const f32x4 bv = (b && !d.first) ? *(const f32x4*)(b + i) : f32x4{0.f, 0.f, 0.f, 0.f};
-            f32x4 po, bo = bv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float pe, be = bv[e];
-                upd(pv[e], gv[e], bv[e], pe, be);
-                po[e] = pe;
-                bo[e] = be;
-            }
-            *(f32x4*)(p + i) = po;
-            if (b) *(f32x4*)(b + i) = bo;
-        }
-    } else {
-        for (int r = 0; r < SGD_BLOCK_ELEMS / 256; ++r) {
-            const long long i = base + r * 256 + (int)threadIdx.x;
-            if (i >= d.n) break;
-            float po, bo = 0.f;
-            upd(p[i], g[i], (b && !d.first) ? b[i] : 0.f, po, bo);
-            p[i] = po;
-            if (b) b[i] = bo;
-        }
-    }
-}
-
-// ---- hdy_opt_step: SGD | Adam | AdamW plus the weight EMA (reference: train.py:228-233 optimizers, :249 / :480 ModelEMA, common.py:128-155) in
-// one launch.  Same table scheme as above; a row adds the second state and the EMA destination, and g == NULL makes it an EMA-only row
-// (BatchNorm running statistics, frozen or gradient-less parameters).  The algorithm and "the table has EMA destinations" are template
-// parameters: they are uniform over the launch and would otherwise be tested per element.  Adam follows torch.optim.adam's single-tensor
-// path with explicit fused multiply-adds and correctly rounded division / square root, so the result does not depend on compiler flags:
-//   AdamW: p *= 1 - lr*wd;  Adam: g += wd*p;  m += (g - m)*(1 - beta1);  v = beta2*v + (1 - beta2)*g*g;
-//   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps);        ema = d*ema + (1 - d)*p
-// 28 B (SGD) / 36 B (Adam) per parameter with the EMA: p, g, m (, v) and ema are each read once and p, m (, v), ema written once.
 struct OptHyper {
     float v[HDY_OPT_MAX_SLOTS][HDY_OPT_HYPER];
     float ema_d, ema_omd;
@@ -93,7 +50,7 @@ __global__ __launch_bounds__(256) void opt_step_kernel(const hdy_opt_desc* __res
         if (table[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
     }
     const hdy_opt_desc d = table[lo];
-    const long long base = (long long)((int)blockIdx.x - d.first_block) * SGD_BLOCK_ELEMS;
+    const long long base = (long long)((int)blockIdx.x - d.first_block) * OPT_BLOCK_ELEMS;
     const float* hv = h.v[d.slot];
     const float h0 = hv[0], h1 = hv[1], h2 = hv[2], h3 = hv[3], h4 = hv[4], h5 = hv[5], h6 = hv[6];
     float* __restrict__ p = d.p;
@@ -122,7 +79,7 @@ __global__ __launch_bounds__(256) void opt_step_kernel(const hdy_opt_desc* __res
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     if (vec) {
 #pragma unroll
-        for (int r = 0; r < SGD_BLOCK_ELEMS / 1024; ++r) {
+        for (int r = 0; r < OPT_BLOCK_ELEMS / 1024; ++r) {
             const long long i = base + (long long)(r * 256 + (int)threadIdx.x) * 4;
             if (i >= d.n) break;
             f32x4 po = *(const f32x4*)(p + i);
@@ -150,7 +107,7 @@ __global__ __launch_bounds__(256) void opt_step_kernel(const hdy_opt_desc* __res
             }
         }
     } else {
-        for (int r = 0; r < SGD_BLOCK_ELEMS / 256; ++r) {
+        for (int r = 0; r < OPT_BLOCK_ELEMS / 256; ++r) {
             const long long i = base + r * 256 + (int)threadIdx.x;
             if (i >= d.n) break;
             float po = p[i];
@@ -174,7 +131,7 @@ void opt_launch(bool has_ema, int blocks, hipStream_t stream, const hdy_opt_desc
 
 }  // namespace
 
-extern "C" int hdy_opt_blocks(long long n) { return (int)((n + SGD_BLOCK_ELEMS - 1) / SGD_BLOCK_ELEMS); }
+extern "C" int hdy_opt_blocks(long long n) { return (int)((n + OPT_BLOCK_ELEMS - 1) / OPT_BLOCK_ELEMS); }
 
 extern "C" int hdy_opt_step(const hdy_opt_desc* table_device, int ndesc, int total_blocks, int algo, int nesterov, const float* hyper, int nslots,
                             int has_ema, float ema_decay, float ema_one_minus_decay, void* stream) {
@@ -193,18 +150,5 @@ extern "C" int hdy_opt_step(const hdy_opt_desc* table_device, int ndesc, int tot
     else if (algo == HDY_OPT_ADAM) opt_launch<HDY_OPT_ADAM>(has_ema != 0, total_blocks, s, table_device, ndesc, h);
     else opt_launch<HDY_OPT_ADAMW>(has_ema != 0, total_blocks, s, table_device, ndesc, h);
     HDY_LAUNCH_CHECK("opt_step");
-    return HDY_OK;
-}
-
-extern "C" int hdy_sgd_blocks(long long n) { return (int)((n + SGD_BLOCK_ELEMS - 1) / SGD_BLOCK_ELEMS); }
-
-extern "C" int hdy_sgd_step(const hdy_sgd_desc* table_device, int ndesc, int total_blocks, const float* lr, const float* momentum,
-                            const float* dampening, const float* weight_decay, int ngroups, int nesterov, void* stream) {
-    HDY_ARG(table_device && ndesc > 0 && total_blocks > 0, "sgd_step: empty table");
-    HDY_ARG(ngroups > 0 && ngroups <= HDY_SGD_MAX_GROUPS && lr && momentum && dampening && weight_decay, "sgd_step: 1..%d parameter groups", HDY_SGD_MAX_GROUPS);
-    SgdHyper h = {};
-    for (int i = 0; i < ngroups; ++i) { h.lr[i] = lr[i]; h.momentum[i] = momentum[i]; h.dampening[i] = dampening[i]; h.wd[i] = weight_decay[i]; }
-    hipLaunchKernelGGL(sgd_step_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, table_device, ndesc, h, nesterov);
-    HDY_LAUNCH_CHECK("sgd_step");
     return HDY_OK;
 }

@@ -1,4 +1,4 @@
-"""torch.optim.SGD's update as ONE HIP launch over all parameter tensors (csrc/optim.hip).
+"""torch.optim.SGD's update as ONE HIP launch over all parameter tensors (csrc/optim.hip, `hdy_opt_step`).
 
 Drop-in for the optimizer the reference builds (train.py:208-233: `SGD(g0, lr, momentum, nesterov=True)` + `add_param_group` for the
 decayed weights and the biases; train.py:436-444 rewrites `lr` / `momentum` of every group during the warm-up; train.py:478 steps
@@ -6,9 +6,10 @@ it): same constructor arguments, `param_groups`, `state[p]['momentum_buffer']` a
 either class load into the other.  Parameters and gradients must be contiguous fp32 CUDA tensors (the engine's gradients are views of
 one flat fp32 buffer); anything else raises — there is no fallback path.
 
-`Adam` / `AdamW` (train.py:229-231) are the same for torch.optim.Adam / AdamW, and every class takes `step(ema=ModelEMA)`: the launch that writes a
-parameter also writes its exponential moving average (train.py:480 `ema.update(model)` after every step; common.py:128-155), and the
-BatchNorm running statistics, frozen and gradient-less parameters ride along as EMA-only rows (`hdy_opt_step`)."""
+`Adam` / `AdamW` (train.py:229-231) are the same for torch.optim.Adam / AdamW, through the same launch and the same `step()`.  Every class
+takes `step(ema=ModelEMA)`: the launch that writes a parameter also writes its exponential moving average (train.py:480 `ema.update(model)`
+after every step; common.py:128-155), and the BatchNorm running statistics, frozen and gradient-less parameters ride along as EMA-only rows.
+One launch serves `HDY_OPT_MAX_SLOTS` (16) distinct (parameter group, step count) pairs; more raise."""
 import ctypes
 
 import torch
@@ -21,12 +22,13 @@ def _fp32_cuda(*tensors):
 
 
 class _Fused(torch.optim.Optimizer):
-    """The hdy_opt_step side of the three classes: rows, slots, the cached device table, the EMA rows, the launch.
+    """What the three classes share: step(), the rows, slots and cached device table of hdy_opt_step, the EMA rows, the launch.
 
-    A subclass names its algorithm (`_algo`) and gives `_state_rows(group, p)` -> (m, v, first, step count of this step, the state dict whose
-    'step' follows it or None) without touching `self.state`; `_commit` makes missing states once every check has passed, so a refused step
-    leaves no half-made state behind.  Host cost: while the pointers stand still a step is one pass over the tensors that reads their
-    addresses, compares them with the cached table's and moves the integer step counts — no tensor operation per parameter."""
+    A subclass names its algorithm (`_algo` -> (HDY_OPT_*, nesterov), which also raises for what the class does not serve) and gives `_state_rows(group, p)` -> (m, v,
+    first, step count of this step, the state dict whose 'step' follows it or None) without touching `self.state`; `_commit` makes missing
+    states once every check has passed, so a refused step leaves no half-made state behind.  Host cost: while the pointers stand still a step
+    is one pass over the tensors that reads their addresses, compares them with the cached table's and moves the integer step counts — no
+    tensor operation per parameter."""
     _what = 'hd_yolo_amd.optim'
 
     def _init_fused(self):
@@ -61,12 +63,23 @@ class _Fused(torch.optim.Optimizer):
                     pairs[id(s)] = (s, e)
         return pairs
 
-    def _opt_step(self, ema=None):
+    @torch.no_grad()
+    def step(self, closure=None, ema=None):
+        """One step of every parameter that has a gradient; with `ema` (a ModelEMA) the same launch averages the model into it, as
+        `ema.update(model)` after the step would"""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._opt_step(ema)
+        return loss
+
+    def _opt_step(self, ema):
         lib = _lib.load()
         pairs = self._ema_pairs(ema) if ema is not None else {}
-        # row: (p, g, m, v, e, slot, first, group, new step count, state[p] or None); key: the row's pointers, slot and `first`
-        # wrote: what the kernel writes, for the version counters
-        rows, key, slots, wrote = [], [], {}, []
+        # rows: (p, g, m, v, e, slot, first, group, step count) of every table row;  key: the row's pointers, slot and `first`, what the device
+        # table holds;  counts: (state dict, its new step count);  wrote: what the kernel writes, for the version counters
+        rows, key, counts, slots, wrote = [], [], [], {}, []
         for gi, group in enumerate(self.param_groups):
             for p in group['params']:
                 g = p.grad
@@ -76,9 +89,11 @@ class _Fused(torch.optim.Optimizer):
                 slot = slots.setdefault((gi, step), len(slots))
                 pair = pairs.pop(id(p), None) if pairs else None
                 e = None if pair is None else pair[1]
-                rows.append((p, g, m, v, e, slot, first, group, step, st))
+                rows.append((p, g, m, v, e, slot, first, group, step))
                 key.append((p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), 0 if v is None else v.data_ptr(),
                             0 if e is None else e.data_ptr(), slot, first))
+                if st is not None:
+                    counts.append((st, step))
                 wrote.append(p)
                 if m is not None:
                     wrote.append(m)
@@ -87,39 +102,38 @@ class _Fused(torch.optim.Optimizer):
                 if e is not None:
                     wrote.append(e)
         for s, e in pairs.values():               # buffers, frozen parameters, parameters without a gradient in this step
-            rows.append((s, None, None, None, e, 0, False, None, 0, None))
+            rows.append((s, None, None, None, e, 0, False, None, 0))
             key.append((s.data_ptr(), 0, 0, 0, e.data_ptr(), 0, False))
             wrote.append(e)
         if not rows:
             return
         if len(slots) > _lib.OPT_MAX_SLOTS:
             raise ValueError(f'{self._what}: {len(slots)} distinct (parameter group, step count) pairs, one launch serves {_lib.OPT_MAX_SLOTS}')
-        algo, nesterov = self._algo(), int(self._nesterov())
+        (algo, nesterov), dev = self._algo(), rows[0][0].device
         if key == self._okey:
             # the table of the last step serves: same tensors (checked when it was built), every state exists; only the step counts move
-            for r in rows:
-                if r[9] is not None:
-                    r[9]['step'] = r[8]
+            for st, step in counts:
+                st['step'] = step
         else:
             for p, g, m, v, e, *_ in rows:
                 if not _fp32_cuda(*[t for t in (p, g, m, v, e) if t is not None]) or (e is not None and e.numel() != p.numel()):
                     raise TypeError(f'{self._what} needs contiguous fp32 CUDA parameters, gradients, states and EMA entries (of the parameter\'s size)')
             ptr = lambda t: None if t is None else t.data_ptr()
-            descs, blocks, key = (_lib.OptDesc * len(rows))(), 0, []
-            for dsc, (p, g, m, v, e, slot, first, group, step, st) in zip(descs, rows):
+            descs, blocks, fresh = (_lib.OptDesc * len(rows))(), 0, False
+            for dsc, (p, g, m, v, e, slot, first, group, step) in zip(descs, rows):
                 if g is not None:
                     m, v = self._commit(group, p, m, v, step)
                     if first:
+                        fresh = True
                         wrote += [t for t in (m, v) if t is not None]
                 dsc.p, dsc.g, dsc.m, dsc.v, dsc.ema = ptr(p), ptr(g), ptr(m), ptr(v), ptr(e)
                 dsc.n, dsc.slot, dsc.first, dsc.first_block = p.numel(), slot, int(first), blocks
                 blocks += lib.hdy_opt_blocks(p.numel())
-                key.append((dsc.p or 0, dsc.g or 0, dsc.m or 0, dsc.v or 0, dsc.ema or 0, slot, first))
-            self._otable = _lib.device_table(descs, rows[0][0].device)
+            self._otable = _lib.device_table(descs, dev)
             self._ondesc, self._oblocks = len(rows), blocks
             self.table_builds += 1
-            # a table with first-step rows is valid for this step only
-            self._okey = None if any(k[6] for k in key) else key
+            # a table with first-step rows serves that step only (their states were made just now: the key above does not name them)
+            self._okey = None if fresh else key
         nslots = max(1, len(slots))
         hyper = (ctypes.c_float * (_lib.OPT_HYPER * nslots))()
         for (gi, step), slot in slots.items():
@@ -129,16 +143,13 @@ class _Fused(torch.optim.Optimizer):
         if ema is not None:
             ema.updates += 1
             d = ema.decay(ema.updates)
-        rc = lib.hdy_opt_step(self._otable.data_ptr(), self._ondesc, self._oblocks, algo, nesterov, hyper, nslots, int(ema is not None), d, 1 - d,
-                              torch.cuda.current_stream(rows[0][0].device).cuda_stream)
+        rc = lib.hdy_opt_step(self._otable.data_ptr(), self._ondesc, self._oblocks, algo, int(nesterov), hyper, nslots, int(ema is not None), d, 1 - d,
+                              torch.cuda.current_stream(dev).cuda_stream)
         if rc:
             raise _lib.HdyError(f'hdy_opt_step failed (status {rc}): {lib.hdy_last_error().decode()}')
         # raw-pointer writes: every `_version`-keyed cache (segrun.PackCache, ops.PackTable, ops.BnEvalTable — val.run(ema.ema) goes through them)
         # must see the parameters, the state and the EMA entries change, as after an in-place torch update
         torch._C._increment_version(wrote)
-
-    def _nesterov(self):
-        return False
 
 
 class SGD(_Fused):
@@ -148,83 +159,18 @@ class SGD(_Fused):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError('Nesterov momentum requires a momentum and zero dampening')
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov))
-        self._key, self._table, self._ndesc, self._blocks = None, None, 0, 0
         self._init_fused()
 
-    def _build(self, rows, dev):
-        lib = _lib.load()
-        descs = (_lib.SgdDesc * len(rows))()
-        blocks = 0
-        for d, (p, g, buf, gi, first) in zip(descs, rows):
-            d.p, d.g, d.buf = p.data_ptr(), g.data_ptr(), (buf.data_ptr() if buf is not None else None)
-            d.n, d.group, d.first, d.first_block = p.numel(), gi, int(first), blocks
-            blocks += lib.hdy_sgd_blocks(p.numel())
-        self._table, self._ndesc, self._blocks = _lib.device_table(descs, dev), len(rows), blocks
-
-    @torch.no_grad()
-    def step(self, closure=None, ema=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        if ema is not None:
-            self._opt_step(ema)
-            return loss
-        if len(self.param_groups) > 8:
-            raise ValueError('hd_yolo_amd.optim.SGD: at most 8 parameter groups')
-        nesterov = {bool(g['nesterov']) for g in self.param_groups}
-        if len(nesterov) != 1:
-            raise ValueError('hd_yolo_amd.optim.SGD: nesterov must be the same in every parameter group')
-        rows, key, dev = [], [], None
-        for gi, group in enumerate(self.param_groups):
-            for p in group['params']:
-                g = p.grad
-                if g is None:
-                    continue
-                if not (p.is_cuda and g.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous()):
-                    raise TypeError('hd_yolo_amd.optim.SGD needs contiguous fp32 CUDA parameters and gradients')
-                dev = p.device
-                st = self.state[p]
-                buf, first = st.get('momentum_buffer'), False
-                if group['momentum'] != 0 and buf is None:
-                    buf = st['momentum_buffer'] = torch.empty_like(p, memory_format=torch.contiguous_format)
-                    first = True
-                if group['momentum'] == 0:
-                    buf = None
-                rows.append((p, g, buf, gi, first))
-                key.append((p.data_ptr(), g.data_ptr(), 0 if buf is None else buf.data_ptr(), gi, first))
-        if not rows:
-            return loss
-        if key != self._key:
-            self._build(rows, dev)
-            # a table with first-step rows is valid for this step only
-            self._key = None if any(r[4] for r in rows) else key
-        n = len(self.param_groups)
-        arr = lambda name: (ctypes.c_float * n)(*[float(g[name]) for g in self.param_groups])
-        lib = _lib.load()
-        rc = lib.hdy_sgd_step(self._table.data_ptr(), self._ndesc, self._blocks, arr('lr'), arr('momentum'), arr('dampening'), arr('weight_decay'),
-                              n, int(nesterov.pop()), torch.cuda.current_stream(dev).cuda_stream)
-        if rc:
-            raise _lib.HdyError(f'hdy_sgd_step failed (status {rc}): {lib.hdy_last_error().decode()}')
-        # the kernel wrote the parameters through raw pointers: tell autograd / every `_version`-keyed cache (segrun.PackCache, ops.PackTable,
-        # ops.BnEvalTable) that they changed, as an in-place torch update would have
-        torch._C._increment_version([p for p, _, _, _, _ in rows] + [buf for _, _, buf, _, _ in rows if buf is not None])
-        return loss
-
-    # ---- step(ema=...): the same update through hdy_opt_step, one slot per parameter group
     def _algo(self):
-        return _lib.OPT_SGD
-
-    def _nesterov(self):
         nesterov = {bool(g['nesterov']) for g in self.param_groups}
         if len(nesterov) != 1:
             raise ValueError('hd_yolo_amd.optim.SGD: nesterov must be the same in every parameter group')
-        return nesterov.pop()
+        return _lib.OPT_SGD, nesterov.pop()
 
     def _state_rows(self, group, p):
         if group['momentum'] == 0:
             return None, None, False, 0, None
-        buf = self.state[p].get('momentum_buffer')
+        buf = self.state.get(p, {}).get('momentum_buffer')
         return buf, None, buf is None, 0, None
 
     def _commit(self, group, p, m, v, step):
@@ -258,21 +204,12 @@ class Adam(_Fused):
             if on:
                 raise ValueError(f'{self._what} does not support {", ".join(on)}')
 
-    @torch.no_grad()
-    def step(self, closure=None, ema=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._unsupported()                                   # a loaded state_dict or add_param_group may have switched one on
-        self._opt_step(ema)
-        return loss
-
     def _algo(self):
+        self._unsupported()                                   # a loaded state_dict or add_param_group may have switched one on
         decoupled = {bool(g.get('decoupled_weight_decay', False)) for g in self.param_groups}
         if len(decoupled) != 1:
             raise ValueError(f'{self._what}: decoupled_weight_decay must be the same in every parameter group')
-        return _lib.OPT_ADAMW if decoupled.pop() else _lib.OPT_ADAM
+        return (_lib.OPT_ADAMW if decoupled.pop() else _lib.OPT_ADAM), False
 
     def _state_rows(self, group, p):
         st = self.state.get(p)

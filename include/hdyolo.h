@@ -46,7 +46,7 @@ const char* hdy_last_error(void);
 /* ABI revision of THIS header: bumped whenever an entry point's parameter list, a structure or an option changes meaning.  hdy_version() returns the
  * value the library was built with; a binding written against another revision must refuse the library (hd_yolo_amd/_lib.py:load does) — with
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
-#define HDY_ABI_VERSION 14
+#define HDY_ABI_VERSION 15
 int hdy_version(void);
 /* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
@@ -706,31 +706,17 @@ int hdy_bn_finalize_sums(const double* sums, int sums_ld, const double* count, i
                          float* scale, float* shift, float* save_mean, float* save_invstd, void* stream);
 int hdy_bn_bwd_coeffs_sums(const double* sums, int K, float* c1, float* c2, void* stream);
 
-/* ---- optimizer step of the training loop (reference: train.py:208-233 torch.optim.SGD(momentum, nesterov=True) in three parameter
- * groups, stepped at train.py:478).  One launch for all tensors: a device table of descriptors (fp32 parameter, gradient, momentum
- * buffer or NULL, element count, parameter group, first = the buffer is uninitialised: buf = g'), first_block = running sum of
- * hdy_sgd_blocks(n).  g' = g + wd*p; buf = momentum*buf + (1-dampening)*g'; p -= lr * (nesterov ? g' + momentum*buf : buf).
- * lr / momentum / dampening / weight_decay: HOST arrays of ngroups (<= HDY_SGD_MAX_GROUPS) values, passed by value to the kernel. */
-#define HDY_SGD_MAX_GROUPS 8
-typedef struct hdy_sgd_desc {
-    float* p;
-    const float* g;
-    float* buf;
-    long long n;
-    int group, first, first_block, pad_;
-} hdy_sgd_desc;
-int hdy_sgd_blocks(long long n);
-int hdy_sgd_step(const hdy_sgd_desc* table_device, int ndesc, int total_blocks, const float* lr, const float* momentum, const float* dampening,
-                 const float* weight_decay, int ngroups, int nesterov, void* stream);
-
-/* ---- SGD | Adam | AdamW and the weight EMA in one launch (reference: train.py:228-233 the three optimizers, :249 / :480 ModelEMA.update after
- * every optimizer step, metayolo/common.py:128-155).  Same scheme as hdy_sgd_step: a device table of descriptors, first_block = running sum
- * of hdy_opt_blocks(n), a block owns 4096 consecutive elements of one row.  A row: fp32 parameter p; gradient g or NULL; first state m (SGD
- * momentum buffer / Adam exp_avg) or NULL; second state v (Adam exp_avg_sq) or NULL; EMA destination or NULL; first = m / v are
- * uninitialised: written, not read (as from zeros for Adam, buf = g' for SGD).  g == NULL: an EMA-only row — p, m, v are not written, ema is
- * updated from p (BatchNorm running statistics, frozen and gradient-less parameters).  A row with g and ema both NULL is a caller error
- * (nothing is written for it).  16-byte accesses when all of a row's pointers are 16-byte aligned and n % 4 == 0, scalar ones otherwise.
- *   algo: one of HDY_OPT_* for the whole table.  SGD: the arithmetic of hdy_sgd_step.  Adam / AdamW: torch.optim.adam's single-tensor path,
+/* ---- optimizer step of the training loop and the weight EMA in one launch: SGD | Adam | AdamW (reference: train.py:208-233 builds one of the
+ * three over three parameter groups, stepped at train.py:478; :249 / :480 ModelEMA.update after every optimizer step,
+ * metayolo/common.py:128-155).  One launch for all tensors: a device table of descriptors, first_block = running sum of hdy_opt_blocks(n),
+ * a block owns 4096 consecutive elements of one row.  A row: fp32 parameter p; gradient g or NULL; first state m (SGD momentum buffer / Adam
+ * exp_avg) or NULL; second state v (Adam exp_avg_sq) or NULL; EMA destination or NULL; first = m / v are uninitialised: written, not read (as
+ * from zeros for Adam, buf = g' for SGD).  g == NULL: an EMA-only row — p, m, v are not written, ema is updated from p (BatchNorm running
+ * statistics, frozen and gradient-less parameters).  A row with g and ema both NULL is a caller error (nothing is written for it).  16-byte
+ * accesses when all of a row's pointers are 16-byte aligned and n % 4 == 0, scalar ones otherwise.
+ *   algo: one of HDY_OPT_* for the whole table.
+ *     SGD: torch.optim.SGD, g' = g + wd*p; buf = momentum*buf + (1-dampening)*g'; p -= lr * (nesterov ? g' + momentum*buf : buf); m == NULL:
+ *     no momentum, p -= lr*g'.  Adam / AdamW: torch.optim.adam's single-tensor path,
  *     AdamW: p *= 1 - lr*wd;  Adam: g += wd*p;  m += (g - m)*(1 - beta1);  v = beta2*v + (1 - beta2)*g*g;
  *     p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),  bc1 = 1 - beta1^step, bc2 = 1 - beta2^step,
  *     with fused multiply-adds and correctly rounded division and square root.

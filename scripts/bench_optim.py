@@ -1,7 +1,7 @@
 """Optimizer step + weight EMA on yolov5s' real parameter set: the one-launch path (hd_yolo_amd.optim `step(ema=ema)`, csrc/optim.hip hdy_opt_step)
 against the path it replaces, alternated (reference: train.py:478-480 `optimizer.step(); ema.update(model)` with train.py:228-233's optimizers).
 
-  parent  SGD: hd_yolo_amd.optim.SGD.step() (hdy_sgd_step) + ModelEMA.update;  Adam / AdamW: torch.optim's step + ModelEMA.update
+  parent  SGD: hd_yolo_amd.optim.SGD.step() + ModelEMA.update (two calls, the step's launch without the EMA);  Adam / AdamW: torch.optim's step + ModelEMA.update
   fused   hd_yolo_amd.optim.{SGD, Adam, AdamW}.step(ema=ema)
 
 Gradients are views of one flat buffer, as the engine hands them out (engine.GradStore).  Per optimizer and alternation: time per step between

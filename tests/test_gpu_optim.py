@@ -1,4 +1,4 @@
-"""hd_yolo_amd.optim.Adam / AdamW and step(ema=...) of all three classes (csrc/optim.hip, hdy_opt_step) on a real MI355X, against the float64
+"""hd_yolo_amd.optim.SGD / Adam / AdamW, step() and step(ema=...) (csrc/optim.hip, hdy_opt_step) on a real MI355X, against the float64
 restatement of tests/optim_ref.py, with torch.optim on the GPU as the yardstick for what fp32 can give.
 
 Shapes: lengths 1, 3, 4, 5 (scalar tail), 4095 / 4096 / 4097 (block boundary), 8196 (three blocks, a partial last one), a (64, 32, 3, 3)
@@ -6,6 +6,9 @@ filter, a 4100-element view at storage offset 1 (4-byte aligned only: scalar pat
 gradient in step 2 (two step counts in one group: two slots).  Three parameter groups as train.py builds them, weight decay on the second,
 lr (and SGD's momentum) rewritten before every step."""
 import copy
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -141,24 +144,52 @@ def test_adam_is_as_close_to_float64_as_torch(name):
     assert of.state[bf.ps[LATE]]['step'] == 3 and of.state[bf.ps[0]]['step'] == 5
 
 
-def test_sgd_through_the_new_entry_is_bit_identical():
-    ba, bb = Bag(), Bag()
-    oa, ob = make_opt(SGD, ba, **KW['SGD']), make_opt(SGD, bb, **KW['SGD'])
-    ema = ModelEMA(bb)
+def sha256(tensors):
+    """one SHA-256 over the raw fp32 bytes of the tensors, in order"""
+    h = hashlib.sha256()
+    for t in tensors:
+        assert t.dtype == torch.float32
+        h.update(t.detach().contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
+def sgd_bits(with_ema=False):
+    """Four SGD steps of the recipe above, as digests: {'initial_parameters', 'steps': [{'gradients', 'parameters': one per tensor of bag.ps,
+    'momentum_buffers': one per tensor, None where it has none}]}.  tests/golden/make_golden_optim_sgd.py recorded optim_sgd_bits.json with it."""
+    bag = Bag()
+    opt = make_opt(SGD, bag, **KW['SGD'])
+    step_kw = {'ema': ModelEMA(bag)} if with_ema else {}
+    out = {'initial_parameters': sha256(bag.ps), 'steps': []}
     for step in range(4):
-        warm_up(oa, step), warm_up(ob, step)
-        set_grads(ba, step), set_grads(bb, step)
-        oa.step()
-        ob.step(ema=ema)
-        for i, (a, b) in enumerate(zip(ba.ps, bb.ps)):
-            assert torch.equal(a, b), (step, i)
-            sa, sb = oa.state.get(a, {}).get('momentum_buffer'), ob.state.get(b, {}).get('momentum_buffer')
-            assert (sa is None) == (sb is None) and (sa is None or torch.equal(sa, sb)), (step, i)
-            assert (sa is None) == (i in GROUPS[2] or (i == LATE and step < 2))
-    assert ob.table_builds > 0 and oa.table_builds == 0      # one went through hdy_opt_step, the other through hdy_sgd_step
+        warm_up(opt, step)
+        set_grads(bag, step)
+        grads = sha256([p.grad for p in bag.ps if p.grad is not None])
+        opt.step(**step_kw)
+        bufs = [opt.state.get(p, {}).get('momentum_buffer') for p in bag.ps]
+        out['steps'].append({'gradients': grads, 'parameters': [sha256([p]) for p in bag.ps],
+                             'momentum_buffers': [None if b is None else sha256([b]) for b in bufs]})
+    return out
 
 
-@pytest.mark.parametrize('name', ['Adam', 'AdamW'])
+def test_sgd_bits_are_those_of_the_retired_kernel():
+    """SGD.step() gives, bit for bit, what the SGD-only `sgd_step_kernel` (retired with ABI revision 15) gave on the same recipe at the last
+    commit that had it: tests/golden/optim_sgd_bits.json, written there by tests/golden/make_golden_optim_sgd.py"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'optim_sgd_bits.json')) as f:
+        want = json.load(f)
+    got = sgd_bits()
+    assert len(got['steps']) == len(want['steps']) == 4
+    inputs = lambda bits: [bits['initial_parameters']] + [s['gradients'] for s in bits['steps']]
+    assert inputs(got) == inputs(want), 'the inputs no longer reproduce (initial parameters or gradients of the recipe): this says nothing about the update'
+    for step, (g, w) in enumerate(zip(got['steps'], want['steps'])):
+        assert len(g['parameters']) == len(w['parameters']) == len(SHAPES) + 2
+        for i, (a, b) in enumerate(zip(g['parameters'], w['parameters'])):
+            assert a == b, f'step {step}: parameter {i} differs from the retired kernel\'s'
+        for i, (a, b) in enumerate(zip(g['momentum_buffers'], w['momentum_buffers'])):
+            assert (b is None) == (i in GROUPS[2] or (i == LATE and step < 2)), (step, i)
+            assert a == b, f'step {step}: momentum buffer {i} differs from the retired kernel\'s'
+
+
+@pytest.mark.parametrize('name', ['SGD', 'Adam', 'AdamW'])
 def test_the_ema_does_not_change_the_update(name):
     """rank 0 steps with the EMA, the other ranks without (train.py): their parameters and states must stay the same bits"""
     ba, bb = Bag(), Bag()
@@ -174,7 +205,13 @@ def test_the_ema_does_not_change_the_update(name):
             sa, sb = oa.state.get(a), ob.state.get(b)
             assert bool(sa) == bool(sb), (step, i)
             if sa:
-                assert sa['step'] == sb['step'] and torch.equal(sa['exp_avg'], sb['exp_avg']) and torch.equal(sa['exp_avg_sq'], sb['exp_avg_sq']), (step, i)
+                assert list(sa) == list(sb), (step, i)
+                for k, x in sa.items():
+                    assert torch.equal(x, sb[k]) if torch.is_tensor(x) else x == sb[k], (step, i, k)
+            if name == 'SGD':                                 # no buffer for the momentum-free group, nor for the late parameter before step 2
+                assert (not sa) == (i in GROUPS[2] or (i == LATE and step < 2)), (step, i)
+                assert not sa or list(sa) == ['momentum_buffer']
+    assert oa.table_builds > 0 and ob.table_builds > 0
 
 
 def ema_snapshot(ema):
@@ -348,24 +385,24 @@ def test_what_is_not_served_raises():
                 cls([p], **{k: True})
     for bad in (torch.nn.Parameter(torch.zeros(4)), torch.nn.Parameter(torch.zeros(4, device=DEV, dtype=torch.float16))):
         bad.grad = torch.zeros_like(bad)
-        for cls in (Adam, AdamW):
-            opt = cls([bad])
+        for cls, kw in ((Adam, {}), (AdamW, {}), (SGD, {}), (SGD, dict(momentum=0.9))):
+            opt = cls([bad], **kw)
             with pytest.raises(TypeError):
                 opt.step()
             assert not opt.state
     many = [torch.nn.Parameter(torch.zeros(4, device=DEV)) for _ in range(_lib.OPT_MAX_SLOTS + 1)]
-    opt = AdamW([{'params': [q]} for q in many])
     for q in many:
         q.grad = torch.ones_like(q)
-    with pytest.raises(ValueError, match='17 distinct'):
-        opt.step()
-    assert not opt.state and all(float(q.detach().sum()) == 0 for q in many)          # refused before anything was made or written
+    for cls, kw in ((AdamW, {}), (SGD, dict(lr=0.1)), (SGD, dict(lr=0.1, momentum=0.9))):
+        opt = cls([{'params': [q]} for q in many], **kw)
+        with pytest.raises(ValueError, match='17 distinct'):
+            opt.step()
+        assert not opt.state and all(float(q.detach().sum()) == 0 for q in many)      # refused before anything was made or written
     with pytest.raises(TypeError, match='ModelEMA'):
         AdamW([p]).step(ema=object())
 
 
-@pytest.mark.parametrize('name', ['SGD', 'Adam', 'AdamW'])
-def test_repeats_are_bit_identical(name):
+def repeat_runs(name, with_ema):
     runs = []
     for _ in range(2):
         bag = Bag(convs=True)
@@ -374,8 +411,18 @@ def test_repeats_are_bit_identical(name):
         for step in range(3):
             warm_up(opt, step)
             set_grads(bag, step)
-            opt.step(ema=ema)
+            opt.step(ema=ema if with_ema else None)
         out = [p.detach().clone() for p in bag.trained()] + [v.clone() for v in ema.ema.state_dict().values()]
         out += [t.clone() for p in bag.trained() for t in opt.state.get(p, {}).values() if torch.is_tensor(t)]
         runs.append(out)
     assert len(runs[0]) == len(runs[1]) and all(torch.equal(a, b) for a, b in zip(*runs))
+
+
+@pytest.mark.parametrize('name', ['SGD', 'Adam', 'AdamW'])
+def test_repeats_are_bit_identical(name):
+    repeat_runs(name, True)
+
+
+@pytest.mark.parametrize('name', ['SGD', 'Adam', 'AdamW'])
+def test_repeats_without_the_ema_are_bit_identical(name):
+    repeat_runs(name, False)

@@ -33,10 +33,10 @@ def levels_call(lib, table=None, nl=3, C=32, boxes=FAKE, level=FAKE, nex=1, n_ke
     return lib.hdy_roi_align_levels_fwd(tp, nl, C, boxes, level, nex, n_keep, B, max_det, P, S, aligned, out, out_rows, dtype, None)
 
 
-def test_revision_14_in_header_binding_and_library(lib):
+def test_revision_15_in_header_binding_and_library(lib):
     header = open(os.path.join(ROOT, 'include', 'hdyolo.h')).read()
-    assert int(re.search(r'#define\s+HDY_ABI_VERSION\s+(\d+)', header).group(1)) == 14
-    assert _lib.ABI_VERSION == 14 and lib.hdy_version() == 14
+    assert int(re.search(r'#define\s+HDY_ABI_VERSION\s+(\d+)', header).group(1)) == 15
+    assert _lib.ABI_VERSION == 15 and lib.hdy_version() == 15
     for name in ('hdy_roi_align_levels_fwd', 'hdy_mask_rows'):
         assert name in _lib.SIGNATURES and hasattr(lib, name) and lib.hdy_exec_op(name.encode()) >= 0
     assert ctypes.sizeof(ops._RoiLevel) == 24       # hdy_roi_level: pointer, three ints, one float
