@@ -15,7 +15,7 @@ hot path.  Timing brackets exactly what the reference brackets (
 synchronisation on both sides because HIP launches are asynchronous.
 
     python evaluation.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--weights w.pt] [--slide 2048 [--u8] [--min-tissue 0.05] [--score] [--masks --label-map]]
-    (--score with --masks --label-map also scores the synthetic sets as segmentations: score_slide_masks, mask mAP@.5)
+    (--score with --masks --label-map also scores the synthetic sets as segmentations: score_slide_masks, mask mAP@.5, PQ / AJI / Dice)
 """
 import argparse
 import os
@@ -372,15 +372,24 @@ def _slide_stats(hit, live, ps, pl, tl, iouv, ignore):
 
 
 @torch.no_grad()
-def score_slide_masks(result, truth, iouv=None, ignore=(-100, -1)):
+def slide_segmentation_summary(stats, pred_labels, true_labels, nc=None):
+    """PQ / SQ / DQ / mPQ / AJI / Dice and the counts behind them (metayolo.models.metrics.segmentation_counts) from score_slide_masks'
+    'pairs', 'pred_area' and 'true_area'; one device-to-host copy (and, with nc=None, one read of the largest label)"""
+    from metayolo.models.metrics import segmentation_counts, segmentation_counts_to_host, segmentation_ratios
+    c = segmentation_counts_to_host(segmentation_counts(stats['pairs'], stats['pred_area'], stats['true_area'], pred_labels, true_labels, nc=nc))
+    return {**segmentation_ratios(c), **c}
+
+
+@torch.no_grad()
+def score_slide_masks(result, truth, iouv=None, ignore=(-100, -1), summaries=False):
     """Scores one task's whole-slide segmentation on mask IoU: `result` as inference_on_slide(..., compute_masks=True, label_map=True) returns it
     ({'label_map' int32 (H, W) with -1 background and else the owning row, 'scores', 'labels'}) against the slide's annotation
     ({'label_map' int32 (H, W) with negative background and else the object's row, 'labels'}), all device tensors.  Both sides are disjoint, so
     the mask IoU of every overlapping pair comes from one streaming pass over the two maps (ops.label_overlap: no dense (n_true, n_pred, H * W)
     product as in the reference's get_mask_ious) and the matching of APMeter from one more call (ops.mask_ap_match).  Returns score_slide's
     stats dict ('match' is the row of the matched object or -1) plus 'pred_area', 'true_area' (int32 pixels per row) and 'pairs' ((n, 3) int64:
-    detection, object, shared pixels), device tensors, from which a caller can form Dice / PQ / AJI.  One device-to-host read before the
-    curves (the overlap status)."""
+    detection, object, shared pixels), device tensors.  summaries=True adds 'pq', 'sq', 'dq', 'mpq', 'aji', 'dice' and their counts
+    (slide_segmentation_summary), formed from those.  One device-to-host read before the curves (the overlap status)."""
     from hd_yolo_amd import ops
     iouv = torch.linspace(0.5, 0.95, 10) if iouv is None else iouv
     if result['labels'].dim() != 1 or truth['labels'].dim() != 1:
@@ -393,6 +402,8 @@ def score_slide_masks(result, truth, iouv=None, ignore=(-100, -1)):
     hit, live, match, miou = ops.mask_ap_match(pairs, pa, ta, ps, pl, tl, iouv, ignore=ignore)
     stats = _slide_stats(hit, live, ps, pl, tl, iouv, ignore)
     stats.update(match=match, match_iou=miou, hit=hit, live=live, pred_area=pa, true_area=ta, pairs=pairs)
+    if summaries:
+        stats.update(slide_segmentation_summary(stats, pl, tl))
     return stats
 
 
@@ -487,6 +498,9 @@ def main():
                 torch.cuda.synchronize()
                 print(f'mask score: {len(ps)} detections x {len(tl)} truths on a {opt.slide} x {opt.slide} label map, {len(sm["pairs"])} overlapping pairs, '
                       f'mask mAP@.5 {float(sm["ap"][:, 0].mean()):.4f} in {(time.time() - t0) * 1e3:.1f} ms')
+                seg = slide_segmentation_summary(sm, pl[order], tl, nc=opt.nc)
+                print(f'mask summaries: PQ {seg["pq"]:.4f} SQ {seg["sq"]:.4f} DQ {seg["dq"]:.4f} mPQ {seg["mpq"]:.4f} AJI {seg["aji"]:.4f} Dice {seg["dice"]:.4f} '
+                      f'(tp {seg["tp"]} fp {seg["fp"]} fn {seg["fn"]})')
 
 
 if __name__ == '__main__':

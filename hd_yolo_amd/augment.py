@@ -188,6 +188,7 @@ class TileBank:
         self.n, self.H, self.W = n, tiles.shape[1], tiles.shape[2]
         self.nc = int(labels.max()) if len(labels) else 0
         self.device = None
+        self.path = None                       # load() records where the bank came from, for messages
         self.instances, self.has_mask = None, None
         if instances is not None:
             self.instances, self.has_mask = self._check_instances(np.asarray(instances))
@@ -225,7 +226,9 @@ class TileBank:
             missing = [key for key in ('tiles', 'boxes', 'labels', 'offsets') if key not in z.files]
             if missing:
                 raise ValueError(f'tile bank {path}: missing arrays {missing}')
-            return cls(z['tiles'], z['boxes'], z['labels'], z['offsets'], z['instances'] if 'instances' in z.files else None)
+            bank = cls(z['tiles'], z['boxes'], z['labels'], z['offsets'], z['instances'] if 'instances' in z.files else None)
+        bank.path = str(path)
+        return bank
 
     def save(self, path):
         extra = {} if self.instances is None else {'instances': self.instances}

@@ -1,6 +1,7 @@
 """Synthetic tile stream with the reference loader's batch schema (reference: metayolo/datasets.py:462-519 target dict,
 :850-870 create_dataloader, engines/torch_utils.py:172 collate).  BASELINE.json's workload is synthetic 640x640 RGB tiles;
-the reference's CSV/cv2/albumentations pipeline is CPU image I/O and out of scope."""
+the reference's CSV/cv2/albumentations pipeline is CPU image I/O and out of scope.  DeviceTiles trains from an 8-bit
+tile bank with the augmentation on the device; BankTiles validates on one, in order and unaugmented."""
 import torch
 
 from hd_yolo_amd import synth
@@ -152,3 +153,99 @@ class DeviceTiles:
             if i + 1 < self.steps:
                 self._issue(i + 1, self.slots[(i + 1) % 2])
             yield self._hand_out(self.slots[i % 2])
+
+
+def bank_batches(n, batch_size):
+    """[(first, count)] of tiles 0 .. n - 1 in batches of batch_size: ceil(n / batch_size) of them, the last one partial"""
+    if batch_size < 1:
+        raise ValueError(f'batch_size={batch_size}')
+    return [(first, min(batch_size, n - first)) for first in range(0, n, batch_size)]
+
+
+def bank_origins(n, H):
+    """the bank as one slide of n * H rows: tile t starts at (x0, y0) = (0, t * H); int32 (n, 2)"""
+    import numpy as np
+    out = np.zeros((n, 2), np.int32)
+    out[:, 1] = np.arange(n, dtype=np.int64) * H
+    return out
+
+
+def bank_name(bank):
+    path = getattr(bank, 'path', None)
+    return f'tile bank {path}' if path else f'tile bank ({bank.n} tiles of {bank.H} x {bank.W})'
+
+
+def check_bank_stride(bank, stride):
+    """A validation bank runs at its own tile size (there is no resize), so both tile sides must be multiples of the model's largest stride."""
+    stride = int(stride)
+    for side, name in ((bank.H, 'height'), (bank.W, 'width')):
+        if side % stride:
+            raise ValueError(f'{bank_name(bank)}: tile {name} {side} is not a multiple of the model\'s largest stride {stride} '
+                             '(validation runs a bank at its own tile size)')
+
+
+class BankTiles:
+    """Validation batches from an 8-bit tile bank (hd_yolo_amd.augment.TileBank) at the bank's own tile size: tile 0 .. n - 1 in order,
+    ceil(n / batch_size) batches with the last one partial, no augmentation, no resize, no filtering of small boxes, no shuffling
+    (set_epoch is a no-op).  Iterable like SyntheticTiles: yields (imgs, targets), imgs a tuple of (3, H, W) float32 tensors equal to
+    tile.permute(2, 0, 1).float() / 255 (the correctly rounded quotient that hdy_slide_tiles_u8 writes), targets the per-image dicts of the
+    reference's schema with device tensors: 'boxes' (n_t, 4) fp32 xyxy in PIXELS (the reference validates with normalize_box=augment, i.e.
+    off) and 'labels' (n_t,) int64, views of the uploaded bank.  A bank with an instance map and masks=True (the default) adds
+    'instances', the tile's (H, W) 16-bit map as DeviceAPMeter.add_batch_masks takes it — the bank's bits, a view; masks=True on a bank
+    without `instances` silently gives box-only targets.
+
+    For the 8-bit forward (Model.forward_tiles) the loader is also the bank as one slide: `slide` = d_tiles viewed (n * H, W, C), `origins`
+    the int32 device table of (0, t * H), `tile` = (H, W), built once, and u8_batches() yields ((first, count), targets) without making a
+    float batch; val_nuclei.run takes that path when handed a BankTiles.  check_stride(stride) refuses tile sides that are no multiple of
+    a model's largest stride (where the model is known: val_nuclei.run and the command lines)."""
+
+    def __init__(self, bank, batch_size, device='cuda', task='det', masks=True):
+        self.bank, self.batch_size, self.task = bank, int(batch_size), task
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        if bank.device != self.device:
+            bank.to(self.device)
+        self.masks = bool(masks) and getattr(bank, 'instances', None) is not None
+        n, H, W, C = bank.d_tiles.shape
+        if not bank.d_tiles.is_contiguous():
+            raise ValueError(f'{bank_name(bank)}: {C}-byte pixels with strides {tuple(bank.d_tiles.stride())}: the tiles must be contiguous to be '
+                             f'read as one slide of {n * H} rows')
+        self.batches = bank_batches(n, self.batch_size)
+        self.tile = (H, W)
+        self.slide = bank.d_tiles.view(n * H, W, C)
+        self.origins = torch.from_numpy(bank_origins(n, H)).to(self.device)
+        self._size = torch.tensor([H, W], dtype=torch.int64)
+        self._offsets = [int(v) for v in bank.offsets]
+        import numpy as np
+        self._quotients = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(self.device)
+
+    def set_epoch(self, epoch):
+        pass
+
+    def __len__(self):
+        return len(self.batches)
+
+    def check_stride(self, stride):
+        check_bank_stride(self.bank, stride)
+
+    def _targets(self, first, count):
+        bank, o = self.bank, self._offsets
+        out = []
+        for t in range(first, first + count):
+            ann = {'size': self._size, 'boxes': bank.d_boxes[o[t]:o[t + 1]], 'labels': bank.d_labels[o[t]:o[t + 1]]}
+            if self.masks:
+                ann['instances'] = bank.d_instances[t]
+            out.append({'image_id': torch.tensor([t], dtype=torch.int64), 'size': self._size, 'anns': {self.task: [ann]}})
+        return tuple(out)
+
+    def u8_batches(self):
+        """((first, count), targets) per batch: tiles [first, first + count) of `slide` / `origins`"""
+        for first, count in self.batches:
+            yield (first, count), self._targets(first, count)
+
+    def __iter__(self):
+        for first, count in self.batches:
+            # byte / 255 through a table of the 256 correctly rounded quotients: a device division by a scalar multiplies by its reciprocal
+            x = self._quotients[self.bank.d_tiles[first:first + count, :, :, :3].permute(0, 3, 1, 2).to(torch.int32)]
+            yield tuple(x.unbind(0)), self._targets(first, count)

@@ -3,7 +3,8 @@
 (pinned by tests/golden/apmeter.npz); DeviceAPMeter does the same matching on the device (csrc/score.hip) for batches and whole
 slides, and shares the curve arithmetic (ap_curves).  Mask IoU: get_mask_ious defines the name the reference's APMeter.add calls without
 defining it (metrics.py:275; the function is utils_nucls.py:480-489), for the host meter's iou_type='masks'; on the device
-DeviceAPMeter.add_batch_masks scores label maps (csrc/mask_score.hip)."""
+DeviceAPMeter.add_batch_masks scores label maps (csrc/mask_score.hip).  segmentation_counts / segmentation_ratios form PQ, AJI and Dice from the
+same overlap pairs (torch tensor ops, any device; no reference counterpart: the reference's validation stops at pasting the masks)."""
 import numpy as np
 import torch
 
@@ -148,6 +149,97 @@ def ap_curves(hit, scores, y_pred, y_true, iouv, ignore, eps=1e-16):
     return out
 
 
+SEG_COUNT_KEYS = ('tp', 'fp', 'fn', 'iou_sum', 'C', 'U', 'inter_sum', 'pred_sum', 'true_sum')     # what pools by addition
+
+
+def segmentation_counts(pairs, pred_area, true_area, pred_labels=None, true_labels=None, nc=None):
+    """The counts behind PQ, AJI and Dice of two disjoint instance segmentations, from their sparse overlap as ops.label_overlap returns it:
+    pairs (n, 3) int64 rows (p, t, inter > 0) sorted by (p, t), pred_area / true_area the pixels per row.  An instance is a row with
+    area > 0.  Torch tensor ops on the device of `pairs` (CPU included): no host read, no loop over rows.  Returns 0-dim tensors, int64
+    unless noted:
+      inter_sum, pred_sum, true_sum   Dice = 2 inter_sum / (pred_sum + true_sum)
+      tp, fp, fn, iou_sum (float64)   PQ (Kirillov et al. 2019): a pair with IoU > 0.5, decided as 3 inter > area_p + area_t, is unique for
+                                      both of its rows; iou_sum adds inter / (area_p + area_t - inter) over them; fp / fn are the instances
+                                      of either side in no such pair.  DQ = tp / (tp + fp / 2 + fn / 2), SQ = iou_sum / tp, PQ = DQ SQ
+      C, U                            AJI = C / U (Kumar et al. 2017; a prediction may serve several truths): every truth with a pair takes
+                                      the pair of highest IoU, ties to the lowest p, and adds its intersection to C and its union to U;
+                                      a truth without a pair adds its area to U, and so does every prediction that no truth took.  IoUs are
+                                      compared exactly, inter union' against inter' union in int64 (areas below 2^31: products below 2^63)
+    With both label arrays (one label per row) also tp_c, fp_c, fn_c and iou_sum_c, (nc,) tensors for classes 1..nc: a pair counts for
+    class c when both labels are c, fp_c / fn_c are the instances of label c not counted in tp_c.  nc=None takes the largest label, which
+    is a host read.  All of them pool over images by addition (SEG_COUNT_KEYS); segmentation_ratios forms the quotients."""
+    dev = pairs.device
+    p, t, inter = pairs[:, 0], pairs[:, 1], pairs[:, 2]
+    pa, ta = pred_area.reshape(-1).to(torch.int64), true_area.reshape(-1).to(torch.int64)
+    n, n_pred, n_true = pairs.shape[0], pa.numel(), ta.numel()
+    ap, at = pa[p], ta[t]
+    union = ap + at - inter
+    is_tp = 3 * inter > ap + at
+    iou = inter.double() / union.double()
+    tp = is_tp.sum()
+    out = {'tp': tp, 'fp': (pa > 0).sum() - tp, 'fn': (ta > 0).sum() - tp, 'iou_sum': torch.where(is_tp, iou, iou.new_zeros(())).sum(),
+           'inter_sum': inter.sum(), 'pred_sum': pa.sum(), 'true_sum': ta.sum()}
+
+    # AJI: the best pair of every truth as a segmented maximum over the pairs in (t, p) order.  best[k] is the winner among the pairs of
+    # k's truth in a window that ends at k; every round doubles the window (the order "higher IoU, then lower p" is total, so overlapping
+    # windows do no harm).  A truth has at most n_pred pairs, which bounds the rounds by log2 of a shape: nothing is read.
+    order = torch.sort(t, stable=True).indices
+    ts, bp, bi, bu = t[order], p[order], inter[order], union[order]
+    d = 1
+    while d < min(n, n_pred):
+        ci, cu, cp = bi[:-d], bu[:-d], bp[:-d]
+        lhs, rhs = ci * bu[d:], bi[d:] * cu
+        take = (ts[d:] == ts[:-d]) & ((lhs > rhs) | ((lhs == rhs) & (cp < bp[d:])))
+        ni, nu, np_ = bi.clone(), bu.clone(), bp.clone()
+        ni[d:], nu[d:], np_[d:] = torch.where(take, ci, bi[d:]), torch.where(take, cu, bu[d:]), torch.where(take, cp, bp[d:])
+        bi, bu, bp = ni, nu, np_
+        d *= 2
+    last = torch.ones((n,), dtype=torch.int64, device=dev)          # the last pair of a truth holds the winner of all its pairs
+    last[:-1] = (ts[1:] != ts[:-1]).to(torch.int64)
+    taken = torch.zeros((n_pred,), dtype=torch.int64, device=dev).index_add_(0, bp, last) > 0
+    paired = torch.zeros((n_true,), dtype=torch.int64, device=dev).index_add_(0, t, torch.ones_like(t)) > 0
+    out['C'] = (bi * last).sum()
+    out['U'] = (bu * last).sum() + (ta * ~paired).sum() + (pa * ~taken).sum()
+
+    if pred_labels is not None and true_labels is not None:
+        lp, lt = pred_labels.reshape(-1).to(dev, torch.int64), true_labels.reshape(-1).to(dev, torch.int64)
+        if nc is None:
+            nc = int(max(lp.max() if n_pred else 0, lt.max() if n_true else 0, 0))
+        per_class = lambda labels, weight: torch.zeros((nc + 1,), dtype=weight.dtype, device=dev).index_add_(   # noqa: E731
+            0, torch.where((labels >= 1) & (labels <= nc), labels, torch.zeros_like(labels)), weight)[1:]
+        both = is_tp & (lp[p] == lt[t])
+        tp_c = per_class(lp[p], both.to(torch.int64))
+        out.update(tp_c=tp_c, fp_c=per_class(lp, (pa > 0).to(torch.int64)) - tp_c, fn_c=per_class(lt, (ta > 0).to(torch.int64)) - tp_c,
+                   iou_sum_c=per_class(lp[p], torch.where(both, iou, iou.new_zeros(()))))
+    return out
+
+
+def segmentation_counts_to_host(counts):
+    """a dict of device tensors (segmentation_counts, or sums of it) as Python ints / floats and numpy arrays, through ONE copy"""
+    if not counts:
+        return {}
+    flat = torch.cat([v.reshape(-1) if v.dtype == torch.int64 else v.reshape(-1).double().view(torch.int64) for v in counts.values()]).cpu().numpy()
+    out, at = {}, 0
+    for k, v in counts.items():
+        part = flat[at:at + v.numel()]
+        at += v.numel()
+        part = part if v.dtype == torch.int64 else part.view(np.float64)
+        out[k] = part.copy() if v.dim() else (int(part[0]) if v.dtype == torch.int64 else float(part[0]))
+    return out
+
+
+def segmentation_ratios(c):
+    """PQ / SQ / DQ / AJI / Dice (and mPQ when the per-class counts are there) from host counts; a ratio with denominator 0 is 0.0, as
+    val_nuclei.summarize_stats reports an empty meter.  mPQ is the mean of PQ_c over the classes with an instance on either side."""
+    div = lambda a, b: float(a) / float(b) if b else 0.0   # noqa: E731
+    dq, sq = div(c['tp'], c['tp'] + 0.5 * c['fp'] + 0.5 * c['fn']), div(c['iou_sum'], c['tp'])
+    out = {'pq': dq * sq, 'sq': sq, 'dq': dq, 'aji': div(c['C'], c['U']), 'dice': div(2 * c['inter_sum'], c['pred_sum'] + c['true_sum'])}
+    if 'tp_c' in c:
+        pq_c = [div(i, tp + 0.5 * fp + 0.5 * fn) for i, tp, fp, fn in zip(c['iou_sum_c'], c['tp_c'], c['fp_c'], c['fn_c']) if tp + fp + fn > 0]
+        out['mpq'] = sum(pq_c) / len(pq_c) if pq_c else 0.0
+    return out
+
+
 class APMeter:
     """Dataset-level detection AP with the reference's accumulation and matching rules (metayolo/models/metrics.py:251-375).
 
@@ -266,6 +358,7 @@ class DeviceAPMeter:
     def reset(self):
         self._batches = []          # per batch: device tensors (scores, labels, hit, live, pred_off, true_labels, true_off)
         self._host_cache = None
+        self._seg = None            # add_batch_masks: the pooled segmentation_counts, device tensors
 
     def add(self, output, target, iou_type='boxes'):
         if iou_type == 'masks' and 'masks' in output and 'masks' in target:
@@ -308,7 +401,8 @@ class DeviceAPMeter:
         one matching call.  Instances are disjoint on both sides by construction.  One device-to-host read per batch (the overlap status).
         max_pairs sizes the overlap's pair table (ops.label_overlap; default: from the row counts), for batches whose instances fragment into
         more overlapping pairs than that holds.  A 16-bit map is refused once the batch has more than 65535 truths (0xFFFF would be a row).
-        Results are stored as add_batch stores them."""
+        Results are stored as add_batch stores them; the batch's segmentation counts (segmentation_counts) are added to the meter's on the
+        device, for segmentation_summary."""
         from ... import ops
         if not len(outputs):
             return
@@ -336,6 +430,15 @@ class DeviceAPMeter:
         hit, live, _, _ = ops.mask_ap_match(pairs, pa, ta, scores, labels, tlabels, self.iouv, ignore=self.ignore)
         self._batches.append((scores, labels, hit, live, pred_off, tlabels, true_off))
         self._host_cache = None
+        counts = segmentation_counts(pairs, pa, ta)                  # rows of different images share no pair: the batch is one pooled image
+        self._seg = counts if self._seg is None else {k: self._seg[k] + v for k, v in counts.items()}
+
+    def segmentation_summary(self):
+        """PQ / SQ / DQ / AJI / Dice of everything add_batch_masks received, as segmentations (segmentation_counts: class-agnostic, every
+        row that owns a pixel is an instance): the ratios of the pooled counts, not means of per-image ratios, and the counts themselves
+        (SEG_COUNT_KEYS).  One device-to-host copy.  Without any add_batch_masks call: all zero."""
+        c = segmentation_counts_to_host(self._seg) if self._seg is not None else {k: 0.0 if k == 'iou_sum' else 0 for k in SEG_COUNT_KEYS}
+        return {**segmentation_ratios(c), **c}
 
     def _host(self):
         """the compact arrays on the host (one copy per array), rows outside every image's span dropped, and the image of every prediction"""

@@ -17,6 +17,7 @@ Checkpoints: state_dicts by default ('model', 'ema'); `--weights` also reads the
 
     python train.py --variant s --nc 8 --batch-size 64 --imgsz 640 --epochs 2 --steps-per-epoch 20
     python train.py --cfg my_model.yaml --hyp my_hyp.yaml --freeze backbone --masks --save-period 5
+    python train.py --variant s --nc 8 --tile-bank train.npz --val-bank held_out.npz [--masks]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py --batch-size 512 ...
 """
 import argparse
@@ -175,7 +176,14 @@ def train(hyp, opt, device):
                              masks=with_masks)
     else:
         loader = SyntheticTiles(batch_size, imgsz, nc, opt.steps_per_epoch, rank=max(RANK, 0), seed=opt.seed, device=device, **mk)
-    val_loader = SyntheticTiles(batch_size, imgsz, nc, opt.val_batches, rank=0, seed=opt.seed + 99, device=device, task=task0)
+    if opt.val_bank and RANK in (-1, 0):                               # a held-out 8-bit bank at its own tile size (metayolo/datasets.py BankTiles)
+        val_loader = val.load_val_bank(opt.val_bank, nc, batch_size, device, task0, with_masks)
+        try:
+            val_loader.check_stride(val.max_stride(model))
+        except ValueError as e:
+            raise SystemExit(f'--val-bank: {e}')
+    else:
+        val_loader = SyntheticTiles(batch_size, imgsz, nc, opt.val_batches, rank=0, seed=opt.seed + 99, device=device, task=task0)
     nb = len(loader)
     nw = max(round(hyp['warmup_epochs'] * nb), 100)
     last_opt_step = -1
@@ -225,7 +233,7 @@ def train(hyp, opt, device):
             final = epoch + 1 == opt.epochs
             fitness = 0.0
             if not opt.noval or final:
-                fitness, _, speeds = val.run(ema.ema, val_loader, half=True)
+                fitness, _, speeds = val.run(ema.ema, val_loader, half=True, device_metrics=bool(opt.val_bank))
                 ema.ema.float()
             best_fitness = max(best_fitness, fitness)
             if not opt.nosave or final:
@@ -287,6 +295,9 @@ def argument_parser():
     p.add_argument('--tile-bank', default='', help='.npz tile bank (tiles uint8 (n,H,W,3), boxes float32 xyxy px, labels int64 1..nc, offsets int64 '
                                                    '(n+1); for --masks also instances uint16 (n,H,W)): train on it with device-side augmentation '
                                                    'instead of synthetic tiles')
+    p.add_argument('--val-bank', default='', help='.npz tile bank to validate on (rank 0, at the bank\'s own tile size, 8-bit path, device metrics; with '
+                                                  '--masks and an instance map also mask mAP, PQ / SQ / DQ / AJI / Dice) instead of synthetic tiles; '
+                                                  'best.pt and --patience keep using the box fitness')
     p.add_argument('--k-mosaic', type=int, default=2, help='mosaic side k: every image is a random crop of k x k augmented cells')
     p.add_argument('--patch-size', type=int, default=0, help='side of a mosaic cell in pixels (0: img-size)')
     p.add_argument('--degrees', type=float, default=0.0)

@@ -3,6 +3,7 @@
 (reference: val_nuclei.py:108-221), on the MI355X path: eval forward (HIP plan) -> decode + NMS kernels -> APMeter.
 
     python val_nuclei.py --variant s --nc 8 --imgsz 640 --batch-size 32 --batches 4 [--device-metrics]
+    python val_nuclei.py --variant s --nc 8 --weights best.pt --tile-bank held_out.npz [--masks]
 """
 import argparse
 import os
@@ -82,12 +83,48 @@ def _add_batch_on_device(meter, outputs, targets, task_id, w, h):
     meter.add_batch(outs, [{'boxes': b, 'labels': t['labels']} for b, t in zip(boxes, tgts)])
 
 
+def max_stride(model):
+    """the largest stride of any header's levels: what a tile side must be a multiple of"""
+    return int(max(h._stride_cached(i) for h in model.headers.values() for i in range(h.nl)))
+
+
+def _add_batch_masks_on_device(meter, outputs, targets, task_id, size):
+    """one batch of one task into its mask meter (DeviceAPMeter.add_batch_masks); an image without detections comes without 'masks'"""
+    outs = []
+    for output in outputs:
+        o = output[task_id]
+        outs.append(o if 'masks' in o else dict(o, masks=o['boxes'].new_zeros((len(o['boxes']), 1, 28, 28))))
+    tgts = [{'labels': a['labels'], 'instances': a['instances']} for a in (target['anns'][task_id][0] for target in targets)]
+    meter.add_batch_masks(outs, tgts, size)
+
+
+def summarize_masks(mask_meter, task_id):
+    """the mask table of one task: summarize_stats on mask IoU, then PQ / SQ / DQ / AJI / Dice of the pooled segmentations"""
+    stats = summarize_stats(mask_meter, task_id=f'{task_id}/mask')
+    seg = mask_meter.segmentation_summary()
+    LOGGER.info(('%10s' * 2 + '%12s' * 5) % (f'{task_id}/mask', 'Instances', 'PQ', 'SQ', 'DQ', 'AJI', 'Dice'))
+    LOGGER.info(('%10s' + '%10i' + '%12.3g' * 5) % ('all', seg['tp'] + seg['fn'], seg['pq'], seg['sq'], seg['dq'], seg['aji'], seg['dice']))
+    return {**stats, **seg}
+
+
 @torch.no_grad()
 def run(model, dataloader, meta_info=None, callbacks=None, batch_size=32, half=True, verbose=False, save_txt=False,
         save_dir='', plots=False, epoch=0, device_metrics=False):
     """device_metrics=True: the tasks whose header is single-label are scored by DeviceAPMeter (the matching on the device, one call per
     batch, no device-to-host read in the loop); the others, and everything by default, by the host APMeter.  Return values and the log
-    table are the same in both modes."""
+    table are the same in both modes.
+
+    A metayolo.datasets.BankTiles loader runs through the 8-bit path: every batch is gathered from the bank straight into the plan's input
+    buffer (Model.forward_tiles), no float batch is made, and the detections are bit-identical to those of the loader's float tuples.  Its
+    tile sides must be multiples of the model's largest stride (ValueError).
+
+    Masks are scored for a task when the model's only header has a mask branch, the task is scored on the device and every target of the
+    batch carries 'instances' (BankTiles on a bank with an instance map): the forward then runs with compute_masks=True and a second
+    DeviceAPMeter receives add_batch_masks.  val_stats[task]['masks'] then holds summarize_stats' six keys on mask IoU plus pq, sq, dq, aji,
+    dice and the counts behind them (DeviceAPMeter.segmentation_summary), with one more log table; every other key, and fitness, stay the box
+    metrics.  The segmentation that PQ / AJI / Dice judge is everything the model outputs at its conf_thres, pasted in score order: at the
+    AP-style threshold of 0.001 the low-score rows count as instances and own pixels too."""
+    from metayolo.datasets import BankTiles
     callbacks = callbacks or _NoCallbacks()
     device = next(model.parameters()).device
     model.half() if half else model.float()
@@ -95,28 +132,46 @@ def run(model, dataloader, meta_info=None, callbacks=None, batch_size=32, half=T
     names = lambda task_id: (meta_info or {}).get(task_id, {}).get('labels_text', {})   # noqa: E731
     on_device = {task_id: bool(device_metrics) and not getattr(h, 'multi_label', False) for task_id, h in model.headers.items()}
     meters = {task_id: (DeviceAPMeter if on_device[task_id] else APMeter)(names(task_id)) for task_id in model.headers}
+    # (the mask branch of a plan belongs to its only header, as in Model._forward_headers)
+    mask_tasks = [task_id for task_id, h in model.headers.items() if on_device[task_id] and getattr(h, 'nc_masks', 0) > 0 and len(model.headers) == 1]
+    mask_meters = {}
+    from_bank = isinstance(dataloader, BankTiles)
+    if from_bank:
+        dataloader.check_stride(max_stride(model))
     callbacks.run('on_val_start')
     dt, n_image = [0.0, 0.0, 0.0], 0
-    for batch_i, (imgs, targets) in enumerate(dataloader):
+    for batch_i, (imgs, targets) in enumerate(dataloader.u8_batches() if from_bank else dataloader):
         callbacks.run('on_val_batch_start')
         t1 = time_sync()
-        imgs = torch.stack(list(imgs)).to(device, non_blocking=True).float()
+        if from_bank:
+            (first, count), (h, w) = imgs, dataloader.tile
+        else:
+            imgs = torch.stack(list(imgs)).to(device, non_blocking=True).float()
+            h, w = imgs.shape[-2:]
         targets = to_device(targets, device)
+        with_masks = [task_id for task_id in mask_tasks if all('instances' in t['anns'][task_id][0] for t in targets)]
         t2 = time_sync()
         dt[0] += t2 - t1
-        _, outputs = model(imgs, compute_masks=False)
+        if from_bank:
+            _, outputs = model.forward_tiles(dataloader.slide, dataloader.origins, first, count, (h, w), compute_masks=bool(with_masks),
+                                             device_outputs=False)
+        else:
+            _, outputs = model(imgs, compute_masks=bool(with_masks))
         t3 = time_sync()
         dt[1] += t3 - t2
         for task_id in model.headers:
             if on_device[task_id]:
-                _add_batch_on_device(meters[task_id], outputs, targets, task_id, imgs.shape[-1], imgs.shape[-2])
+                _add_batch_on_device(meters[task_id], outputs, targets, task_id, w, h)
+        for task_id in with_masks:
+            if task_id not in mask_meters:
+                mask_meters[task_id] = DeviceAPMeter(names(task_id))
+            _add_batch_masks_on_device(mask_meters[task_id], outputs, targets, task_id, (h, w))
         for output, target in zip(outputs, targets):
             n_image += 1
             for task_id in model.headers:
                 if on_device[task_id]:
                     continue
                 o, t = output[task_id], dict(target['anns'][task_id][0])
-                h, w = imgs.shape[-2:]
                 if t['boxes'].numel() and float(t['boxes'].max()) <= 1.0:      # normalised training boxes -> pixels
                     t['boxes'] = t['boxes'] * t['boxes'].new_tensor([w, h, w, h])
                 if o['labels'].dim() == 2:
@@ -129,8 +184,20 @@ def run(model, dataloader, meta_info=None, callbacks=None, batch_size=32, half=T
     speeds = tuple(x / max(n_image, 1) * 1e3 for x in dt)
     val_stats = {task_id: summarize_stats(m, task_id=task_id) for task_id, m in meters.items()}
     fitness = sum(s['fitness'] for s in val_stats.values())
+    for task_id, m in mask_meters.items():
+        val_stats[task_id]['masks'] = summarize_masks(m, task_id)
     model.float()
     return fitness, val_stats, speeds
+
+
+def load_val_bank(path, nc, batch_size, device, task, masks):
+    """--tile-bank / --val-bank: the bank as a BankTiles loader; a bank whose labels pass the model's nc is refused"""
+    from hd_yolo_amd.augment import TileBank
+    from metayolo.datasets import BankTiles
+    bank = TileBank.load(path)
+    if bank.nc > nc:
+        raise SystemExit(f'tile bank {path} holds labels up to {bank.nc}, the model has nc={nc}')
+    return BankTiles(bank, batch_size, device=device, task=task, masks=masks)
 
 
 def main():
@@ -144,12 +211,21 @@ def main():
     ap.add_argument('--device', default='')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device-metrics', action='store_true', help='score single-label tasks on the device (DeviceAPMeter) instead of the host APMeter')
+    ap.add_argument('--tile-bank', default='', help='.npz tile bank (hd_yolo_amd.augment.TileBank) to validate on, at its own tile size, through the 8-bit '
+                                                   'path and the device metrics, instead of synthetic tiles')
+    ap.add_argument('--masks', action='store_true', help='--tile-bank: a model with the mask branch; a bank with an instance map is also scored on mask '
+                                                         'IoU (mask mAP, PQ / SQ / DQ / AJI / Dice)')
     opt = ap.parse_args()
+    if opt.masks and not opt.tile_bank:
+        ap.error('--masks needs --tile-bank')
     from hd_yolo_amd import synth
     from metayolo.datasets import SyntheticTiles
     from metayolo.models.yolo import Model
     device = select_device(opt.device)
-    model = Model(synth.make_cfg(opt.variant, opt.nc), synth.make_hyp())
+    cfg = synth.make_cfg(opt.variant, opt.nc)
+    if opt.masks:
+        cfg['headers'][0][3][3] = 1                           # stock graph + the mask branch (one shared mask class), as train.py --masks
+    model = Model(cfg, synth.make_hyp())
     if opt.weights:
         from metayolo.engines.general import checkpoint_state, intersect_dicts
         ck = torch.load(opt.weights, map_location='cpu', weights_only=False)
@@ -158,8 +234,18 @@ def main():
     else:
         model.load_state_dict(synth.synth_state_dict(synth.shapes_of(model), seed=0), strict=False)
     model = model.to(device)
-    loader = SyntheticTiles(opt.batch_size, opt.imgsz, opt.nc, opt.batches, seed=12345)
-    fitness, stats, speeds = run(model, loader, half=not opt.no_half, device_metrics=opt.device_metrics)
+    if opt.tile_bank:
+        task = next(iter(model.headers))
+        loader = load_val_bank(opt.tile_bank, opt.nc, opt.batch_size, device, task, opt.masks)
+        try:
+            loader.check_stride(max_stride(model))
+        except ValueError as e:
+            raise SystemExit(str(e))
+        LOGGER.info(f'--tile-bank: --imgsz is ignored, the inference size is the tile size {loader.tile[0]} x {loader.tile[1]} of {opt.tile_bank}')
+        fitness, stats, speeds = run(model, loader, half=not opt.no_half, device_metrics=True)
+    else:
+        loader = SyntheticTiles(opt.batch_size, opt.imgsz, opt.nc, opt.batches, seed=12345)
+        fitness, stats, speeds = run(model, loader, half=not opt.no_half, device_metrics=opt.device_metrics)
     print(f'fitness {fitness:.4f}; ms/img pre {speeds[0]:.3f} infer+nms {speeds[1]:.3f} metrics {speeds[2]:.3f}')
 
 
