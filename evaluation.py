@@ -152,7 +152,7 @@ def _check_slide(slide):
 
 @torch.no_grad()
 def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=1.0, iou_thres=None, compute_masks=False, min_tissue=0.0,
-                       background=220, label_map=False):
+                       background=220, label_map=False, measure=False):
     """Whole-slide detection as the reference's ROI protocol composes it: tiles of one amplification are run in batches, each tile's
     detections carry their 'roi' offset, `Detect.merge_outputs` shifts and concatenates them (yolo_head.py:450-462), overlapping
     windows are de-duplicated by one class-agnostic NMS on the MI355X kernel (as Ensemble.merge does, yolo.py:189-199), and
@@ -168,8 +168,15 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     background are skipped, a pixel being background when min(R, G, B) >= background.  0.0 keeps every tile and launches nothing.
     label_map=True (with compute_masks, on a model with a mask branch; not in the reference, which pastes per image: val_nuclei.py:169-176):
     every task with masks gains 'label_map', the int32 (round(H * scale), round(W * scale)) nucleus segmentation of the slide drawn from the
-    final boxes and masks (-1 background, else the row of the returned detection that owns the pixel: slide_label_map), and 'areas'."""
+    final boxes and masks (-1 background, else the row of the returned detection that owns the pixel: slide_label_map), and 'areas'.
+    measure=True (with label_map): every task with a label map gains 'nuclei', the table of slide_nucleus_table: position, size, axes,
+    orientation, outline and border contact of every detection from one more pass over the map, and its mean / standard deviation per stain
+    channel when the slide is 8-bit and scale == 1.0 (map and slide then share a grid; otherwise the table has no 'mean_rgb' / 'std_rgb')
+    (not in the reference, which measures nothing).  measure=False launches nothing new."""
     u8 = _check_slide(slide)
+    if measure and not label_map:
+        raise ValueError('inference_on_slide: measure=True needs label_map=True (the nuclei are measured on the label map)')
+    stained = slide if measure and u8 and float(scale) == 1.0 else None
     inner = model._model if isinstance(model, Deploy) else model
     if label_map:
         headers = getattr(inner, 'headers', None)
@@ -178,7 +185,8 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
         if headers is None or not any(getattr(h, 'nc_masks', 0) > 0 for h in headers.values()):
             raise ValueError('inference_on_slide: label_map=True needs a model with a mask branch')
     if u8:
-        return _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map)
+        return _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map,
+                                      measure, stained)
     if min_tissue:
         raise ValueError('inference_on_slide: min_tissue applies to 8-bit slides (the background rule is defined on 8-bit RGB values)')
     _, H, W = slide.shape
@@ -197,7 +205,7 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     if label_map:
         _zero_row_masks(inner.headers, per_task)
     merged = {task_id: inner.headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained)
 
 
 def _zero_row_masks(headers, per_task):
@@ -224,7 +232,43 @@ def slide_label_map(result, size, window=None, threshold=0.5):
     return lm, ops.label_areas(lm, len(result['boxes']))
 
 
-def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=False):
+@torch.no_grad()
+def slide_nucleus_table(result, slide=None, window=None, threshold=0.5):
+    """One task's result -> the nucleus table (hd_yolo_amd/measure.py: nucleus_table), a dict of device tensors with one row per detection:
+    area, centroid, bbox, major / minor axis, eccentricity, orientation, equivalent diameter, perimeter and border edges, touches_border,
+    compactness, labels, scores and, with the 8-bit `slide` the map was drawn on ((H, W, 3 | 4) uint8), mean_rgb / std_rgb.  The result's
+    'label_map' is measured; a result without one ('boxes' and 'masks' only) gets it from slide_label_map at `threshold`.  window =
+    (x0, y0, w, h): the part of the slide the map holds (default: all of it, from (0, 0)); positions in the table are slide coordinates.
+    One measuring pass (ops.label_measure) whatever the number of detections, moments taken about each box's truncated corner; nothing is
+    read back."""
+    from hd_yolo_amd import measure as hmeasure
+    from hd_yolo_amd import ops
+    lm = result.get('label_map')
+    if lm is None:
+        if window is None and slide is None:
+            raise ValueError("slide_nucleus_table: a result without 'label_map' needs the slide or a window to size the map")
+        size = (int(slide.shape[0]), int(slide.shape[1])) if slide is not None else (int(window[1] + window[3]), int(window[0] + window[2]))
+        lm, _ = slide_label_map(result, size, window=window, threshold=threshold)
+    h, w = lm.shape
+    x0, y0 = (0, 0) if window is None else (int(window[0]), int(window[1]))
+    if window is not None and (int(window[2]), int(window[3])) != (w, h):
+        raise ValueError(f'slide_nucleus_table: window {tuple(window)} does not match the {h} x {w} label map')
+    boxes = result['boxes'].detach().to(lm.device).reshape(-1, 4).float()
+    corner = torch.nan_to_num(boxes[:, :2], nan=0.0) - boxes.new_tensor([x0, y0])
+    hi = boxes.new_tensor([w - 1, h - 1])
+    origin = torch.minimum(corner.clamp(min=0), hi).to(torch.int32)              # truncated and clamped into the window
+    sums, extent = ops.label_measure(lm, len(boxes), image=slide, window=(x0, y0), origin=origin)
+    return hmeasure.nucleus_table(sums, extent, origin=origin, offset=(x0, y0), labels=result.get('labels'), scores=result.get('scores'),
+                                  stain=slide is not None)
+
+
+def save_nucleus_table(path, table):
+    """a nucleus table as .npz or .csv, by the extension of `path` (hd_yolo_amd/measure.py: one device-to-host copy)"""
+    from hd_yolo_amd import measure as hmeasure
+    hmeasure.save_nucleus_table(path, table)
+
+
+def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=False, measure=False, stained=None):
     """everything after the merge: de-duplication of overlapping windows, clamp to the slide, rescale"""
     out = {}
     for task_id, r in merged.items():
@@ -239,10 +283,13 @@ def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=Fals
         if label_map and 'masks' in out[task_id]:
             size = (int(round(H * scale)), int(round(W * scale)))
             out[task_id]['label_map'], out[task_id]['areas'] = slide_label_map(out[task_id], size)
+            if measure:
+                out[task_id]['nuclei'] = slide_nucleus_table(out[task_id], slide=stained)
     return out
 
 
-def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map=False):
+def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map=False,
+                           measure=False, stained=None):
     from hd_yolo_amd import ops
     if isinstance(model, Ensemble):
         raise NotImplementedError('inference_on_slide: 8-bit slides run on one model (Model / Deploy); an Ensemble takes the float slide')
@@ -306,7 +353,7 @@ def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_t
         if label_map:
             _zero_row_masks(headers, per_task)
         merged = {task_id: headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained)
 
 
 SCORE_CELL_SIDES = 4.0          # score_slide: side of an ordering cell, in mean box sides (a block of 256 rows then spans a few cells)
@@ -422,6 +469,8 @@ def main():
     ap.add_argument('--score', action='store_true', help='--slide: also score a synthetic set of slide detections against a synthetic truth (score_slide)')
     ap.add_argument('--masks', action='store_true', help='--slide: also run the slide through a synthetic mask model (the tiny variant, one mask class, fp32) with compute_masks')
     ap.add_argument('--label-map', action='store_true', help='--slide --masks: paste the masks into one int32 label map of the slide (slide_label_map) and count the owned pixels')
+    ap.add_argument('--measure', action='store_true', help='--slide --masks --label-map: measure every nucleus on the label map (slide_nucleus_table; stain columns with --u8)')
+    ap.add_argument('--table', default='', help='--measure: write the nucleus table to this .npz or .csv file (save_nucleus_table)')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
     opt = ap.parse_args()
@@ -452,13 +501,15 @@ def main():
         print(f'slide {opt.slide}x{opt.slide}: ' + ', '.join(f'{k}: {len(v["boxes"])} detections' for k, v in out.items()) + f' in {(time.time() - t0) * 1e3:.1f} ms')
         if opt.label_map and not opt.masks:
             ap.error('--label-map needs --masks')
+        if opt.measure and not opt.label_map:
+            ap.error('--measure needs --label-map')
         if opt.masks:
             cfg = synth.make_cfg('n', 2)
             cfg['headers'][0][3][3] = 1                                   # one mask class: the mask model of tests/test_gpu_mask.py
             mm = Model(cfg, synth.make_hyp(conf_thres=0.05))
             mm.load_state_dict(synth.mask_state_dict(mm), strict=False)
             mdep = Deploy(mm.to(device).eval())
-            kw = dict(tile=min(opt.imgsz, opt.slide), batch_size=opt.batch_size, compute_masks=True, label_map=opt.label_map)
+            kw = dict(tile=min(opt.imgsz, opt.slide), batch_size=opt.batch_size, compute_masks=True, label_map=opt.label_map, measure=opt.measure)
             inference_on_slide(mdep, slide, **kw)                         # warm-up: plans
             torch.cuda.synchronize()
             t0 = time.time()
@@ -470,6 +521,21 @@ def main():
                 if 'areas' in v:
                     line += f', {int(v["areas"].sum())} owned pixels of {v["label_map"].numel()} ({int((v["areas"] > 0).sum())} detections own some)'
                 print(line + f' in {dt:.1f} ms')
+                if 'nuclei' in v:
+                    torch.cuda.synchronize()
+                    t0 = time.time()
+                    nt = slide_nucleus_table(v, slide=slide if opt.u8 else None)
+                    torch.cuda.synchronize()
+                    dtm = (time.time() - t0) * 1e3
+                    own = nt['area'] > 0
+                    med = lambda c: float(c[own].median()) if bool(own.any()) else float('nan')
+                    print(f'nuclei {opt.slide}x{opt.slide}, task {k}: {int(own.sum())} measured, {int((nt["touches_border"] & own).sum())} on the border, median '
+                          f'area {med(nt["area"].double()):.1f} px, median major axis {med(nt["major_axis"]):.2f} px'
+                          + (f', mean RGB {[round(float(c), 1) for c in nt["mean_rgb"][own].mean(0)]}' if 'mean_rgb' in nt and bool(own.any()) else '')
+                          + f' in {dtm:.2f} ms')
+                    if opt.table:
+                        save_nucleus_table(opt.table, v['nuclei'])
+                        print(f'nucleus table written to {opt.table}')
         if opt.score:
             # synthetic weights detect nothing meaningful, so the scored detections are synthetic too: annotations at nucleus density and
             # detections made from them (synth.synth_slide_truth)

@@ -1192,6 +1192,45 @@ def label_areas(label_map, R):
     return areas
 
 
+# ------------------------------------------------------------------------------------------ label measurement (csrc/measure.hip)
+def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
+    """(sums, extent) of the R labels of an int32 (h, w) label map (hdy_label_measure, include/hdyolo_measure.h): sums int64 (R, 14) = n, sum dx,
+    sum dy, sum dx^2, sum dy^2, sum dx dy, boundary edges, edges on the window border, sum R, G, B, sum R^2, G^2, B^2 with dx = j - ox, dy = i - oy;
+    extent int32 (R, 4) = min j, min i, max j, max i ({w, h, -1, -1} for a label that owns nothing).  One pass, integer-exact, no synchronisation.
+    image: the 8-bit slide as slide_u8 takes it ((H, W, 3 | 4) uint8, any row stride), of which the map covers the window at (x0, y0) = window;
+    None leaves the stain columns zero.  origin: int32 (R, 2) = (ox, oy) per label in map coordinates (None = zeros); hd_yolo_amd/measure.py
+    (nucleus_table) turns the sums into the measurements."""
+    from . import _ext
+    require_gpu(label_map)
+    if label_map.dtype != torch.int32 or label_map.dim() != 2 or label_map.numel() == 0:
+        raise _lib.HdyError(f'label_measure: the map must be a non-empty int32 (h, w) tensor, got {label_map.dtype} {tuple(label_map.shape)}')
+    lm = label_map.contiguous()
+    h, w = lm.shape
+    R = int(R)
+    if R < 0:
+        raise _lib.HdyError(f'label_measure: negative row count R={R}')
+    x0, y0 = (int(v) for v in window)
+    ip, nbytes, pitch, pb = None, 0, 0, 0
+    if image is not None:
+        ip, pitch, pb, H, W = slide_u8(image)
+        if image.device != lm.device:
+            raise _lib.HdyError(f'label_measure: the map is on {lm.device}, the image on {image.device}')
+        if x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+            raise _lib.HdyError(f'label_measure: the {h} x {w} map at window origin {(x0, y0)} leaves the {H} x {W} image')
+        nbytes = (H - 1) * pitch + W * pb                     # from the first byte of the view to the last byte of its last pixel
+    if origin is not None:
+        require_gpu(origin)
+        if origin.dtype != torch.int32 or tuple(origin.shape) != (R, 2) or origin.device != lm.device:
+            raise _lib.HdyError(f'label_measure: origin must be an int32 ({R}, 2) tensor on {lm.device}, got {origin.dtype} {tuple(origin.shape)}')
+        origin = origin.contiguous()
+    sums = torch.empty((R, _ext.MEASURE_COLS), dtype=torch.int64, device=lm.device)
+    extent = torch.empty((R, 4), dtype=torch.int32, device=lm.device)
+    if R:
+        _ext.call('hdy_label_measure', lm.data_ptr(), lm.numel(), h, w, ip, nbytes, pitch, pb, x0, y0, ptr(origin), sums.data_ptr(), sums.numel(),
+                  extent.data_ptr(), extent.numel(), R, stream_ptr())
+    return sums, extent
+
+
 # ------------------------------------------------------------------------------------------ mask scoring (csrc/mask_score.hip)
 OVERLAP_MIN_SLOTS, OVERLAP_MAX_SLOTS = 64, _lib.CONSTANTS['HDY_OVERLAP_MAX_SLOTS']
 
