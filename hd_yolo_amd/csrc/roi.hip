@@ -6,6 +6,7 @@
 // row/column interpolates with itself.  Output is NHWC [R][P][P][C] so the head's convolutions consume it directly.
 // Forward: an HBM-bound gather, one lane per (roi, bin, 8- or 4-channel vector).  The backward accumulates into an fp32 image
 // (bf16 has no atomic add and rois overlap), privatised per roi in LDS; hdy_cast_store then writes the plan's gradient buffer.
+// tests/test_gpu_roi_direct.py compares every entry point of this file's RoIAlign family with the float64 restatement tests/roi_ref.py.
 // Inference over a batch's detections: roi_align_levels_kernel does the same gather for every kept row of the padded NMS result from the level
 // that produced it, in compacted order (reference: multiscale_roi_align, yolo_head.py:279-299), and mask_rows_kernel picks each row's mask
 // channel behind the head (:346-351).
@@ -221,7 +222,9 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(const float* __restrict_
 // gradient image with one global atomic per pixel and channel (rois overlap).  The matched truths of a nuclei tile are a few feature
 // pixels wide, so ~200 bins x 4 samples fall onto a handful of pixels: the first version scattered them with global atomics (8 ms per
 // call), the second with LDS atomics into the footprint (1.36 ms per call at B=16, 1280x1280: up to 8 bins in flight hit one address).
-// Rois whose footprint exceeds the LDS tile scatter directly (they are large, hence uncontended).
+// Rois whose footprint exceeds the LDS tile scatter directly (they are large, hence uncontended).  The footprint is the range [min i0, max i1]
+// of the roi's valid per-axis samples, found by the workgroup from the very values that fill Wy / Wx; a roi without a valid sample on an
+// axis contributes nothing and returns.
 constexpr int FT = 24;                   // footprint tile side (feature pixels)
 constexpr int CB = 32;                   // channels per workgroup
 constexpr int PM = 16;                   // largest output side handled by the footprint path (P = 14 for the mask head)
@@ -235,6 +238,9 @@ __device__ __forceinline__ void axis_sample(float v, int size, bool* ok, int* i0
     *lo = 1.f - *hi;                     // weight of i0
 }
 
+// coordinate of sample i of bin pb along one axis: the expression of roi_bin, operation for operation
+__device__ __forceinline__ float axis_coord(float o, float bs, int pb, int i, int S) { return o + (float)pb * bs + ((float)i + 0.5f) * bs / (float)S; }
+
 template <typename T>
 __global__ __launch_bounds__(256) void roi_align_bwd_tiled_kernel(float* __restrict__ dfeat, int B, int H, int W, int C, const float* __restrict__ rois,
                                                                   float scale, int P, int S, int aligned, const T* __restrict__ dout) {
@@ -247,11 +253,24 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled_kernel(float* __restr
     const int cl = threadIdx.x & (CB - 1), bl = threadIdx.x / CB;      // channel lane, 8 row lanes
     const RoiGeom g = roi_geom(rois + (size_t)r * 5, scale, P, aligned);
     if (g.b < 0 || g.b >= B) return;
-    // footprint of all samples (after the clamp of sample_at): rows [fy0, fy1], columns [fx0, fx1]
-    const float ylo = g.y0 + 0.5f * g.bin_h / (float)S, yhi = g.y0 + ((float)P - 0.5f / (float)S) * g.bin_h;
-    const float xlo = g.x0 + 0.5f * g.bin_w / (float)S, xhi = g.x0 + ((float)P - 0.5f / (float)S) * g.bin_w;
-    const int fy0 = min(max((int)floorf(fmaxf(ylo, 0.f)), 0), H - 1), fy1 = min(max((int)floorf(fmaxf(yhi, 0.f)) + 1, 0), H - 1);
-    const int fx0 = min(max((int)floorf(fmaxf(xlo, 0.f)), 0), W - 1), fx1 = min(max((int)floorf(fmaxf(xhi, 0.f)) + 1, 0), W - 1);
+    // footprint of the valid samples, rows [fy0, fy1] and columns [fx0, fx1]: the smallest i0 and the largest i1 of the same 2 P S per-axis
+    // samples (axis_coord, axis_sample) that fill the weight tables below, so a table write cannot leave [f0, f0 + n).  (A closed form of
+    // the top sample, y0 + (P - 0.5 / S) bin, rounds differently from the sample's own expression: once in ~10^6 rois it ends one pixel short.)
+    __shared__ int fpt[4];                   // fy0, fy1, fx0, fx1
+    if (threadIdx.x < 4) fpt[threadIdx.x] = (threadIdx.x & 1) ? -1 : 0x7fffffff;
+    __syncthreads();
+    for (int k = threadIdx.x; k < 2 * P * S; k += 256) {
+        const bool isx = k >= P * S;
+        const int j = isx ? k - P * S : k, pb = j / S;
+        bool ok; int i0, i1; float lo, hi;
+        axis_sample(axis_coord(isx ? g.x0 : g.y0, isx ? g.bin_w : g.bin_h, pb, j - pb * S, S), isx ? W : H, &ok, &i0, &i1, &lo, &hi);
+        if (!ok) continue;
+        atomicMin(&fpt[isx ? 2 : 0], i0);
+        atomicMax(&fpt[isx ? 3 : 1], i1);
+    }
+    __syncthreads();
+    const int fy0 = fpt[0], fy1 = fpt[1], fx0 = fpt[2], fx1 = fpt[3];
+    if (fy1 < fy0 || fx1 < fx0) return;      // an axis without a valid sample: the roi contributes nothing
     const int fh = fy1 - fy0 + 1, fw = fx1 - fx0 + 1;
     const bool tiled = fh <= FT && fw <= FT && P <= PM;
     const float inv = 1.0f / (float)(S * S);
@@ -285,7 +304,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled_kernel(float* __restr
         const float o = isx ? g.x0 : g.y0, bs = isx ? g.bin_w : g.bin_h;
         for (int j = 0; j < n; ++j) row[j] = 0.f;
         for (int i = 0; i < S; ++i) {
-            const float v = o + (float)pb * bs + ((float)i + 0.5f) * bs / (float)S;
+            const float v = axis_coord(o, bs, pb, i, S);
             bool ok; int i0, i1; float lo, hi;
             axis_sample(v, size, &ok, &i0, &i1, &lo, &hi);
             if (!ok) continue;
@@ -313,7 +332,7 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tiled_kernel(float* __restr
     }
 }
 
-// du = dz * (y > 0)
+// du = y <= 0 ? 0 : dz, a select: a NaN y lets dz through (torch's threshold_backward), a non-finite dz behind y <= 0 gives 0
 template <typename T>
 __global__ __launch_bounds__(256) void relu_bwd_kernel(const T* __restrict__ dz, const T* __restrict__ y, T* __restrict__ du, long long nvec) {
     constexpr int VE = RT<T>::VE;
@@ -322,7 +341,7 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const T* __restrict__ dz,
         ld_vec<T>(dz + i * VE, g);
         ld_vec<T>(y + i * VE, v);
 #pragma unroll
-        for (int k = 0; k < VE; ++k) g[k] = v[k] > 0.f ? g[k] : 0.f;
+        for (int k = 0; k < VE; ++k) g[k] = v[k] <= 0.f ? 0.f : g[k];
         st_vec<T>(du + i * VE, g);
     }
 }
@@ -439,6 +458,7 @@ int hdy_roi_align_bwd(const void* dout, float* dfeat_f32, int B, int H, int W, i
     else
         hipLaunchKernelGGL(roi_align_bwd_tiled_kernel<float>, grid, dim3(256), smem, (hipStream_t)stream, dfeat_f32, B, H, W, C, rois, spatial_scale, P,
                            sampling_ratio, aligned, (const float*)dout);
+    hdy_note_dispatch("roi_align_bwd");
     HDY_LAUNCH_CHECK("roi_align_bwd");
     return HDY_OK;
 }
