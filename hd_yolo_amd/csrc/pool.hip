@@ -132,7 +132,8 @@ __global__ __launch_bounds__(NT) void sppf_pool_fwd_kernel(const T* __restrict__
         for (PlaneWalk q(W); q.pix < HW; q.next(W)) {              // rows: a -> b
             const int o = ((q.h + PB) * WP + q.w + PB) * CG + cl;
             f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            unsigned bi[4] = {0, 0, 0, 0};
+            const unsigned t0 = q.w < PB ? PB - q.w : 0;           // first in-bounds tap: where a window of -inf alone keeps its position, as ATen's does
+            unsigned bi[4] = {t0, t0, t0, t0};
 #pragma unroll
             for (int dx = 0; dx < 5; ++dx) {
                 const f32x4 v = ldp(a + o + (dx - 2) * CG);
@@ -147,7 +148,8 @@ __global__ __launch_bounds__(NT) void sppf_pool_fwd_kernel(const T* __restrict__
         for (PlaneWalk q(W); q.pix < HW; q.next(W)) {              // columns: b -> a (the next pool's source)
             const int o = ((q.h + PB) * WP + q.w + PB) * CG + cl;
             f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            unsigned bj[4] = {0, 0, 0, 0};
+            const unsigned t0 = q.h < PB ? PB - q.h : 0;
+            unsigned bj[4] = {t0, t0, t0, t0};
 #pragma unroll
             for (int dy = 0; dy < 5; ++dy) {
                 const f32x4 v = ldp(b + o + (dy - 2) * WP * CG);
@@ -170,8 +172,9 @@ __global__ __launch_bounds__(NT) void sppf_pool_fwd_kernel(const T* __restrict__
 // the zeros as equal), a maximum of values is a maximum of keys, and
 //   * with positions: key << 16 | (7 - tap) as ONE unsigned maximum per channel and tap — the largest value wins, among equals the first tap;
 //   * without (inference): v_pk_max_u16 on the packed pairs, one instruction per two channels and tap;
-// Same outputs and positions as the kernel above (the FIRST of several NaNs in a window where that one keeps the last — a NaN window is NaN either
-// way).  Requesting a thread's plane loads before the border fill was tried on top (forward: +1 us; backward, with all four gradients and three
+// Same outputs and positions as the kernel above, with two documented differences pinned by tests/test_gpu_pool_direct.py: the FIRST of several NaNs
+// in a window keeps the position where that one keeps the last (a NaN window is NaN either way), and a window of -0 alone gives +0.  A window of -inf
+// alone keeps the first in-bounds tap in both (here: the border key 0 lies below the key of -inf; there: each stage starts at that tap).  Requesting a thread's plane loads before the border fill was tried on top (forward: +1 us; backward, with all four gradients and three
 // position tables: 81 -> 106 us): sixteen waves per workgroup already overlap those loads.
 __device__ __forceinline__ unsigned sppf_key2(unsigned d) {           // two packed bf16 -> two packed keys
     unsigned r = 0;
@@ -532,21 +535,23 @@ int hdy_sppf_pool_fwd(const void* x, void* y1, void* y2, void* y3, int ld, unsig
         const bool keys = !hdy_opt(HDY_OPT_SPPF_NO_KEYS) && ld % 4 == 0 && ((uintptr_t)x & 7) == 0 && ((uintptr_t)y1 & 7) == 0 && ((uintptr_t)y2 & 7) == 0 &&
                           ((uintptr_t)y3 & 7) == 0;
         if (keys && C % 32 == 0 && pix * 32 * (2 * sizeof(bf16_t) + ix) <= 150 * 1024)
-            return sppf_fwd_keys_launch<32, 1024>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, pix * 32 * (2 * sizeof(bf16_t) + ix), st);
+            return hdy_note_dispatch(ix ? "sppf_fwd_keys32_pos" : "sppf_fwd_keys32"), sppf_fwd_keys_launch<32, 1024>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, pix * 32 * (2 * sizeof(bf16_t) + ix), st);
         if (keys && C % 16 == 0 && pix * 16 * (2 * sizeof(bf16_t) + ix) <= 150 * 1024)
-            return sppf_fwd_keys_launch<16, 1024>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, pix * 16 * (2 * sizeof(bf16_t) + ix), st);
+            return hdy_note_dispatch(ix ? "sppf_fwd_keys16_pos" : "sppf_fwd_keys16"), sppf_fwd_keys_launch<16, 1024>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, pix * 16 * (2 * sizeof(bf16_t) + ix), st);
         if (C % 32 == 0 && pix * 32 * (2 * sizeof(bf16_t) + ix) <= 150 * 1024)
-            return sppf_fwd_launch<bf16_t, bf16_t, 32, 1024>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, pix * 32 * (2 * sizeof(bf16_t) + ix), st);
+            return hdy_note_dispatch(ix ? "sppf_fwd_float32_pos" : "sppf_fwd_float32"), sppf_fwd_launch<bf16_t, bf16_t, 32, 1024>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, pix * 32 * (2 * sizeof(bf16_t) + ix), st);
         // larger planes (32 x 32 of yolov5l at 1024 x 1024, 40 x 40 of the 1280 x 1280 tiles without positions): 16 channels per workgroup, still bf16
         // planes and 32-byte pieces per pixel instead of the fp32 / 8-channel / 16-byte form below (945 us per C4 forward for a 112 us byte count)
         if (C % 16 == 0 && pix * 16 * (2 * sizeof(bf16_t) + ix) <= 150 * 1024)
-            return sppf_fwd_launch<bf16_t, bf16_t, 16, 1024>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, pix * 16 * (2 * sizeof(bf16_t) + ix), st);
+            return hdy_note_dispatch(ix ? "sppf_fwd_float16_pos" : "sppf_fwd_float16"), sppf_fwd_launch<bf16_t, bf16_t, 16, 1024>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, pix * 16 * (2 * sizeof(bf16_t) + ix), st);
         const size_t smem = pix * CG * (2 * sizeof(float) + ix);
         HDY_ARG(smem <= 150 * 1024, "sppf_pool_fwd: plane %dx%d does not fit LDS", H, W);
+        hdy_note_dispatch(ix ? "sppf_fwd_c8_pos" : "sppf_fwd_c8");
         return sppf_fwd_launch<bf16_t, float, CG, 256>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, smem, st);
     }
     const size_t smem = pix * CG * (2 * sizeof(float) + ix);
     HDY_ARG(smem <= 150 * 1024, "sppf_pool_fwd: plane %dx%d does not fit LDS", H, W);
+    hdy_note_dispatch(ix ? "sppf_fwd_c8_pos" : "sppf_fwd_c8");
     return sppf_fwd_launch<float, float, CG, 256>(x, y1, y2, y3, ld, idx1, idx2, idx3, N, H, W, C, smem, st);
 }
 
@@ -559,11 +564,12 @@ int hdy_sppf_pool_bwd(const void* g0, const void* g1, const void* g2, const void
     hipStream_t st = (hipStream_t)stream;
     // fp32 planes (the sums of the three levels are rounded once, at the end): 16 channels per workgroup when two position planes fit beside them
     if (dtype == HDY_BF16 && C % 16 == 0 && pix * 16 * (2 * sizeof(float) + 2) <= 150 * 1024)
-        return sppf_bwd_launch<bf16_t, 16, 1024>(g0, g1, g2, g3, ldg, idx1, idx2, idx3, dx, lddx, N, H, W, C, 1, pix * 16 * (2 * sizeof(float) + 2), st);
+        return hdy_note_dispatch("sppf_bwd_c16"), sppf_bwd_launch<bf16_t, 16, 1024>(g0, g1, g2, g3, ldg, idx1, idx2, idx3, dx, lddx, N, H, W, C, 1, pix * 16 * (2 * sizeof(float) + 2), st);
     const size_t plane = pix * CG;
     const int two_ix = plane * (2 * sizeof(float) + 2) <= 150 * 1024;
     const size_t smem = plane * (2 * sizeof(float) + (two_ix ? 2 : 1));
     HDY_ARG(smem <= 150 * 1024, "sppf_pool_bwd: plane %dx%d does not fit LDS", H, W);
+    hdy_note_dispatch(two_ix ? "sppf_bwd_c8_two" : "sppf_bwd_c8_one");
     if (dtype == HDY_BF16) return sppf_bwd_launch<bf16_t, CG, 256>(g0, g1, g2, g3, ldg, idx1, idx2, idx3, dx, lddx, N, H, W, C, two_ix, smem, st);
     return sppf_bwd_launch<float, CG, 256>(g0, g1, g2, g3, ldg, idx1, idx2, idx3, dx, lddx, N, H, W, C, two_ix, smem, st);
 }

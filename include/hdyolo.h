@@ -48,7 +48,9 @@ const char* hdy_last_error(void);
  * plain pointers and sizes a mismatched parameter list would otherwise shift arguments silently. */
 #define HDY_ABI_VERSION 15
 int hdy_version(void);
-/* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...).
+/* Which kernel ran: every launcher names the kernel family it picked ("igemm_128x128x2", "conv3x3_c64", "deep_256x128", "wgrad3x3", ...;
+ * hdy_sppf_pool_fwd: "sppf_fwd_keys32" / "_keys16" / "_float32" / "_float16" / "_c8", with "_pos" appended when positions are stored;
+ * hdy_sppf_pool_bwd: "sppf_bwd_c16" / "sppf_bwd_c8_two" / "sppf_bwd_c8_one").
  * hdy_last_dispatch: the last pick on this thread; hdy_dispatch_log: every pick of every thread since hdy_dispatch_log_reset(), in launch
  * order, ';'-separated (process-wide under a mutex — autograd runs the backward list on its own thread — first 32 KB).  The reference has no counterpart (ATen picks its kernels silently); the tests use it to assert that the shapes meant to hit
  * a specialised kernel do. */

@@ -595,6 +595,50 @@ def softdice_case(name, N, H, W, nc):
     return c
 
 
+def sppf_case(name, N, H, W, C, dt, families):
+    """hdy_sppf_pool_fwd (three levels into channel slices of one buffer, three position tables) followed by hdy_sppf_pool_bwd from those
+    tables: the position tables are written before they are read, and hold tap numbers that are only compared, never used as an address"""
+    c = Case(name, families)
+    x = q(rnd((N, C, H, W), 1), dt)
+    g = q(rnd((N, 4 * C, H, W), 2), dt)
+    ld = 4 * C + 8
+    xd = to_dev_nhwc(x, dt, ld=ld)
+    cat = c.buf('cat', (N, H, W, ld), dt)
+    ys = [c.out(f'y{i}', cat[..., i * C:(i + 1) * C]) for i in (1, 2, 3)]
+    idx = [c.out(f'idx{i}', c.buf(f'idx{i}', (N, H, W, C // 4))) for i in (1, 2, 3)]          # four position bytes per fp32 word of the buffer
+    gd = to_dev_nhwc(g, dt)
+    gs = [gd[..., i * C:(i + 1) * C] for i in range(4)]
+    dx = c.out('dx', c.buf('dx', (N, H, W, C + 8), dt)[..., 8:])
+    c.recs = [ops.rec_sppf_pool_fwd(xd, ys[0], ys[1], ys[2], [t.view(torch.uint8) for t in idx]), ops.rec_sppf_pool_bwd(gs[0], gs[1], gs[2], gs[3], [t.view(torch.uint8) for t in idx], dx)]
+
+    def check():
+        xr = x.clone().requires_grad_(True)
+        y1 = F.max_pool2d(xr, 5, 1, 2)
+        y2 = F.max_pool2d(y1, 5, 1, 2)
+        y3 = F.max_pool2d(y2, 5, 1, 2)
+        torch.cat([xr, y1, y2, y3], 1).backward(g)
+        for got, want in zip(ys, (y1, y2, y3)):
+            assert torch.equal(from_dev_nhwc(got), want.detach()), f'{name} forward'
+        assert_close(from_dev_nhwc(dx), xr.grad, TOL[dt], f'{name} backward')
+    c.check = check
+    return c
+
+
+def upsample_case(name, N, H, W, C, dt):
+    """hdy_upsample2x_fwd and hdy_upsample2x_bwd with accumulate = 0 (the upsample kernels note no dispatch name), pitched outputs"""
+    c = Case(name)
+    x, g = q(rnd((N, C, H, W), 1), dt), q(rnd((N, C, 2 * H, 2 * W), 2), dt)
+    y = c.out('y', c.buf('y', (N, 2 * H, 2 * W, C + 8), dt)[..., 8:])
+    dx = c.out('dx', c.buf('dx', (N, H, W, C + 8), dt)[..., :C])
+    c.recs = [ops.rec_upsample_fwd(to_dev_nhwc(x, dt, ld=C + 8, off=8), y), ops.rec_upsample_bwd(to_dev_nhwc(g, dt), dx, accumulate=False)]
+
+    def check():
+        assert torch.equal(from_dev_nhwc(y), F.interpolate(x, scale_factor=2.0, mode='nearest')), f'{name} forward'
+        assert_close(from_dev_nhwc(dx), g.view(N, C, H, 2, W, 2).sum((3, 5)), TOL[dt], f'{name} backward')
+    c.check = check
+    return c
+
+
 # ------------------------------------------------------------------------------------------------------------------------------ the table
 D0 = {'HDY_DEEP_MIN_TILES': 1}
 ROWS = [
@@ -680,6 +724,14 @@ ROWS = [
     ('seg-groupnorm_bwd-bf16', {}, lambda: groupnorm_case('hdy_groupnorm_bwd bf16', 2, 12, 10, 64, 32, BF16, True)),
     ('seg-groupnorm_bwd-fp32', {}, lambda: groupnorm_case('hdy_groupnorm_bwd fp32', 2, 9, 9, 24, 4, F32, True)),
     ('seg-softdice', {}, lambda: softdice_case('hdy_softdice', 3, 173, 211, 3)),
+    # SPPF pools and the upsample (pool.hip): LDS planes with borders the kernels fill themselves, outputs written whole
+    ('sppf-keys32-bwd_c16', {}, lambda: sppf_case('SPPF bf16, 32-channel keys', 2, 20, 20, 64, BF16, ['sppf_fwd_keys32_pos', 'sppf_bwd_c16'])),
+    ('sppf-keys16-bwd_c8_two', {}, lambda: sppf_case('SPPF bf16, 16-channel keys', 1, 32, 32, 48, BF16, ['sppf_fwd_keys16_pos', 'sppf_bwd_c8_two'])),
+    ('sppf-float32', {'HDY_SPPF_NO_KEYS': 1}, lambda: sppf_case('SPPF bf16, 32-channel float compare', 2, 20, 20, 32, BF16, ['sppf_fwd_float32_pos', 'sppf_bwd_c16'])),
+    ('sppf-float16', {'HDY_SPPF_NO_KEYS': 1}, lambda: sppf_case('SPPF bf16, 16-channel float compare', 1, 27, 27, 16, BF16, ['sppf_fwd_float16_pos', 'sppf_bwd_c8_two'])),
+    ('sppf-c8-fp32', {}, lambda: sppf_case('SPPF fp32, 8 channels, one position plane', 1, 40, 40, 24, F32, ['sppf_fwd_c8_pos', 'sppf_bwd_c8_one'])),
+    ('upsample-bf16', {}, lambda: upsample_case('upsample bf16', 2, 5, 6, 24, BF16)),
+    ('upsample-fp32', {}, lambda: upsample_case('upsample fp32', 3, 7, 5, 12, F32)),
 ]
 ROW_IDS = [r[0] for r in ROWS]
 
