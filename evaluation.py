@@ -152,7 +152,7 @@ def _check_slide(slide):
 
 @torch.no_grad()
 def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=1.0, iou_thres=None, compute_masks=False, min_tissue=0.0,
-                       background=220, label_map=False, measure=False):
+                       background=220, label_map=False, measure=False, neighbors=None):
     """Whole-slide detection as the reference's ROI protocol composes it: tiles of one amplification are run in batches, each tile's
     detections carry their 'roi' offset, `Detect.merge_outputs` shifts and concatenates them (yolo_head.py:450-462), overlapping
     windows are de-duplicated by one class-agnostic NMS on the MI355X kernel (as Ensemble.merge does, yolo.py:189-199), and
@@ -172,10 +172,15 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     measure=True (with label_map): every task with a label map gains 'nuclei', the table of slide_nucleus_table: position, size, axes,
     orientation, outline and border contact of every detection from one more pass over the map, and its mean / standard deviation per stain
     channel when the slide is 8-bit and scale == 1.0 (map and slide then share a grid; otherwise the table has no 'mean_rgb' / 'std_rgb')
-    (not in the reference, which measures nothing).  measure=False launches nothing new."""
+    (not in the reference, which measures nothing).  measure=False launches nothing new.
+    neighbors=(r1, r2, ...) (with measure; up to four increasing radii in pixels of the returned coordinates): 'nuclei' gains 'neighbors',
+    'nearest_dist' and 'nearest_row', the columns of slide_neighborhood (hd_yolo_amd/spatial.py) for the header's classes.  None launches
+    nothing new."""
     u8 = _check_slide(slide)
     if measure and not label_map:
         raise ValueError('inference_on_slide: measure=True needs label_map=True (the nuclei are measured on the label map)')
+    if neighbors is not None and not measure:
+        raise ValueError('inference_on_slide: neighbors needs measure=True (the neighbourhoods are those of the nucleus table)')
     stained = slide if measure and u8 and float(scale) == 1.0 else None
     inner = model._model if isinstance(model, Deploy) else model
     if label_map:
@@ -186,7 +191,7 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
             raise ValueError('inference_on_slide: label_map=True needs a model with a mask branch')
     if u8:
         return _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map,
-                                      measure, stained)
+                                      measure, stained, neighbors)
     if min_tissue:
         raise ValueError('inference_on_slide: min_tissue applies to 8-bit slides (the background rule is defined on 8-bit RGB values)')
     _, H, W = slide.shape
@@ -205,7 +210,7 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     if label_map:
         _zero_row_masks(inner.headers, per_task)
     merged = {task_id: inner.headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors)
 
 
 def _zero_row_masks(headers, per_task):
@@ -262,13 +267,29 @@ def slide_nucleus_table(result, slide=None, window=None, threshold=0.5):
                                   stain=slide is not None)
 
 
+@torch.no_grad()
+def slide_neighborhood(result, nc, radii_px, field_px=None):
+    """One task's result -> its neighbourhood columns (hd_yolo_amd/spatial.py: neighborhood), device tensors: 'neighbors' int32 (N, K, nc), the
+    other nuclei of every class within each of the K radii (pixels of the result's coordinates) of every nucleus; 'nearest_dist' float64
+    (N, nc) / 'nearest_row' int32 (N, nc), the nearest nucleus of every class within the largest radius (NaN / -1 = none); with field_px,
+    'density' int32 (gy, gx, nc), the nuclei of every class per field.  Positions are the centroids of the result's 'nuclei' table (rows that
+    own no pixel are absent), or the box centres of a result without one; the class of a row is labels - 1.  With a 'label_map' in the result
+    its size bounds the search grid and nothing is read back."""
+    from hd_yolo_amd import spatial
+    table = result.get('nuclei')
+    if table is None:
+        table = result
+    lm = result.get('label_map')
+    return spatial.neighborhood(table, nc, radii_px, field_px=field_px, size=None if lm is None else tuple(lm.shape))
+
+
 def save_nucleus_table(path, table):
     """a nucleus table as .npz or .csv, by the extension of `path` (hd_yolo_amd/measure.py: one device-to-host copy)"""
     from hd_yolo_amd import measure as hmeasure
     hmeasure.save_nucleus_table(path, table)
 
 
-def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=False, measure=False, stained=None):
+def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=False, measure=False, stained=None, neighbors=None):
     """everything after the merge: de-duplication of overlapping windows, clamp to the slide, rescale"""
     out = {}
     for task_id, r in merged.items():
@@ -285,11 +306,14 @@ def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=Fals
             out[task_id]['label_map'], out[task_id]['areas'] = slide_label_map(out[task_id], size)
             if measure:
                 out[task_id]['nuclei'] = slide_nucleus_table(out[task_id], slide=stained)
+                if neighbors is not None:
+                    columns = slide_neighborhood(out[task_id], header.nc, neighbors)
+                    out[task_id]['nuclei'].update({k: columns[k] for k in ('neighbors', 'nearest_dist', 'nearest_row')})
     return out
 
 
 def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map=False,
-                           measure=False, stained=None):
+                           measure=False, stained=None, neighbors=None):
     from hd_yolo_amd import ops
     if isinstance(model, Ensemble):
         raise NotImplementedError('inference_on_slide: 8-bit slides run on one model (Model / Deploy); an Ensemble takes the float slide')
@@ -353,7 +377,7 @@ def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_t
         if label_map:
             _zero_row_masks(headers, per_task)
         merged = {task_id: headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors)
 
 
 SCORE_CELL_SIDES = 4.0          # score_slide: side of an ordering cell, in mean box sides (a block of 256 rows then spans a few cells)
@@ -470,6 +494,8 @@ def main():
     ap.add_argument('--masks', action='store_true', help='--slide: also run the slide through a synthetic mask model (the tiny variant, one mask class, fp32) with compute_masks')
     ap.add_argument('--label-map', action='store_true', help='--slide --masks: paste the masks into one int32 label map of the slide (slide_label_map) and count the owned pixels')
     ap.add_argument('--measure', action='store_true', help='--slide --masks --label-map: measure every nucleus on the label map (slide_nucleus_table; stain columns with --u8)')
+    ap.add_argument('--neighbors', default='', help='--measure: comma-separated radii in pixels, e.g. 32,64: neighbours of every class within each radius of every nucleus (slide_neighborhood)')
+    ap.add_argument('--density', type=float, default=0.0, help='--neighbors: also count the nuclei of every class per field of this many pixels')
     ap.add_argument('--table', default='', help='--measure: write the nucleus table to this .npz or .csv file (save_nucleus_table)')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
@@ -503,13 +529,19 @@ def main():
             ap.error('--label-map needs --masks')
         if opt.measure and not opt.label_map:
             ap.error('--measure needs --label-map')
+        radii = tuple(float(r) for r in opt.neighbors.split(',')) if opt.neighbors else None
+        if radii and not opt.measure:
+            ap.error('--neighbors needs --measure')
+        if opt.density and not radii:
+            ap.error('--density needs --neighbors')
         if opt.masks:
             cfg = synth.make_cfg('n', 2)
             cfg['headers'][0][3][3] = 1                                   # one mask class: the mask model of tests/test_gpu_mask.py
             mm = Model(cfg, synth.make_hyp(conf_thres=0.05))
             mm.load_state_dict(synth.mask_state_dict(mm), strict=False)
             mdep = Deploy(mm.to(device).eval())
-            kw = dict(tile=min(opt.imgsz, opt.slide), batch_size=opt.batch_size, compute_masks=True, label_map=opt.label_map, measure=opt.measure)
+            kw = dict(tile=min(opt.imgsz, opt.slide), batch_size=opt.batch_size, compute_masks=True, label_map=opt.label_map, measure=opt.measure,
+                      neighbors=radii)
             inference_on_slide(mdep, slide, **kw)                         # warm-up: plans
             torch.cuda.synchronize()
             t0 = time.time()
@@ -533,6 +565,22 @@ def main():
                           f'area {med(nt["area"].double()):.1f} px, median major axis {med(nt["major_axis"]):.2f} px'
                           + (f', mean RGB {[round(float(c), 1) for c in nt["mean_rgb"][own].mean(0)]}' if 'mean_rgb' in nt and bool(own.any()) else '')
                           + f' in {dtm:.2f} ms')
+                    if radii:
+                        from hd_yolo_amd import spatial
+                        nc_task = mdep._model.headers[k].nc
+                        torch.cuda.synchronize()
+                        t0 = time.time()
+                        nb = slide_neighborhood(v, nc_task, radii, field_px=opt.density or None)
+                        torch.cuda.synchronize()
+                        dtn = (time.time() - t0) * 1e3
+                        cls = v['labels'].to(torch.int64) - 1
+                        pairs = spatial.interaction_matrix(nb['neighbors'], cls, nc_task)[-1].double()
+                        per_class = torch.bincount(cls[own & (cls >= 0) & (cls < nc_task)], minlength=nc_task).double()
+                        mean = (pairs / per_class[:, None]).tolist()
+                        print(f'neighbours {opt.slide}x{opt.slide}, task {k}: {int(own.sum())} nuclei queried, mean neighbours within {radii[-1]:g} px per class '
+                              f'pair (row: class of the nucleus, column: class of the neighbour) {[[round(x, 3) for x in r] for r in mean]}'
+                              + (f', density grid {tuple(nb["density"].shape)} holds {int(nb["density"].sum())}' if 'density' in nb else '')
+                              + f' in {dtn:.2f} ms')
                     if opt.table:
                         save_nucleus_table(opt.table, v['nuclei'])
                         print(f'nucleus table written to {opt.table}')

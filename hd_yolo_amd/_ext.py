@@ -1,8 +1,11 @@
-"""ctypes binding of the extension headers of libhdyolo_hip.so (include/hdyolo_measure.h).
+"""ctypes binding of the extension headers of libhdyolo_hip.so (include/hdyolo_measure.h, include/hdyolo_spatial.h).
 
 include/hdyolo.h is the numbered ABI and _lib.py its binding; an extension header declares further entry points of the same library under a
 revision of its own, read by the same reader (_header.read(path)) and bound here on the handle _lib.load() returns.  _lib.SIGNATURES,
 _lib.CONSTANTS and HDY_ABI_VERSION know nothing of them.  No CPU fallback: a library without the symbols, or of another revision, raises.
+
+MEASURE_HEADER, SIGNATURES, PARAMS and CONSTANTS are the tables of hdyolo_measure.h, the first extension header; hdyolo_spatial.h has
+SPATIAL_HEADER, SPATIAL_SIGNATURES, SPATIAL_PARAMS and SPATIAL_CONSTANTS.
 """
 import os
 
@@ -16,31 +19,44 @@ PARAMS = _M.params
 CONSTANTS = _M.constants
 MEASURE_REVISION, MEASURE_COLS, MEASURE_MAX_SIDE = (CONSTANTS['HDY_MEASURE_' + n] for n in ('REVISION', 'COLS', 'MAX_SIDE'))
 
+SPATIAL_HEADER = os.path.join(os.path.dirname(_header.HEADER_PATH), 'hdyolo_spatial.h')
+_S = _header.read(SPATIAL_HEADER)
+SPATIAL_SIGNATURES = _S.functions
+SPATIAL_PARAMS = _S.params
+SPATIAL_CONSTANTS = _S.constants
+SPATIAL_REVISION, SPATIAL_SUBPIXEL, SPATIAL_MAX_CLASSES, SPATIAL_MAX_RADII, SPATIAL_MAX_COORD, SPATIAL_MAX_CELLS = (
+    SPATIAL_CONSTANTS['HDY_SPATIAL_' + n] for n in ('REVISION', 'SUBPIXEL', 'MAX_CLASSES', 'MAX_RADII', 'MAX_COORD', 'MAX_CELLS'))
+
+# header file name -> (signatures, the function that returns the library's revision, the revision this binding is written for, its macro)
+_EXTENSIONS = {'hdyolo_measure.h': (SIGNATURES, 'hdy_measure_revision', MEASURE_REVISION, 'HDY_MEASURE_REVISION'),
+               'hdyolo_spatial.h': (SPATIAL_SIGNATURES, 'hdy_spatial_revision', SPATIAL_REVISION, 'HDY_SPATIAL_REVISION')}
+
 _bound = None
 
 
 def load():
-    """The library handle of _lib.load() with the extension's entry points bound (once)."""
+    """The library handle of _lib.load() with the extensions' entry points bound (once)."""
     global _bound
     lib = _lib.load()
     if _bound is not lib:
         rebuild = 'rebuild with `python -m hd_yolo_amd.build --force`'
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name, None)
-            if fn is None:
-                raise HdyError(f'{_lib.LIB_PATH} does not export {name} (include/hdyolo_measure.h): it was built before the extension header '
-                               f'existed; {rebuild}')
-            fn.restype, fn.argtypes = res, args
-        got = lib.hdy_measure_revision()
-        if got != MEASURE_REVISION:
-            raise HdyError(f'{_lib.LIB_PATH} was built for revision {got} of include/hdyolo_measure.h, this binding is written for '
-                           f'{MEASURE_REVISION} (HDY_MEASURE_REVISION): {rebuild}')
+        for header, (signatures, revision_fn, revision, macro) in _EXTENSIONS.items():
+            for name, (res, args) in signatures.items():
+                fn = getattr(lib, name, None)
+                if fn is None:
+                    raise HdyError(f'{_lib.LIB_PATH} does not export {name} (include/{header}): it was built before the extension header '
+                                   f'existed; {rebuild}')
+                fn.restype, fn.argtypes = res, args
+            got = getattr(lib, revision_fn)()
+            if got != revision:
+                raise HdyError(f'{_lib.LIB_PATH} was built for revision {got} of include/{header}, this binding is written for '
+                               f'{revision} ({macro}): {rebuild}')
         _bound = lib
     return lib
 
 
 def call(name, *args):
-    """Call an int-returning entry point of the extension; raise HdyError(hdy_last_error()) on a non-zero status."""
+    """Call an int-returning entry point of an extension; raise HdyError(hdy_last_error()) on a non-zero status."""
     lib = load()
     rc = getattr(lib, name)(*args)
     if rc != 0:

@@ -1231,6 +1231,123 @@ def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
     return sums, extent
 
 
+# ------------------------------------------------------------------------------------------ neighbourhood features (csrc/spatial.hip)
+def _spatial_inputs(who, xy_units, cls, C):
+    """(xy int32 (N, 2) contiguous, class int32 (N,) with every class outside [0, C) as -1) of a point set on the GPU"""
+    require_gpu(xy_units)
+    if xy_units.dtype != torch.int32 or xy_units.dim() != 2 or xy_units.shape[1] != 2:
+        raise _lib.HdyError(f'{who}: positions must be an int32 (N, 2) tensor of units, got {xy_units.dtype} {tuple(xy_units.shape)}')
+    N = xy_units.shape[0]
+    if cls.dtype not in (torch.int32, torch.int64) or tuple(cls.shape) != (N,) or cls.device != xy_units.device:
+        raise _lib.HdyError(f'{who}: classes must be an int32 / int64 ({N},) tensor on {xy_units.device}, got {cls.dtype} {tuple(cls.shape)} on '
+                            f'{cls.device}')
+    C = int(C)
+    return xy_units.contiguous(), torch.where((cls >= 0) & (cls < C), cls, -1).to(torch.int32), N, C
+
+
+def _spatial_pts(xy, cls32, order=None):
+    """pts int32 (N, 4) = (x, y, class, original row), in `order` when given"""
+    rows = torch.arange(xy.shape[0], dtype=torch.int32, device=xy.device)
+    pts = torch.stack([xy[:, 0], xy[:, 1], cls32, rows], 1)
+    return (pts if order is None else pts[order]).contiguous()
+
+
+def spatial_cells(pts, cell_units, ncx, ncy):
+    """(cell_start int32 (ncx * ncy + 1,), status int32 (1,)) of points in cell order (hdy_spatial_cells, include/hdyolo_spatial.h): pts int32
+    (N, 4) = (x, y, class, original row) sorted by cell, absent points last.  status is a device word, non-zero when pts is not in cell order;
+    nothing is read back."""
+    from . import _ext
+    require_gpu(pts)
+    if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_contiguous():
+        raise _lib.HdyError(f'spatial_cells: pts must be a contiguous int32 (N, 4) tensor, got {pts.dtype} {tuple(pts.shape)}')
+    ncx, ncy = int(ncx), int(ncy)
+    cell_start = torch.empty((max(ncx * ncy, 0) + 1,), dtype=torch.int32, device=pts.device)
+    status = torch.empty((1,), dtype=torch.int32, device=pts.device)
+    N = pts.shape[0]
+    _ext.call('hdy_spatial_cells', pts.data_ptr() if N else None, pts.numel(), N, int(cell_units), ncx, ncy, cell_start.data_ptr(), cell_start.numel(),
+              status.data_ptr(), 1, stream_ptr())
+    if N == 0:
+        cell_start.zero_()
+        status.zero_()
+    return cell_start, status
+
+
+def spatial_neighbors_sorted(pts, cell_start, cell_units, ncx, ncy, radii_units, C):
+    """(counts int32 (N, K, C), near_d2 int64 (N, C), near_row int32 (N, C)) from points in cell order and their cell_start
+    (hdy_spatial_neighbors): the second half of spatial_neighbors, rows of the outputs = the points' original rows."""
+    from . import _ext
+    require_gpu(pts)
+    require_gpu(cell_start)
+    if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_contiguous():
+        raise _lib.HdyError(f'spatial_neighbors: pts must be a contiguous int32 (N, 4) tensor, got {pts.dtype} {tuple(pts.shape)}')
+    if cell_start.dtype != torch.int32 or cell_start.dim() != 1 or not cell_start.is_contiguous() or cell_start.device != pts.device:
+        raise _lib.HdyError(f'spatial_neighbors: cell_start must be a contiguous int32 vector on {pts.device}, got {cell_start.dtype} '
+                            f'{tuple(cell_start.shape)}')
+    radii = [int(r) for r in radii_units]
+    N, K, C = pts.shape[0], len(radii), int(C)
+    dev = pts.device
+    counts = torch.empty((N, K, max(C, 0)), dtype=torch.int32, device=dev)
+    near_d2 = torch.empty((N, max(C, 0)), dtype=torch.int64, device=dev)
+    near_row = torch.empty((N, max(C, 0)), dtype=torch.int32, device=dev)
+    host_radii = (ctypes.c_int * max(K, 1))(*radii)                       # a host array: the entry point reads it before it returns
+    p = (lambda t: t.data_ptr() if N else None)
+    _ext.call('hdy_spatial_neighbors', p(pts), pts.numel(), N, cell_start.data_ptr(), cell_start.numel(), int(cell_units), int(ncx), int(ncy),
+              host_radii, K, C, p(counts), counts.numel(), p(near_d2), near_d2.numel(), p(near_row), near_row.numel(), stream_ptr())
+    return counts, near_d2, near_row
+
+
+SPATIAL_GRID_SIDE = 4096        # spatial_neighbors: at most this many cells along a side, whatever the extent (score_slide's bound)
+
+
+def spatial_neighbors(xy_units, cls, C, radii_units, cell_units=None, extent_units=None, info=None):
+    """(counts, near_d2, near_row) of a point set (include/hdyolo_spatial.h): per point, the number of other points of every class c in [0, C)
+    within each of the K radii (counts int32 (N, K, C), cumulative), the squared distance in units to the nearest one of every class within
+    the largest radius (near_d2 int64 (N, C), -1 = none) and its row (near_row int32 (N, C), lowest row among equals, -1 = none).
+    xy_units int32 (N, 2) in units of 1/16 pixel (hd_yolo_amd/spatial.py: to_units); a negative coordinate makes the point absent.  cls: int32 /
+    int64 (N,); a class outside [0, C) makes the point a query only.  radii_units: K strictly increasing integers.
+    cell_units: the side of a search cell (default max(r_K, ceil(extent / 4096))); the result does not depend on it.  extent_units = (x, y)
+    bounds of the coordinates when the caller knows them (the slide's size): without it the largest coordinates are read back once, to size
+    the grid.  The points are ordered by cell with one stable device sort, packed, and handed to hdy_spatial_cells and hdy_spatial_neighbors.
+    info (a dict) receives 'status' (the device word of hdy_spatial_cells: 0 unless the order was broken), 'cell_units', 'ncx', 'ncy' and the
+    workspace of the two calls, 'pts' (the packed points in cell order) and 'cell_start'."""
+    xy, cls32, N, C = _spatial_inputs('spatial_neighbors', xy_units, cls, C)
+    radii = [int(r) for r in radii_units]
+    if not radii:
+        raise _lib.HdyError('spatial_neighbors: no radii')
+    present = (xy >= 0).all(1)
+    if extent_units is None:
+        mx, my = torch.where(present[:, None], xy, 0).amax(0).tolist() if N else (0, 0)
+    else:
+        mx, my = (max(int(v) - 1, 0) for v in extent_units)
+    cell = max(radii[-1], -(-(max(mx, my) + 1) // SPATIAL_GRID_SIDE), 1) if cell_units is None else int(cell_units)
+    if cell < 1:
+        raise _lib.HdyError(f'spatial_neighbors: cell_units={cell} must be positive')
+    ncx, ncy = mx // cell + 1, my // cell + 1
+    cx = torch.div(xy[:, 0], cell, rounding_mode='floor').clamp(max=ncx - 1)
+    cy = torch.div(xy[:, 1], cell, rounding_mode='floor').clamp(max=ncy - 1)
+    cid = torch.where(present, cy.to(torch.int64) * ncx + cx, ncx * ncy)          # absent points behind every cell
+    pts = _spatial_pts(xy, cls32, torch.sort(cid, stable=True)[1])
+    cell_start, status = spatial_cells(pts, cell, ncx, ncy)
+    if info is not None:
+        info.update(status=status, cell_units=cell, ncx=ncx, ncy=ncy, pts=pts, cell_start=cell_start)
+    return spatial_neighbors_sorted(pts, cell_start, cell, ncx, ncy, radii, C)
+
+
+def spatial_density(xy_units, cls, C, g_units, gx, gy):
+    """grid int32 (gy, gx, C): the present points of class c in [0, C) whose position falls into field (y // g_units, x // g_units)
+    (hdy_spatial_density); points outside the gx x gy fields, absent points and query-only points are not counted.  Integer adds only."""
+    from . import _ext
+    xy, cls32, N, C = _spatial_inputs('spatial_density', xy_units, cls, C)
+    gx, gy = int(gx), int(gy)
+    pts = _spatial_pts(xy, cls32)
+    grid = torch.empty((max(gy, 0), max(gx, 0), max(C, 0)), dtype=torch.int32, device=xy.device)
+    _ext.call('hdy_spatial_density', pts.data_ptr() if N else None, pts.numel(), N, int(g_units), gx, gy, C, grid.data_ptr() if grid.numel() else None,
+              grid.numel(), stream_ptr())
+    if N == 0:
+        grid.zero_()                                                      # N = 0 launches nothing
+    return grid
+
+
 # ------------------------------------------------------------------------------------------ mask scoring (csrc/mask_score.hip)
 OVERLAP_MIN_SLOTS, OVERLAP_MAX_SLOTS = 64, _lib.CONSTANTS['HDY_OVERLAP_MAX_SLOTS']
 
