@@ -107,7 +107,15 @@ __global__ __launch_bounds__(2 * BM, (BM == 256 || BN == 128 || STAT) ? 2 : (BN 
     const int tile_step = interleave ? (int)gridDim.x : 1;
     const int tile_begin = interleave ? wg_id : wg_id * tpb;
     const int tile_end = interleave ? tiles_total : min(tile_begin + tpb, tiles_total);
-    if (tile_begin >= tile_end) return;
+    if (tile_begin >= tile_end) {
+        if constexpr (STAT) {                      // a workgroup without tiles still owns slab blockIdx.x of every request: its sums are 0
+            for (int r = 0; r < p.nstat; ++r) {
+                const int w = p.stat[r].c1 - p.stat[r].c0;
+                for (int j = tid; j < 2 * w; j += NTHR) p.stat[r].slabs[(size_t)blockIdx.x * 2 * w + j] = 0.f;
+            }
+        }
+        return;
+    }
     const int nkb = p.Kdp / BKE;
 
     const T* __restrict__ x = (const T*)p.x;

@@ -882,7 +882,7 @@ class Plan:
         # module turns them into dgamma / dbeta and c1 / c2 in the bn_c12 rows
         c1, c2 = self.bn_c12[0, :u.K], self.bn_c12[1, :u.K]
         for (m, o, ch), (kind, idx, off, nslabs) in zip(self._channels(u), b.producers(u.outs)):
-            slabs = self._new(nslabs, 2, o.c, dtype=torch.float32, zero=True)     # workgroups without tiles never write theirs
+            slabs = self._new(nslabs, 2, o.c, dtype=torch.float32, zero=True)     # (every workgroup writes its slab, those without tiles zeros)
             b.pending.setdefault(idx, []).append(ops.StatRequest(u.yraw[..., ch], u.scale[ch], u.shift[ch], slabs, off, u.act))
             b.add(ops.rec_bn_bwd_finalize_slabs(slabs, M, u.mean[ch], u.invstd[ch], b.grad(m.bn.weight), b.grad(m.bn.bias), c1[ch], c2[ch]))
         if dy is not None:

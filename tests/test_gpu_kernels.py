@@ -714,8 +714,9 @@ def test_errors_are_loud():
                                           (96, (7, 10057), True, True), (96, (4, 19200), False, False)])
 def test_fused_1x1_backward_matches_reference_and_the_three_launch_path(K, M, pair, acc):
     """hdy_conv1x1_bwd_fused (BatchNorm/SiLU backward apply + wgrad + dgrad in one pass) against (a) plain torch fp32 on the bf16-rounded
-    operands and (b) the three-launch path (hdy_bn_act_bwd -> dy, hdy_conv_wgrad, hdy_conv_dgrad) it replaces: same dy bits, so dx / dW
-    differ by accumulation order only.  Operands are channel slices of wider buffers; the pair case splits dz over two tensors."""
+    operands and (b) the three-launch path (hdy_bn_act_bwd -> dy, hdy_conv_wgrad, hdy_conv_dgrad) it replaces.  Both round dy to bf16 (the fused kernel into its LDS
+    tile, `o.h[...] = (bf16_t)...`), from fp32 values that differ in the last bits (xhat as y * invstd + (-mean * invstd) with FMAs against
+    (y - mean) * invstd), so a few dy elements fall on neighbouring bf16 values; beyond that dx / dW differ by accumulation order.  Operands are channel slices of wider buffers; the pair case splits dz over two tensors."""
     dt = torch.bfloat16
     C = K
     Nb, Wd = M if isinstance(M, tuple) else (1, M)                         # pixels as Nb rows of Wd (the generic kernels address 16-bit image sides)
@@ -778,7 +779,7 @@ def test_fused_1x1_backward_matches_reference_and_the_three_launch_path(K, M, pa
     assert_close(got_dx, ref_dx, 1.5e-2, 'dx vs torch')
     assert_close(got_dw, ref_dw, 1.5e-2, 'dW vs torch')
     assert_close(got_dx, dx_b.float().cpu().reshape(M, C), 8e-3, 'dx vs three launches')         # one bf16 rounding of the output apart at most
-    assert_close(got_dw, gw_b.cpu()[:, :, 0, 0], 2e-4, 'dW vs three launches', elementwise=False)   # two bf16-operand paths: the three launches round dy to bf16 in between, the fused kernel does not — elements that cancel differ by more than a summation order
+    assert_close(got_dw, gw_b.cpu()[:, :, 0, 0], 2e-4, 'dW vs three launches', elementwise=False)   # two bf16-operand paths: both round dy to bf16, from fp32 values that differ in the last bits (docstring), so single dy elements sit one bf16 step apart — elements that cancel differ by more than a summation order
     # dgrad only / wgrad only
     dx_o = to_dev_nhwc(dx0, dt, ld=C + 8, off=8)
     gw_o = torch.zeros((K, C, 1, 1), device=DEV)
