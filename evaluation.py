@@ -152,7 +152,7 @@ def _check_slide(slide):
 
 @torch.no_grad()
 def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=1.0, iou_thres=None, compute_masks=False, min_tissue=0.0,
-                       background=220, label_map=False, measure=False, neighbors=None):
+                       background=220, label_map=False, measure=False, neighbors=None, outlines=False):
     """Whole-slide detection as the reference's ROI protocol composes it: tiles of one amplification are run in batches, each tile's
     detections carry their 'roi' offset, `Detect.merge_outputs` shifts and concatenates them (yolo_head.py:450-462), overlapping
     windows are de-duplicated by one class-agnostic NMS on the MI355X kernel (as Ensemble.merge does, yolo.py:189-199), and
@@ -175,12 +175,17 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     (not in the reference, which measures nothing).  measure=False launches nothing new.
     neighbors=(r1, r2, ...) (with measure; up to four increasing radii in pixels of the returned coordinates): 'nuclei' gains 'neighbors',
     'nearest_dist' and 'nearest_row', the columns of slide_neighborhood (hd_yolo_amd/spatial.py) for the header's classes.  None launches
-    nothing new."""
+    nothing new.
+    outlines=True (with measure): 'nuclei' gains the shape columns of slide_nucleus_outlines (hd_yolo_amd/outline.py: outline vertices and
+    edges, enclosed area, simple, convex area and perimeter, solidity, convexity, the Feret diameters) and the task gains 'polygons' =
+    (offsets, verts), the outline of every nucleus as a polygon in the returned coordinates.  False launches nothing new."""
     u8 = _check_slide(slide)
     if measure and not label_map:
         raise ValueError('inference_on_slide: measure=True needs label_map=True (the nuclei are measured on the label map)')
     if neighbors is not None and not measure:
         raise ValueError('inference_on_slide: neighbors needs measure=True (the neighbourhoods are those of the nucleus table)')
+    if outlines and not measure:
+        raise ValueError('inference_on_slide: outlines=True needs measure=True (the outlines start from the extents of the nucleus table)')
     stained = slide if measure and u8 and float(scale) == 1.0 else None
     inner = model._model if isinstance(model, Deploy) else model
     if label_map:
@@ -191,7 +196,7 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
             raise ValueError('inference_on_slide: label_map=True needs a model with a mask branch')
     if u8:
         return _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map,
-                                      measure, stained, neighbors)
+                                      measure, stained, neighbors, outlines)
     if min_tissue:
         raise ValueError('inference_on_slide: min_tissue applies to 8-bit slides (the background rule is defined on 8-bit RGB values)')
     _, H, W = slide.shape
@@ -210,7 +215,7 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     if label_map:
         _zero_row_masks(inner.headers, per_task)
     merged = {task_id: inner.headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors, outlines)
 
 
 def _zero_row_masks(headers, per_task):
@@ -283,13 +288,49 @@ def slide_neighborhood(result, nc, radii_px, field_px=None):
     return spatial.neighborhood(table, nc, radii_px, field_px=field_px, size=None if lm is None else tuple(lm.shape))
 
 
+@torch.no_grad()
+def slide_nucleus_outlines(result, window=None):
+    """One task's result with its 'label_map' and 'nuclei' (slide_nucleus_table) -> (shape columns, (offsets, verts)): the columns of
+    hd_yolo_amd/outline.py's shape_table (outline_vertices, outline_edges, enclosed_area, simple, convex_area, solidity, convex_perimeter,
+    convexity, feret_max, feret_min, feret_ratio; device tensors, one row per detection) and the outline of every nucleus as a polygon,
+    vertices of nucleus r = verts[offsets[r]:offsets[r + 1]] in the table's coordinates (slide pixels at the map's magnification).  The
+    extents are the table's 'bbox': nothing is measured again.  window = (x0, y0, w, h): the part of the slide the map holds, as it was given
+    to slide_nucleus_table.  Three passes (ops.label_outline: count and write; ops.label_hull); the number of vertices is read back once, to size verts."""
+    from hd_yolo_amd import ops
+    from hd_yolo_amd import outline as houtline
+    lm, table = result.get('label_map'), result.get('nuclei')
+    if lm is None or table is None:
+        raise ValueError("slide_nucleus_outlines: the result needs 'label_map' and 'nuclei' (inference_on_slide(..., label_map=True, measure=True))")
+    x0, y0 = (0, 0) if window is None else (int(window[0]), int(window[1]))
+    n = table['area']
+    R = len(n)
+    shift = torch.tensor([x0, y0, x0, y0], dtype=torch.int64, device=lm.device)
+    extent = torch.where((n > 0)[:, None], table['bbox'] - shift, table['bbox']).to(torch.int32)        # nucleus_table shifted the rows that own pixels
+    offsets, verts, counts = ops.label_outline(lm, R, extent)
+    hull_i, hull_f = ops.label_hull(lm, R, extent)
+    sums = torch.zeros((R, 7), dtype=torch.int64, device=lm.device)
+    sums[:, 0], sums[:, 6] = n, table['perimeter_edges']
+    columns = houtline.shape_table(sums, counts, hull_i, hull_f)
+    if x0 or y0:
+        verts = verts + torch.tensor([x0, y0], dtype=torch.int32, device=lm.device)
+    return columns, (offsets, verts)
+
+
+def save_polygons(path, polygons, scale=1.0, labels=None, scores=None):
+    """the polygons of slide_nucleus_outlines as .npz or .geojson, by the extension of `path` (hd_yolo_amd/outline.py); scale: the
+    magnification of the run, so that the file speaks the coordinates of the slide as it was given"""
+    from hd_yolo_amd import outline as houtline
+    houtline.save_polygons(path, polygons[0], polygons[1], scale=scale, labels=labels, scores=scores)
+
+
 def save_nucleus_table(path, table):
     """a nucleus table as .npz or .csv, by the extension of `path` (hd_yolo_amd/measure.py: one device-to-host copy)"""
     from hd_yolo_amd import measure as hmeasure
     hmeasure.save_nucleus_table(path, table)
 
 
-def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=False, measure=False, stained=None, neighbors=None):
+def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=False, measure=False, stained=None, neighbors=None,
+                  outlines=False):
     """everything after the merge: de-duplication of overlapping windows, clamp to the slide, rescale"""
     out = {}
     for task_id, r in merged.items():
@@ -309,11 +350,14 @@ def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=Fals
                 if neighbors is not None:
                     columns = slide_neighborhood(out[task_id], header.nc, neighbors)
                     out[task_id]['nuclei'].update({k: columns[k] for k in ('neighbors', 'nearest_dist', 'nearest_row')})
+                if outlines:
+                    columns, out[task_id]['polygons'] = slide_nucleus_outlines(out[task_id])
+                    out[task_id]['nuclei'].update(columns)
     return out
 
 
 def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map=False,
-                           measure=False, stained=None, neighbors=None):
+                           measure=False, stained=None, neighbors=None, outlines=False):
     from hd_yolo_amd import ops
     if isinstance(model, Ensemble):
         raise NotImplementedError('inference_on_slide: 8-bit slides run on one model (Model / Deploy); an Ensemble takes the float slide')
@@ -377,7 +421,7 @@ def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_t
         if label_map:
             _zero_row_masks(headers, per_task)
         merged = {task_id: headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors, outlines)
 
 
 SCORE_CELL_SIDES = 4.0          # score_slide: side of an ordering cell, in mean box sides (a block of 256 rows then spans a few cells)
@@ -497,6 +541,8 @@ def main():
     ap.add_argument('--neighbors', default='', help='--measure: comma-separated radii in pixels, e.g. 32,64: neighbours of every class within each radius of every nucleus (slide_neighborhood)')
     ap.add_argument('--density', type=float, default=0.0, help='--neighbors: also count the nuclei of every class per field of this many pixels')
     ap.add_argument('--table', default='', help='--measure: write the nucleus table to this .npz or .csv file (save_nucleus_table)')
+    ap.add_argument('--outlines', action='store_true', help='--measure: outline every nucleus as a polygon and add the hull descriptors: solidity, convexity, Feret diameters (slide_nucleus_outlines)')
+    ap.add_argument('--polygons', default='', help='--outlines: write the polygons to this .geojson or .npz file (save_polygons)')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
     opt = ap.parse_args()
@@ -534,6 +580,10 @@ def main():
             ap.error('--neighbors needs --measure')
         if opt.density and not radii:
             ap.error('--density needs --neighbors')
+        if opt.outlines and not opt.measure:
+            ap.error('--outlines needs --measure')
+        if opt.polygons and not opt.outlines:
+            ap.error('--polygons needs --outlines')
         if opt.masks:
             cfg = synth.make_cfg('n', 2)
             cfg['headers'][0][3][3] = 1                                   # one mask class: the mask model of tests/test_gpu_mask.py
@@ -541,7 +591,7 @@ def main():
             mm.load_state_dict(synth.mask_state_dict(mm), strict=False)
             mdep = Deploy(mm.to(device).eval())
             kw = dict(tile=min(opt.imgsz, opt.slide), batch_size=opt.batch_size, compute_masks=True, label_map=opt.label_map, measure=opt.measure,
-                      neighbors=radii)
+                      neighbors=radii, outlines=opt.outlines)
             inference_on_slide(mdep, slide, **kw)                         # warm-up: plans
             torch.cuda.synchronize()
             t0 = time.time()
@@ -581,6 +631,20 @@ def main():
                               f'pair (row: class of the nucleus, column: class of the neighbour) {[[round(x, 3) for x in r] for r in mean]}'
                               + (f', density grid {tuple(nb["density"].shape)} holds {int(nb["density"].sum())}' if 'density' in nb else '')
                               + f' in {dtn:.2f} ms')
+                    if opt.outlines:
+                        torch.cuda.synchronize()
+                        t0 = time.time()
+                        sh, polygons = slide_nucleus_outlines(v)
+                        torch.cuda.synchronize()
+                        dto = (time.time() - t0) * 1e3
+                        done = sh['outline_vertices'] > 0
+                        meds = lambda c: float(c[done].median()) if bool(done.any()) else float('nan')
+                        print(f'outlines {opt.slide}x{opt.slide}, task {k}: {int(done.sum())} nuclei outlined with {len(polygons[1])} vertices, '
+                              f'{float((sh["simple"] & done).sum()) / max(int(done.sum()), 1):.3f} simple, median solidity {meds(sh["solidity"]):.3f}, median '
+                              f'Feret max / min {meds(sh["feret_max"]):.2f} / {meds(sh["feret_min"]):.2f} px in {dto:.2f} ms')
+                        if opt.polygons:
+                            save_polygons(opt.polygons, polygons, labels=v.get('labels'), scores=v.get('scores'))
+                            print(f'polygons written to {opt.polygons}')
                     if opt.table:
                         save_nucleus_table(opt.table, v['nuclei'])
                         print(f'nucleus table written to {opt.table}')

@@ -1231,6 +1231,67 @@ def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
     return sums, extent
 
 
+# ------------------------------------------------------------------------------------------ outlines and hulls (csrc/outline.hip)
+def _outline_inputs(who, label_map, R, extent):
+    require_gpu(label_map)
+    if label_map.dtype != torch.int32 or label_map.dim() != 2 or label_map.numel() == 0:
+        raise _lib.HdyError(f'{who}: the map must be a non-empty int32 (h, w) tensor, got {label_map.dtype} {tuple(label_map.shape)}')
+    R = int(R)
+    if R < 0:
+        raise _lib.HdyError(f'{who}: negative row count R={R}')
+    require_gpu(extent)
+    if extent.dtype != torch.int32 or tuple(extent.shape) != (R, 4) or extent.device != label_map.device:
+        raise _lib.HdyError(f'{who}: extent must be an int32 ({R}, 4) tensor on {label_map.device} (ops.label_measure makes it), got '
+                            f'{extent.dtype} {tuple(extent.shape)} on {extent.device}')
+    return label_map.contiguous(), R, extent.contiguous()
+
+
+def label_outline(label_map, R, extent):
+    """(offsets int64 (R + 1,), verts int32 (total, 2), counts int64 (R, 4)) of the R labels of an int32 (h, w) label map: the outer boundary
+    of every label's first 4-connected component as a closed polygon of lattice corners (x, y), clockwise on screen, the start corner first
+    (include/hdyolo_outline.h states the geometry).  extent: the int32 (R, 4) boxes of ops.label_measure on the same map.  counts = {V, twice
+    the enclosed area, unit cracks L, flags (1 empty, 2 box side above 1024, 4 the extent was not this map's)}; the vertices of label r are
+    verts[offsets[r]:offsets[r + 1]].  Two launches (hdy_label_outline_count, hdy_label_outline_write) with torch.cumsum between them on the
+    device.  `total`, the number of vertices, is the one scalar of the result this call reads back: it sizes verts.  The status word of the
+    writing pass (non-zero when the second walk disagrees with the first) is read once the pass is queued and raises."""
+    from . import _ext
+    lm, R, extent = _outline_inputs('label_outline', label_map, R, extent)
+    h, w = lm.shape
+    dev = lm.device
+    counts = torch.empty((R, 4), dtype=torch.int64, device=dev)
+    offsets = torch.zeros((R + 1,), dtype=torch.int64, device=dev)
+    if R == 0:
+        return offsets, torch.empty((0, 2), dtype=torch.int32, device=dev), counts
+    head = (lm.data_ptr(), lm.numel(), h, w, extent.data_ptr(), extent.numel(), R)
+    _ext.call('hdy_label_outline_count', *head, counts.data_ptr(), counts.numel(), stream_ptr())
+    torch.cumsum(counts[:, 0], 0, out=offsets[1:])
+    total = int(offsets[-1])                                              # the read-back that sizes verts
+    verts = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    _ext.call('hdy_label_outline_write', *head, offsets.data_ptr(), offsets.numel(), verts.data_ptr() if total else None, verts.numel(),
+              status.data_ptr(), stream_ptr())
+    if int(status):
+        raise _lib.HdyError('label_outline: the writing pass counted other vertices than the counting pass (status 1): the map or the extent '
+                            'changed between the two launches')
+    return offsets, verts, counts
+
+
+def label_hull(label_map, R, extent):
+    """(hull_i int64 (R, 4), hull_f float64 (R, 2)) of the R labels of an int32 (h, w) label map (hdy_label_hull, include/hdyolo_outline.h): the
+    convex hull of all pixel squares of every label, fragments included, holes ignored.  hull_i = {hull vertices, twice the hull area, squared
+    maximum Feret diameter, flags as label_outline's}, exact; hull_f = {hull perimeter, minimum Feret diameter}.  extent: ops.label_measure's.
+    One pass, nothing is read back."""
+    from . import _ext
+    lm, R, extent = _outline_inputs('label_hull', label_map, R, extent)
+    h, w = lm.shape
+    hull_i = torch.empty((R, 4), dtype=torch.int64, device=lm.device)
+    hull_f = torch.empty((R, 2), dtype=torch.float64, device=lm.device)
+    if R:
+        _ext.call('hdy_label_hull', lm.data_ptr(), lm.numel(), h, w, extent.data_ptr(), extent.numel(), R, hull_i.data_ptr(), hull_i.numel(),
+                  hull_f.data_ptr(), hull_f.numel(), stream_ptr())
+    return hull_i, hull_f
+
+
 # ------------------------------------------------------------------------------------------ neighbourhood features (csrc/spatial.hip)
 def _spatial_inputs(who, xy_units, cls, C):
     """(xy int32 (N, 2) contiguous, class int32 (N,) with every class outside [0, C) as -1) of a point set on the GPU"""
