@@ -152,7 +152,7 @@ def _check_slide(slide):
 
 @torch.no_grad()
 def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=1.0, iou_thres=None, compute_masks=False, min_tissue=0.0,
-                       background=220, label_map=False, measure=False, neighbors=None, outlines=False):
+                       background=220, label_map=False, measure=False, neighbors=None, outlines=False, graph=None):
     """Whole-slide detection as the reference's ROI protocol composes it: tiles of one amplification are run in batches, each tile's
     detections carry their 'roi' offset, `Detect.merge_outputs` shifts and concatenates them (yolo_head.py:450-462), overlapping
     windows are de-duplicated by one class-agnostic NMS on the MI355X kernel (as Ensemble.merge does, yolo.py:189-199), and
@@ -178,7 +178,10 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     nothing new.
     outlines=True (with measure): 'nuclei' gains the shape columns of slide_nucleus_outlines (hd_yolo_amd/outline.py: outline vertices and
     edges, enclosed area, simple, convex area and perimeter, solidity, convexity, the Feret diameters) and the task gains 'polygons' =
-    (offsets, verts), the outline of every nucleus as a polygon in the returned coordinates.  False launches nothing new."""
+    (offsets, verts), the outline of every nucleus as a polygon in the returned coordinates.  False launches nothing new.
+    graph=(k, max_px) (with measure): the task gains 'graph', the cell graph of slide_cell_graph: every nucleus joined to its k <= 16 nearest
+    nuclei of the header's classes within max_px pixels of the returned coordinates, with the union edge list.  'nuclei' keeps its columns.
+    None launches nothing new."""
     u8 = _check_slide(slide)
     if measure and not label_map:
         raise ValueError('inference_on_slide: measure=True needs label_map=True (the nuclei are measured on the label map)')
@@ -186,6 +189,8 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
         raise ValueError('inference_on_slide: neighbors needs measure=True (the neighbourhoods are those of the nucleus table)')
     if outlines and not measure:
         raise ValueError('inference_on_slide: outlines=True needs measure=True (the outlines start from the extents of the nucleus table)')
+    if graph is not None and not measure:
+        raise ValueError('inference_on_slide: graph needs measure=True (the nodes of the graph are the rows of the nucleus table)')
     stained = slide if measure and u8 and float(scale) == 1.0 else None
     inner = model._model if isinstance(model, Deploy) else model
     if label_map:
@@ -196,7 +201,7 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
             raise ValueError('inference_on_slide: label_map=True needs a model with a mask branch')
     if u8:
         return _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map,
-                                      measure, stained, neighbors, outlines)
+                                      measure, stained, neighbors, outlines, graph)
     if min_tissue:
         raise ValueError('inference_on_slide: min_tissue applies to 8-bit slides (the background rule is defined on 8-bit RGB values)')
     _, H, W = slide.shape
@@ -215,7 +220,7 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     if label_map:
         _zero_row_masks(inner.headers, per_task)
     merged = {task_id: inner.headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors, outlines)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors, outlines, graph)
 
 
 def _zero_row_masks(headers, per_task):
@@ -316,6 +321,31 @@ def slide_nucleus_outlines(result, window=None):
     return columns, (offsets, verts)
 
 
+@torch.no_grad()
+def slide_cell_graph(result, k, max_px, nc=None, mode='union'):
+    """One task's result -> its cell graph (hd_yolo_amd/graph.py: knn_graph and edges), a dict of device tensors: 'knn_row' int32 (N, k), the
+    rows of the k <= 16 nearest other nuclei within max_px pixels of the result's coordinates, nearest first, ties by the lowest row, -1
+    padding; 'knn_dist' float64 (N, k) pixels (NaN padding); 'knn_count' int32 (N,); 'knn_mutual' bool (N, k); and the edge list of `mode`
+    ('union', 'mutual' or 'directed'): 'edge_index' int64 (2, E), 'edge_dist' float64 (E,), 'edge_mutual' bool (E,).  Positions are those of
+    slide_neighborhood: the centroids of the result's 'nuclei' table (rows that own no pixel are absent), or the box centres of a result
+    without one.  With nc, the class of a row is labels - 1 and a row outside 0 .. nc - 1 is a query only; without it every present row is a
+    node.  With a 'label_map' in the result its size bounds the search grid: the one scalar read back is the number of edges."""
+    from hd_yolo_amd import graph as hgraph
+    table = result.get('nuclei')
+    if table is None:
+        table = result
+    lm = result.get('label_map')
+    g = hgraph.knn_graph(table, k, max_px, nc=nc, size=None if lm is None else tuple(lm.shape))
+    g.update(hgraph.edges(g, mode))
+    return g
+
+
+def save_cell_graph(path, graph, xy=None, labels=None):
+    """the dict of slide_cell_graph as .npz (hd_yolo_amd/graph.py: one device-to-host copy); xy (N, 2) and labels (N,) go in beside it"""
+    from hd_yolo_amd import graph as hgraph
+    hgraph.save_cell_graph(path, graph, graph, xy=xy, labels=labels)
+
+
 def save_polygons(path, polygons, scale=1.0, labels=None, scores=None):
     """the polygons of slide_nucleus_outlines as .npz or .geojson, by the extension of `path` (hd_yolo_amd/outline.py); scale: the
     magnification of the run, so that the file speaks the coordinates of the slide as it was given"""
@@ -330,7 +360,7 @@ def save_nucleus_table(path, table):
 
 
 def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=False, measure=False, stained=None, neighbors=None,
-                  outlines=False):
+                  outlines=False, graph=None):
     """everything after the merge: de-duplication of overlapping windows, clamp to the slide, rescale"""
     out = {}
     for task_id, r in merged.items():
@@ -353,11 +383,13 @@ def _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map=Fals
                 if outlines:
                     columns, out[task_id]['polygons'] = slide_nucleus_outlines(out[task_id])
                     out[task_id]['nuclei'].update(columns)
+                if graph is not None:
+                    out[task_id]['graph'] = slide_cell_graph(out[task_id], graph[0], graph[1], nc=header.nc)
     return out
 
 
 def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_thres, compute_masks, min_tissue, background, label_map=False,
-                           measure=False, stained=None, neighbors=None, outlines=False):
+                           measure=False, stained=None, neighbors=None, outlines=False, graph=None):
     from hd_yolo_amd import ops
     if isinstance(model, Ensemble):
         raise NotImplementedError('inference_on_slide: 8-bit slides run on one model (Model / Deploy); an Ensemble takes the float slide')
@@ -421,7 +453,7 @@ def _inference_on_slide_u8(model, slide, tile, overlap, batch_size, scale, iou_t
         if label_map:
             _zero_row_masks(headers, per_task)
         merged = {task_id: headers[task_id].merge_outputs(parts) for task_id, parts in per_task.items()}
-    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors, outlines)
+    return _finish_slide(inner, merged, H, W, overlap, scale, iou_thres, label_map, measure, stained, neighbors, outlines, graph)
 
 
 SCORE_CELL_SIDES = 4.0          # score_slide: side of an ordering cell, in mean box sides (a block of 256 rows then spans a few cells)
@@ -543,6 +575,8 @@ def main():
     ap.add_argument('--table', default='', help='--measure: write the nucleus table to this .npz or .csv file (save_nucleus_table)')
     ap.add_argument('--outlines', action='store_true', help='--measure: outline every nucleus as a polygon and add the hull descriptors: solidity, convexity, Feret diameters (slide_nucleus_outlines)')
     ap.add_argument('--polygons', default='', help='--outlines: write the polygons to this .geojson or .npz file (save_polygons)')
+    ap.add_argument('--graph', default='', help='--measure: K,PX, e.g. 8,64: join every nucleus to its K <= 16 nearest nuclei within PX pixels (slide_cell_graph)')
+    ap.add_argument('--graph-file', default='', help='--graph: write the cell graph to this .npz file (save_cell_graph)')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
     opt = ap.parse_args()
@@ -584,6 +618,16 @@ def main():
             ap.error('--outlines needs --measure')
         if opt.polygons and not opt.outlines:
             ap.error('--polygons needs --outlines')
+        knn = None
+        if opt.graph:
+            parts = opt.graph.split(',')
+            if len(parts) != 2:
+                ap.error('--graph takes K,PX, e.g. 8,64')
+            knn = (int(parts[0]), float(parts[1]))
+        if knn and not opt.measure:
+            ap.error('--graph needs --measure')
+        if opt.graph_file and not knn:
+            ap.error('--graph-file needs --graph')
         if opt.masks:
             cfg = synth.make_cfg('n', 2)
             cfg['headers'][0][3][3] = 1                                   # one mask class: the mask model of tests/test_gpu_mask.py
@@ -591,7 +635,7 @@ def main():
             mm.load_state_dict(synth.mask_state_dict(mm), strict=False)
             mdep = Deploy(mm.to(device).eval())
             kw = dict(tile=min(opt.imgsz, opt.slide), batch_size=opt.batch_size, compute_masks=True, label_map=opt.label_map, measure=opt.measure,
-                      neighbors=radii, outlines=opt.outlines)
+                      neighbors=radii, outlines=opt.outlines, graph=knn)
             inference_on_slide(mdep, slide, **kw)                         # warm-up: plans
             torch.cuda.synchronize()
             t0 = time.time()
@@ -645,6 +689,21 @@ def main():
                         if opt.polygons:
                             save_polygons(opt.polygons, polygons, labels=v.get('labels'), scores=v.get('scores'))
                             print(f'polygons written to {opt.polygons}')
+                    if knn:
+                        torch.cuda.synchronize()
+                        t0 = time.time()
+                        cg = slide_cell_graph(v, knn[0], knn[1], nc=mdep._model.headers[k].nc)
+                        torch.cuda.synchronize()
+                        dtg = (time.time() - t0) * 1e3
+                        E = cg['edge_index'].shape[1]
+                        held = cg['knn_dist'][~torch.isnan(cg['knn_dist'])]
+                        print(f'graph {opt.slide}x{opt.slide}, task {k}: {int((cg["knn_count"] > 0).sum())} nodes with neighbours of {len(cg["knn_count"])} '
+                              f'rows, {E} edges (k = {knn[0]} within {knn[1]:g} px), {float(cg["edge_mutual"].sum()) / max(E, 1):.3f} mutual, median kNN '
+                              f'distance {float(held.median()) if held.numel() else float("nan"):.2f} px in {dtg:.2f} ms')
+                        if opt.graph_file:
+                            xy = torch.stack([v['nuclei']['centroid_x'], v['nuclei']['centroid_y']], 1)
+                            save_cell_graph(opt.graph_file, cg, xy=xy, labels=v.get('labels'))
+                            print(f'cell graph written to {opt.graph_file}')
                     if opt.table:
                         save_nucleus_table(opt.table, v['nuclei'])
                         print(f'nucleus table written to {opt.table}')

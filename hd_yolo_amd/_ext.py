@@ -1,11 +1,12 @@
-"""ctypes binding of the extension headers of libhdyolo_hip.so (include/hdyolo_measure.h, include/hdyolo_spatial.h, include/hdyolo_outline.h).
+"""ctypes binding of the extension headers of libhdyolo_hip.so (include/hdyolo_measure.h, include/hdyolo_spatial.h, include/hdyolo_outline.h,
+include/hdyolo_graph.h).
 
 include/hdyolo.h is the numbered ABI and _lib.py its binding; an extension header declares further entry points of the same library under a
 revision of its own, read by the same reader (_header.read(path)) and bound here on the handle _lib.load() returns.  _lib.SIGNATURES,
 _lib.CONSTANTS and HDY_ABI_VERSION know nothing of them.  No CPU fallback: a library without the symbols, or of another revision, raises.
 
 MEASURE_HEADER, SIGNATURES, PARAMS and CONSTANTS are the tables of hdyolo_measure.h, the first extension header; hdyolo_spatial.h has
-SPATIAL_HEADER, SPATIAL_SIGNATURES, SPATIAL_PARAMS and SPATIAL_CONSTANTS, hdyolo_outline.h the same four under OUTLINE_.
+SPATIAL_HEADER, SPATIAL_SIGNATURES, SPATIAL_PARAMS and SPATIAL_CONSTANTS, hdyolo_outline.h the same four under OUTLINE_, hdyolo_graph.h under GRAPH_.
 """
 import os
 
@@ -34,10 +35,18 @@ OUTLINE_PARAMS = _O.params
 OUTLINE_CONSTANTS = _O.constants
 OUTLINE_REVISION, OUTLINE_MAX_SIDE, OUTLINE_MAX_WINDOW = (OUTLINE_CONSTANTS['HDY_OUTLINE_' + n] for n in ('REVISION', 'MAX_SIDE', 'MAX_WINDOW'))
 
+GRAPH_HEADER = os.path.join(os.path.dirname(_header.HEADER_PATH), 'hdyolo_graph.h')
+_G = _header.read(GRAPH_HEADER)
+GRAPH_SIGNATURES = _G.functions
+GRAPH_PARAMS = _G.params
+GRAPH_CONSTANTS = _G.constants
+GRAPH_REVISION, GRAPH_MAX_K, GRAPH_MAX_RINGS = (GRAPH_CONSTANTS['HDY_GRAPH_' + n] for n in ('REVISION', 'MAX_K', 'MAX_RINGS'))
+
 # header file name -> (signatures, the function that returns the library's revision, the revision this binding is written for, its macro)
 _EXTENSIONS = {'hdyolo_measure.h': (SIGNATURES, 'hdy_measure_revision', MEASURE_REVISION, 'HDY_MEASURE_REVISION'),
                'hdyolo_spatial.h': (SPATIAL_SIGNATURES, 'hdy_spatial_revision', SPATIAL_REVISION, 'HDY_SPATIAL_REVISION'),
-               'hdyolo_outline.h': (OUTLINE_SIGNATURES, 'hdy_outline_revision', OUTLINE_REVISION, 'HDY_OUTLINE_REVISION')}
+               'hdyolo_outline.h': (OUTLINE_SIGNATURES, 'hdy_outline_revision', OUTLINE_REVISION, 'HDY_OUTLINE_REVISION'),
+               'hdyolo_graph.h': (GRAPH_SIGNATURES, 'hdy_graph_revision', GRAPH_REVISION, 'HDY_GRAPH_REVISION')}
 
 _bound = None
 

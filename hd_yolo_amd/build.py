@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(CSRC, 'build')
 LIB = os.path.join(OUT, 'libhdyolo_hip.so')
-SOURCES = ['api.hip', 'conv_dispatch.hip', 'conv_igemm.hip', 'conv3x3.hip', 'conv3x3_c128.hip', 'conv3x3s2.hip', 'conv_deep.hip', 'conv_stem.hip', 'conv_wgrad.hip', 'conv_wgrad3x3.hip', 'conv_wgrad_deep.hip', 'conv_dgrad_s2.hip', 'conv1x1_bwd.hip', 'bn_act.hip', 'pool.hip', 'detect.hip', 'nms_grid.hip', 'slide.hip', 'augment.hip', 'augment_masks.hip', 'score.hip', 'paste.hip', 'mask_score.hip', 'measure.hip', 'spatial.hip', 'outline.hip', 'loss.hip', 'roi.hip', 'seg.hip', 'optim.hip', 'exec.hip']
+SOURCES = ['api.hip', 'conv_dispatch.hip', 'conv_igemm.hip', 'conv3x3.hip', 'conv3x3_c128.hip', 'conv3x3s2.hip', 'conv_deep.hip', 'conv_stem.hip', 'conv_wgrad.hip', 'conv_wgrad3x3.hip', 'conv_wgrad_deep.hip', 'conv_dgrad_s2.hip', 'conv1x1_bwd.hip', 'bn_act.hip', 'pool.hip', 'detect.hip', 'nms_grid.hip', 'slide.hip', 'augment.hip', 'augment_masks.hip', 'score.hip', 'paste.hip', 'mask_score.hip', 'measure.hip', 'spatial.hip', 'outline.hip', 'graph.hip', 'loss.hip', 'roi.hip', 'seg.hip', 'optim.hip', 'exec.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
          '-I' + CSRC, '-I' + os.path.join(os.path.dirname(HERE), 'include')]
 
@@ -23,7 +23,7 @@ def _newer(a, bs):
 def build(force=False, verbose=True):
     os.makedirs(OUT, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith('.h')]
-    headers += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('hdyolo.h', 'hdyolo_measure.h', 'hdyolo_spatial.h', 'hdyolo_outline.h')]
+    headers += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('hdyolo.h', 'hdyolo_measure.h', 'hdyolo_spatial.h', 'hdyolo_outline.h', 'hdyolo_graph.h')]
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 
     def compile_one(src):

@@ -1409,6 +1409,95 @@ def spatial_density(xy_units, cls, C, g_units, gx, gy):
     return grid
 
 
+# ------------------------------------------------------------------------------------------ k nearest neighbours (csrc/graph.hip)
+KNN_CELL_FILL = 0.25            # spatial_knn's default cell aims at this many times k points per cell: a lane then searches two rings or three, about 6 k
+                                # candidates; 2, 1 and 0.5 each lost the sweep of scripts/bench_graph.py to its half
+
+
+def spatial_knn_sorted(pts, cell_start, cell_units, ncx, ncy, k, max_radius_units):
+    """(nbr_row int32 (N, k), nbr_d2 int64 (N, k), nbr_count int32 (N,)) from points in cell order and their cell_start (hdy_graph_knn,
+    include/hdyolo_graph.h): the second half of spatial_knn, rows of the outputs = the points' original rows."""
+    from . import _ext
+    require_gpu(pts)
+    require_gpu(cell_start)
+    if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_contiguous():
+        raise _lib.HdyError(f'spatial_knn: pts must be a contiguous int32 (N, 4) tensor, got {pts.dtype} {tuple(pts.shape)}')
+    if cell_start.dtype != torch.int32 or cell_start.dim() != 1 or not cell_start.is_contiguous() or cell_start.device != pts.device:
+        raise _lib.HdyError(f'spatial_knn: cell_start must be a contiguous int32 vector on {pts.device}, got {cell_start.dtype} '
+                            f'{tuple(cell_start.shape)}')
+    N, k = pts.shape[0], int(k)
+    dev = pts.device
+    nbr_row = torch.empty((N, max(k, 0)), dtype=torch.int32, device=dev)
+    nbr_d2 = torch.empty((N, max(k, 0)), dtype=torch.int64, device=dev)
+    nbr_count = torch.empty((N,), dtype=torch.int32, device=dev)
+    p = (lambda t: t.data_ptr() if N else None)
+    _ext.call('hdy_graph_knn', p(pts), pts.numel(), N, cell_start.data_ptr(), cell_start.numel(), int(cell_units), int(ncx), int(ncy), k,
+              int(max_radius_units), p(nbr_row), nbr_row.numel(), p(nbr_d2), nbr_d2.numel(), p(nbr_count), nbr_count.numel(), stream_ptr())
+    return nbr_row, nbr_d2, nbr_count
+
+
+def knn_cell_units(N, k, max_radius_units, mx, my, fill=KNN_CELL_FILL):
+    """The default cell side of spatial_knn, host arithmetic only: the side at which a cell of an (mx + 1) x (my + 1) extent with N points
+    spread evenly holds fill * k of them, floored by ceil(max_radius / HDY_GRAPH_MAX_RINGS) (the ring bound of hdy_graph_knn) and by
+    ceil(extent / SPATIAL_GRID_SIDE)."""
+    import math
+    from . import _ext
+    want = math.isqrt(int((mx + 1) * (my + 1) * fill * max(int(k), 1)) // max(int(N), 1))
+    return max(want, -(-int(max_radius_units) // _ext.GRAPH_MAX_RINGS), -(-(max(mx, my) + 1) // SPATIAL_GRID_SIDE), 1)
+
+
+def spatial_knn(xy_units, k, max_radius_units, cls=None, C=None, cell_units=None, extent_units=None, info=None):
+    """(nbr_row, nbr_d2, nbr_count) of a point set (include/hdyolo_graph.h): per point the rows of its k nearest other nodes within
+    max_radius_units, nearest first, ties by the lowest row (nbr_row int32 (N, k), -1 padding), their squared distances in units (nbr_d2 int64
+    (N, k), -1 padding) and how many there are (nbr_count int32 (N,)).
+    xy_units int32 (N, 2) in units of 1/16 pixel; a negative coordinate makes the point absent (-1 / -1 / 0).  With cls (int32 / int64 (N,)) and C,
+    a point of a class outside [0, C) is a query only: it gets neighbours and is nobody's; without them every present point is a node.
+    cell_units: the side of a search cell (default knn_cell_units: about KNN_CELL_FILL * k points per cell); the result does not depend on it,
+    but ceil(max_radius_units / cell_units) may not pass HDY_GRAPH_MAX_RINGS.  extent_units = (x, y) bounds of the coordinates when the caller
+    knows them: without it the largest coordinates are read back once, to size the grid; with it nothing is read back.  The points are ordered
+    by cell with one stable device sort, packed, and handed to hdy_spatial_cells and hdy_graph_knn.  info (a dict) receives what
+    spatial_neighbors puts there: 'status', 'cell_units', 'ncx', 'ncy', 'pts' and 'cell_start'."""
+    if (cls is None) != (C is None):
+        raise _lib.HdyError('spatial_knn: cls and C go together')
+    if cls is None:
+        require_gpu(xy_units)
+        cls, C = torch.zeros((xy_units.shape[0] if xy_units.dim() else 0,), dtype=torch.int32, device=xy_units.device), 1
+    xy, cls32, N, C = _spatial_inputs('spatial_knn', xy_units, cls, C)
+    k, rmax = int(k), int(max_radius_units)
+    present = (xy >= 0).all(1)
+    if extent_units is None:
+        mx, my = torch.where(present[:, None], xy, 0).amax(0).tolist() if N else (0, 0)
+    else:
+        mx, my = (max(int(v) - 1, 0) for v in extent_units)
+    cell = knn_cell_units(N, k, rmax, mx, my) if cell_units is None else int(cell_units)
+    if cell < 1:
+        raise _lib.HdyError(f'spatial_knn: cell_units={cell} must be positive')
+    ncx, ncy = mx // cell + 1, my // cell + 1
+    cx = torch.div(xy[:, 0], cell, rounding_mode='floor').clamp(max=ncx - 1)
+    cy = torch.div(xy[:, 1], cell, rounding_mode='floor').clamp(max=ncy - 1)
+    cid = torch.where(present, cy.to(torch.int64) * ncx + cx, ncx * ncy)          # absent points behind every cell
+    pts = _spatial_pts(xy, cls32, torch.sort(cid, stable=True)[1])
+    cell_start, status = spatial_cells(pts, cell, ncx, ncy)
+    if info is not None:
+        info.update(status=status, cell_units=cell, ncx=ncx, ncy=ncy, pts=pts, cell_start=cell_start)
+    return spatial_knn_sorted(pts, cell_start, cell, ncx, ncy, k, rmax)
+
+
+def knn_mutual(nbr_row):
+    """mutual int32 (N, k) of nbr_row int32 (N, k) (hdy_graph_mutual): entry (p, s) is 1 when q = nbr_row[p, s] is a row and p is among q's
+    neighbours, else 0.  Any content of nbr_row is safe."""
+    from . import _ext
+    require_gpu(nbr_row)
+    if nbr_row.dtype != torch.int32 or nbr_row.dim() != 2:
+        raise _lib.HdyError(f'knn_mutual: nbr_row must be an int32 (N, k) tensor, got {nbr_row.dtype} {tuple(nbr_row.shape)}')
+    nbr_row = nbr_row.contiguous()
+    N, k = nbr_row.shape
+    mutual = torch.empty((N, k), dtype=torch.int32, device=nbr_row.device)
+    p = (lambda t: t.data_ptr() if N else None)
+    _ext.call('hdy_graph_mutual', p(nbr_row), nbr_row.numel(), N, k, p(mutual), mutual.numel(), stream_ptr())
+    return mutual
+
+
 # ------------------------------------------------------------------------------------------ mask scoring (csrc/mask_score.hip)
 OVERLAP_MIN_SLOTS, OVERLAP_MAX_SLOTS = 64, _lib.CONSTANTS['HDY_OVERLAP_MAX_SLOTS']
 

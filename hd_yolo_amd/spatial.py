@@ -32,6 +32,13 @@ def _points(t, nc):
     """(xy int32 (N, 2) units, class int64 (N,)) of a nucleus table or a result"""
     if 'labels' not in t:
         raise ValueError("neighborhood: the table or result has no 'labels' (the class of a nucleus is labels - 1)")
+    xy = _positions(t)
+    cls = t['labels'].to(device=xy.device, dtype=torch.int64).reshape(-1) - 1
+    return xy, torch.where((cls >= 0) & (cls < int(nc)), cls, -1)
+
+
+def _positions(t):
+    """xy int32 (N, 2) units of a nucleus table (centroids; rows of area 0 absent) or a result (box centres)"""
     if 'centroid_x' in t:
         xy = torch.stack([t['centroid_x'], t['centroid_y']], 1).double()
         if 'area' in t:
@@ -41,8 +48,7 @@ def _points(t, nc):
         xy = torch.stack([(b[:, 0] + b[:, 2]) * 0.5, (b[:, 1] + b[:, 3]) * 0.5], 1)
     else:
         raise ValueError("neighborhood: neither a nucleus table ('centroid_x', 'centroid_y') nor a result ('boxes')")
-    cls = t['labels'].to(device=xy.device, dtype=torch.int64).reshape(-1) - 1
-    return to_units(xy), torch.where((cls >= 0) & (cls < int(nc)), cls, -1)
+    return to_units(xy)
 
 
 @torch.no_grad()
