@@ -369,7 +369,8 @@ inline int next_pow2(int v) {
 // (child, parent) pair of the class tree in the reference's order: child *= parent, in place on the padded NMS rows), then per kept box
 // score = best class score if it beats conf, else objectness; label = best class + 1, else -100 — written COMPACTED (image b's rows start
 // at the sum of the earlier images' counts, which every workgroup adds up for itself) so that the host splits three tensors instead of
-// slicing 3 x B padded ones.  multi_label: all 1 + nc scores per box and (score > conf) flags.
+// slicing 3 x B padded ones.  multi_label: all 1 + nc scores per box and (score > conf) flags.  A NaN among the class scores is the maximum
+// (the first NaN, as torch.max): no hit, the objectness and -100.
 __global__ __launch_bounds__(256) void det_outputs_kernel(float* __restrict__ scores, const float* __restrict__ boxes, const int* __restrict__ n_keep,
                                                           int B, int max_det, int nc, const int* __restrict__ pairs, int npairs, float conf,
                                                           int multi_label, float* __restrict__ out_boxes, float* __restrict__ out_scores,
@@ -403,8 +404,10 @@ __global__ __launch_bounds__(256) void det_outputs_kernel(float* __restrict__ sc
         } else {
             float best = row[1];
             int arg = 0;
-            for (int c = 1; c < nc; ++c)
-                if (row[1 + c] > best) { best = row[1 + c]; arg = c; }       // first maximum, as torch.max
+            for (int c = 1; c < nc; ++c) {
+                const float v = row[1 + c];
+                if (v > best || (v != v && best == best)) { best = v; arg = c; }       // first maximum, as torch.max: a NaN is the maximum, the first NaN stays
+            }
             const bool hit = best > conf;
             out_scores[off + j] = hit ? best : row[0];
             ((long long*)out_labels)[off + j] = hit ? arg + 1 : -100;
