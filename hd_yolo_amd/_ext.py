@@ -1,52 +1,43 @@
 """ctypes binding of the extension headers of libhdyolo_hip.so (include/hdyolo_measure.h, include/hdyolo_spatial.h, include/hdyolo_outline.h,
-include/hdyolo_graph.h).
+include/hdyolo_graph.h: _header.EXTENSION_NAMES).
 
 include/hdyolo.h is the numbered ABI and _lib.py its binding; an extension header declares further entry points of the same library under a
 revision of its own, read by the same reader (_header.read(path)) and bound here on the handle _lib.load() returns.  _lib.SIGNATURES,
 _lib.CONSTANTS and HDY_ABI_VERSION know nothing of them.  No CPU fallback: a library without the symbols, or of another revision, raises.
 
-MEASURE_HEADER, SIGNATURES, PARAMS and CONSTANTS are the tables of hdyolo_measure.h, the first extension header; hdyolo_spatial.h has
-SPATIAL_HEADER, SPATIAL_SIGNATURES, SPATIAL_PARAMS and SPATIAL_CONSTANTS, hdyolo_outline.h the same four under OUTLINE_, hdyolo_graph.h under GRAPH_.
+EXTENSIONS maps an extension's short name to its tables; SIGNATURES, PARAMS and CONSTANTS are their unions.  A name belongs to one header:
+the import fails when two of them, or one of them and include/hdyolo.h, declare the same function or constant.
 """
 import os
+from collections import namedtuple
 
 from . import _header, _lib
 from ._header import HdyError
 
-MEASURE_HEADER = os.path.join(os.path.dirname(_header.HEADER_PATH), 'hdyolo_measure.h')
-_M = _header.read(MEASURE_HEADER)
-SIGNATURES = _M.functions         # name -> (restype, [argtypes]) of every function include/hdyolo_measure.h declares
-PARAMS = _M.params
-CONSTANTS = _M.constants
-MEASURE_REVISION, MEASURE_COLS, MEASURE_MAX_SIDE = (CONSTANTS['HDY_MEASURE_' + n] for n in ('REVISION', 'COLS', 'MAX_SIDE'))
+# functions, params, constants: as _header.Header's; revision_fn returns the library's revision, revision_macro states the one bound here
+Extension = namedtuple('Extension', 'header functions params constants revision_fn revision revision_macro')
 
-SPATIAL_HEADER = os.path.join(os.path.dirname(_header.HEADER_PATH), 'hdyolo_spatial.h')
-_S = _header.read(SPATIAL_HEADER)
-SPATIAL_SIGNATURES = _S.functions
-SPATIAL_PARAMS = _S.params
-SPATIAL_CONSTANTS = _S.constants
-SPATIAL_REVISION, SPATIAL_SUBPIXEL, SPATIAL_MAX_CLASSES, SPATIAL_MAX_RADII, SPATIAL_MAX_COORD, SPATIAL_MAX_CELLS = (
-    SPATIAL_CONSTANTS['HDY_SPATIAL_' + n] for n in ('REVISION', 'SUBPIXEL', 'MAX_CLASSES', 'MAX_RADII', 'MAX_COORD', 'MAX_CELLS'))
+EXTENSIONS = {}
+for _name, _macro in ((n, f'HDY_{n.upper()}_REVISION') for n in _header.EXTENSION_NAMES):
+    _path = _header.extension_header(_name)
+    _h = _header.read(_path)
+    EXTENSIONS[_name] = Extension(_path, _h.functions, _h.params, _h.constants, f'hdy_{_name}_revision', _h.constants[_macro], _macro)
 
-OUTLINE_HEADER = os.path.join(os.path.dirname(_header.HEADER_PATH), 'hdyolo_outline.h')
-_O = _header.read(OUTLINE_HEADER)
-OUTLINE_SIGNATURES = _O.functions
-OUTLINE_PARAMS = _O.params
-OUTLINE_CONSTANTS = _O.constants
-OUTLINE_REVISION, OUTLINE_MAX_SIDE, OUTLINE_MAX_WINDOW = (OUTLINE_CONSTANTS['HDY_OUTLINE_' + n] for n in ('REVISION', 'MAX_SIDE', 'MAX_WINDOW'))
 
-GRAPH_HEADER = os.path.join(os.path.dirname(_header.HEADER_PATH), 'hdyolo_graph.h')
-_G = _header.read(GRAPH_HEADER)
-GRAPH_SIGNATURES = _G.functions
-GRAPH_PARAMS = _G.params
-GRAPH_CONSTANTS = _G.constants
-GRAPH_REVISION, GRAPH_MAX_K, GRAPH_MAX_RINGS = (GRAPH_CONSTANTS['HDY_GRAPH_' + n] for n in ('REVISION', 'MAX_K', 'MAX_RINGS'))
+def check_disjoint(extensions):
+    """raise HdyError when a function or a constant is declared twice among include/hdyolo.h and the headers of `extensions`"""
+    owner = dict.fromkeys((*_lib.SIGNATURES, *_lib.CONSTANTS), os.path.basename(_header.HEADER_PATH))
+    for ext in extensions.values():
+        for name in (*ext.functions, *ext.constants):
+            if name in owner:
+                raise HdyError(f'{name} is declared by include/{owner[name]} and by include/{os.path.basename(ext.header)}: a name belongs to one header')
+            owner[name] = os.path.basename(ext.header)
 
-# header file name -> (signatures, the function that returns the library's revision, the revision this binding is written for, its macro)
-_EXTENSIONS = {'hdyolo_measure.h': (SIGNATURES, 'hdy_measure_revision', MEASURE_REVISION, 'HDY_MEASURE_REVISION'),
-               'hdyolo_spatial.h': (SPATIAL_SIGNATURES, 'hdy_spatial_revision', SPATIAL_REVISION, 'HDY_SPATIAL_REVISION'),
-               'hdyolo_outline.h': (OUTLINE_SIGNATURES, 'hdy_outline_revision', OUTLINE_REVISION, 'HDY_OUTLINE_REVISION'),
-               'hdyolo_graph.h': (GRAPH_SIGNATURES, 'hdy_graph_revision', GRAPH_REVISION, 'HDY_GRAPH_REVISION')}
+
+check_disjoint(EXTENSIONS)
+SIGNATURES = {n: v for e in EXTENSIONS.values() for n, v in e.functions.items()}
+PARAMS = {n: v for e in EXTENSIONS.values() for n, v in e.params.items()}
+CONSTANTS = {n: v for e in EXTENSIONS.values() for n, v in e.constants.items()}
 
 _bound = None
 
@@ -57,17 +48,18 @@ def load():
     lib = _lib.load()
     if _bound is not lib:
         rebuild = 'rebuild with `python -m hd_yolo_amd.build --force`'
-        for header, (signatures, revision_fn, revision, macro) in _EXTENSIONS.items():
-            for name, (res, args) in signatures.items():
+        for ext in EXTENSIONS.values():
+            header = os.path.basename(ext.header)
+            for name, (res, args) in ext.functions.items():
                 fn = getattr(lib, name, None)
                 if fn is None:
                     raise HdyError(f'{_lib.LIB_PATH} does not export {name} (include/{header}): it was built before the extension header '
                                    f'existed; {rebuild}')
                 fn.restype, fn.argtypes = res, args
-            got = getattr(lib, revision_fn)()
-            if got != revision:
+            got = getattr(lib, ext.revision_fn)()
+            if got != ext.revision:
                 raise HdyError(f'{_lib.LIB_PATH} was built for revision {got} of include/{header}, this binding is written for '
-                               f'{revision} ({macro}): {rebuild}')
+                               f'{ext.revision} ({ext.revision_macro}): {rebuild}')
         _bound = lib
     return lib
 

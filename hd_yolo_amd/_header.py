@@ -16,6 +16,7 @@ import re
 from collections import namedtuple
 
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'hdyolo.h')
+EXTENSION_NAMES = ('measure', 'spatial', 'outline', 'graph')      # the extension headers, oldest first: _ext.py binds them, build.py watches them
 SCALARS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'long long': ctypes.c_longlong, 'unsigned long long': ctypes.c_ulonglong,
            'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double}
 POINTEES = set(SCALARS) | {'void', 'char', 'unsigned char', 'unsigned short', 'uint16_t'}       # what a pointer may point at, beside a structure
@@ -25,6 +26,11 @@ _INT = r'(0[xX][0-9a-fA-F]+|0|[1-9][0-9]*)(?:[uU]|[uU]?(?:ll|LL))?'
 
 class HdyError(RuntimeError):
     pass
+
+
+def extension_header(name):
+    """the path of the extension header of that short name, beside include/hdyolo.h"""
+    return os.path.join(os.path.dirname(HEADER_PATH), f'hdyolo_{name}.h')
 
 
 def _ctype(symbol, text, structs):

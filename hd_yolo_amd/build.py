@@ -7,6 +7,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from . import _header
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(CSRC, 'build')
@@ -22,8 +24,8 @@ def _newer(a, bs):
 
 def build(force=False, verbose=True):
     os.makedirs(OUT, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith('.h')]
-    headers += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('hdyolo.h', 'hdyolo_measure.h', 'hdyolo_spatial.h', 'hdyolo_outline.h', 'hdyolo_graph.h')]
+    headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith('.h')] + [_header.HEADER_PATH]
+    headers += [_header.extension_header(n) for n in _header.EXTENSION_NAMES]
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 
     def compile_one(src):

@@ -18,9 +18,8 @@
 // mutual_kernel: one lane per (p, s): k loads of the row of q = nbr_row[p][s].
 //
 // Contract: no allocation, everything on the passed stream, no host synchronisation; all argument checks before any launch.
-#include "common.h"
 #include "hdyolo_graph.h"
-#include "hdyolo_spatial.h"
+#include "spatial_common.h"
 
 namespace {
 
@@ -33,7 +32,8 @@ static_assert(MAXK * 12 * THREADS <= 64 * 1024, "the lists of a workgroup fit th
 struct KArgs {
     const i32x4* pts;
     const int* cell_start;
-    int N, k, cell, ncx, ncy, rings;
+    int N, k, rings;
+    Grid g;
     long long rmax, rmax2;
     int* nbr_row;
     long long* nbr_d2;
@@ -69,11 +69,10 @@ __device__ __forceinline__ void offer(List& l, u64 d2, int row) {
     }
 }
 
-// the candidates of the cells c0 .. c1 of grid row ry: one contiguous range of pts, clamped into [0, N] (safe on any cell_start)
+// the candidates of the cells c0 .. c1 of grid row ry: one contiguous range of pts
 __device__ __forceinline__ void scan(const KArgs& a, List& l, const i32x4& me, int self, int ry, int c0, int c1) {
-    const int s = max(a.cell_start[ry * a.ncx + c0], 0);
-    const int e = min(a.cell_start[ry * a.ncx + c1 + 1], a.N);
-    for (int j = s; j < e; ++j) {
+    const Run span = cell_run(a.cell_start, a.g, a.N, ry, c0, c1);
+    for (int j = span.s; j < span.e; ++j) {
         const i32x4 q = a.pts[j];
         if (j == self || q.x < 0 || q.y < 0 || q.z < 0) continue;                    // another point (identity), present, a node
         const long long dx = (long long)q.x - me.x, dy = (long long)q.y - me.y;
@@ -94,19 +93,19 @@ __global__ __launch_bounds__(THREADS) void knn_kernel(const KArgs a) {
     const bool row_ok = (unsigned)me.w < (unsigned)a.N;
     const size_t row = (size_t)(row_ok ? me.w : 0);
     if (me.x >= 0 && me.y >= 0) {
-        const int cx = min(me.x / a.cell, a.ncx - 1), cy = min(me.y / a.cell, a.ncy - 1);
+        const int cx = min(me.x / a.g.cell, a.g.ncx - 1), cy = min(me.y / a.g.cell, a.g.ncy - 1);
         for (int t = 0; t <= a.rings; ++t) {
-            const int x0 = max(cx - t, 0), x1 = min(cx + t, a.ncx - 1);
+            const int x0 = max(cx - t, 0), x1 = min(cx + t, a.g.ncx - 1);
             if (cy - t >= 0) scan(a, l, me, (int)i, cy - t, x0, x1);
-            if (t > 0 && cy + t <= a.ncy - 1) scan(a, l, me, (int)i, cy + t, x0, x1);
-            for (int ry = max(cy - t + 1, 0); ry <= min(cy + t - 1, a.ncy - 1); ++ry) {  // at most 2 * rings - 1 rows
+            if (t > 0 && cy + t <= a.g.ncy - 1) scan(a, l, me, (int)i, cy + t, x0, x1);
+            for (int ry = max(cy - t + 1, 0); ry <= min(cy + t - 1, a.g.ncy - 1); ++ry) {  // at most 2 * rings - 1 rows
                 if (cx - t >= 0) scan(a, l, me, (int)i, ry, cx - t, cx - t);
-                if (cx + t <= a.ncx - 1) scan(a, l, me, (int)i, ry, cx + t, cx + t);
+                if (cx + t <= a.g.ncx - 1) scan(a, l, me, (int)i, ry, cx + t, cx + t);
             }
-            const long long reach = (long long)t * a.cell;                               // every unvisited point is further than this
+            const long long reach = (long long)t * a.g.cell;                             // every unvisited point is further than this
             if (reach >= a.rmax) break;
             if (l.n == l.k && l.wd2 <= (u64)(reach * reach)) break;                      // reach < max_radius < 2^31: no overflow
-            if (cx - t <= 0 && cx + t >= a.ncx - 1 && cy - t <= 0 && cy + t >= a.ncy - 1) break;
+            if (cx - t <= 0 && cx + t >= a.g.ncx - 1 && cy - t <= 0 && cy + t >= a.g.ncy - 1) break;
         }
     }
     if (!row_ok) return;
@@ -138,19 +137,14 @@ int hdy_graph_knn(const int* pts, long long pts_elems, int N, const int* cell_st
                   int k, int max_radius, int* nbr_row, long long nbr_row_elems, long long* nbr_d2, long long nbr_d2_elems, int* nbr_count,
                   long long nbr_count_elems, void* stream) {
     const char* who = "graph_knn";
-    HDY_ARG(N >= 0 && pts_elems >= 0, "%s: negative count (N=%d, pts_elems=%lld)", who, N, pts_elems);
-    HDY_ARG(pts_elems == 4ll * N, "%s: pts_elems=%lld, the call reads 4 * N = 4 * %d", who, pts_elems, N);
-    HDY_ARG(N == 0 || pts, "%s: null pts pointer", who);
-    HDY_ARG(((uintptr_t)pts & 15) == 0, "%s: misaligned pts pointer (16 bytes)", who);
-    HDY_ARG(cell_units >= 1, "%s: cell_units=%d must be positive", who, cell_units);
-    HDY_ARG(ncx >= 1 && ncy >= 1 && (long long)ncx * ncy <= HDY_SPATIAL_MAX_CELLS, "%s: a grid of %d x %d cells (sides >= 1, at most %d cells)", who,
-            ncx, ncy, HDY_SPATIAL_MAX_CELLS);
+    HDY_CHECKED(check_pts(who, pts, pts_elems, N));
+    HDY_CHECKED(check_grid(who, cell_units, ncx, ncy));
     HDY_ARG(k >= 1 && k <= MAXK, "%s: k=%d outside [1, %d]", who, k, MAXK);
     HDY_ARG(max_radius >= 1, "%s: max_radius=%d must be positive", who, max_radius);
     const long long rings = ((long long)max_radius + cell_units - 1) / cell_units;
     HDY_ARG(rings <= MAXRINGS, "%s: max_radius=%d is %lld rings of cell_units=%d, at most %d", who, max_radius, rings, cell_units, MAXRINGS);
     const int ncells = ncx * ncy;
-    HDY_ARG(cell_start_elems == (long long)ncells + 1, "%s: cell_start_elems=%lld, the call reads ncx * ncy + 1 = %d", who, cell_start_elems, ncells + 1);
+    HDY_CHECKED(check_cell_start(who, cell_start_elems, ncells, "reads"));
     HDY_ARG(nbr_row_elems == (long long)N * k, "%s: nbr_row_elems=%lld, the call writes N * k = %d * %d", who, nbr_row_elems, N, k);
     HDY_ARG(nbr_d2_elems == (long long)N * k, "%s: nbr_d2_elems=%lld, the call writes N * k = %d * %d", who, nbr_d2_elems, N, k);
     HDY_ARG(nbr_count_elems == (long long)N, "%s: nbr_count_elems=%lld, the call writes N = %d", who, nbr_count_elems, N);
@@ -160,7 +154,7 @@ int hdy_graph_knn(const int* pts, long long pts_elems, int N, const int* cell_st
     if (N == 0) return HDY_OK;
     KArgs a = {};
     a.pts = (const i32x4*)pts; a.cell_start = cell_start; a.N = N; a.k = k;
-    a.cell = cell_units; a.ncx = ncx; a.ncy = ncy; a.rings = (int)rings;
+    a.g = {cell_units, ncx, ncy, ncells}; a.rings = (int)rings;
     a.rmax = max_radius; a.rmax2 = (long long)max_radius * max_radius;
     a.nbr_row = nbr_row; a.nbr_d2 = nbr_d2; a.nbr_count = nbr_count;
     hipLaunchKernelGGL(knn_kernel, dim3((unsigned)(((long long)N + THREADS - 1) / THREADS)), dim3(THREADS), (size_t)k * 12 * THREADS,

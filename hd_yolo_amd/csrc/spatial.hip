@@ -22,8 +22,7 @@
 // density_kernel: one lane per point, one integer atomicAdd into the field's class counter; the grid is zeroed by a pass of the same call.
 //
 // Contract: no allocation, everything on the passed stream, no host synchronisation; all argument checks before any launch.
-#include "common.h"
-#include "hdyolo_spatial.h"
+#include "spatial_common.h"
 
 namespace {
 
@@ -33,17 +32,6 @@ constexpr int THREADS = 256;
 constexpr int MAXC = HDY_SPATIAL_MAX_CLASSES, MAXK = HDY_SPATIAL_MAX_RADII;
 constexpr int LDS_BUDGET = 64 * 1024;
 static_assert((MAXK * MAXC + 3 * MAXC) * 128 * 4 <= LDS_BUDGET, "the slots of 128 lanes fit the static LDS budget at the limits");
-
-struct Grid {
-    int cell, ncx, ncy, ncells;
-};
-
-// the cell of a point, ncells for an absent one (which ranks behind every cell)
-__device__ __forceinline__ int cell_of(const i32x4& p, const Grid& g) {
-    if (p.x < 0 || p.y < 0) return g.ncells;
-    const int cx = min(p.x / g.cell, g.ncx - 1), cy = min(p.y / g.cell, g.ncy - 1);
-    return cy * g.ncx + cx;
-}
 
 __global__ __launch_bounds__(THREADS) void cells_kernel(const i32x4* __restrict__ pts, int N, Grid g, int* __restrict__ cell_start,
                                                         int* __restrict__ status) {
@@ -102,10 +90,8 @@ __global__ __launch_bounds__(THREADS) void neighbors_kernel(const NArgs a) {
     const int cx = min(me.x / a.g.cell, a.g.ncx - 1), cy = min(me.y / a.g.cell, a.g.ncy - 1);
     const int c0 = max(cx - 1, 0), c1 = min(cx + 1, a.g.ncx - 1);
     for (int ry = max(cy - 1, 0); ry <= min(cy + 1, a.g.ncy - 1); ++ry) {
-        // three consecutive cells of one grid row: one contiguous range of pts (clamped into [0, N]: safe on any cell_start)
-        const int s = max(a.cell_start[ry * a.g.ncx + c0], 0);
-        const int e = min(a.cell_start[ry * a.g.ncx + c1 + 1], a.N);
-        for (int j = s; j < e; ++j) {
+        const Run span = cell_run(a.cell_start, a.g, a.N, ry, c0, c1);     // three consecutive cells of one grid row
+        for (int j = span.s; j < span.e; ++j) {
             const i32x4 q = a.pts[j];
             const long long dx = (long long)q.x - me.x, dy = (long long)q.y - me.y;
             const long long d2 = dx * dx + dy * dy;
@@ -149,21 +135,6 @@ __global__ __launch_bounds__(THREADS) void density_kernel(const i32x4* __restric
     atomicAdd(&grid[((size_t)fy * gx + fx) * C + p.z], 1);
 }
 
-int check_pts(const char* who, const int* pts, long long pts_elems, int N) {
-    HDY_ARG(N >= 0 && pts_elems >= 0, "%s: negative count (N=%d, pts_elems=%lld)", who, N, pts_elems);
-    HDY_ARG(pts_elems == 4ll * N, "%s: pts_elems=%lld, the call reads 4 * N = 4 * %d", who, pts_elems, N);
-    HDY_ARG(N == 0 || pts, "%s: null pts pointer", who);
-    HDY_ARG(((uintptr_t)pts & 15) == 0, "%s: misaligned pts pointer (16 bytes)", who);
-    return HDY_OK;
-}
-
-int check_grid(const char* who, int cell_units, int ncx, int ncy) {
-    HDY_ARG(cell_units >= 1, "%s: cell_units=%d must be positive", who, cell_units);
-    HDY_ARG(ncx >= 1 && ncy >= 1 && (long long)ncx * ncy <= HDY_SPATIAL_MAX_CELLS, "%s: a grid of %d x %d cells (sides >= 1, at most %d cells)", who,
-            ncx, ncy, HDY_SPATIAL_MAX_CELLS);
-    return HDY_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -173,11 +144,10 @@ int hdy_spatial_revision(void) { return HDY_SPATIAL_REVISION; }
 int hdy_spatial_cells(const int* pts, long long pts_elems, int N, int cell_units, int ncx, int ncy, int* cell_start, long long cell_start_elems,
                       int* status, long long status_elems, void* stream) {
     const char* who = "spatial_cells";
-    int rc = check_pts(who, pts, pts_elems, N);
-    if (rc == HDY_OK) rc = check_grid(who, cell_units, ncx, ncy);
-    if (rc != HDY_OK) return rc;
+    HDY_CHECKED(check_pts(who, pts, pts_elems, N));
+    HDY_CHECKED(check_grid(who, cell_units, ncx, ncy));
     const int ncells = ncx * ncy;
-    HDY_ARG(cell_start_elems == (long long)ncells + 1, "%s: cell_start_elems=%lld, the call writes ncx * ncy + 1 = %d", who, cell_start_elems, ncells + 1);
+    HDY_CHECKED(check_cell_start(who, cell_start_elems, ncells, "writes"));
     HDY_ARG(status_elems == 1, "%s: status_elems=%lld, the call writes 1", who, status_elems);
     HDY_ARG(N == 0 || (cell_start && status), "%s: null cell_start or status pointer", who);
     HDY_ARG((((uintptr_t)cell_start | (uintptr_t)status) & 3) == 0, "%s: misaligned pointer (cell_start, status 4 bytes)", who);
@@ -200,9 +170,8 @@ int hdy_spatial_neighbors(const int* pts, long long pts_elems, int N, const int*
                           int ncy, const int* radii, int K, int C, int* counts, long long counts_elems, long long* near_d2, long long near_d2_elems,
                           int* near_row, long long near_row_elems, void* stream) {
     const char* who = "spatial_neighbors";
-    int rc = check_pts(who, pts, pts_elems, N);
-    if (rc == HDY_OK) rc = check_grid(who, cell_units, ncx, ncy);
-    if (rc != HDY_OK) return rc;
+    HDY_CHECKED(check_pts(who, pts, pts_elems, N));
+    HDY_CHECKED(check_grid(who, cell_units, ncx, ncy));
     HDY_ARG(C >= 1 && C <= MAXC, "%s: C=%d outside [1, %d]", who, C, MAXC);
     HDY_ARG(K >= 1 && K <= MAXK, "%s: K=%d outside [1, %d]", who, K, MAXK);
     HDY_ARG(radii, "%s: null radii pointer (a host array of K radii)", who);
@@ -211,7 +180,7 @@ int hdy_spatial_neighbors(const int* pts, long long pts_elems, int N, const int*
         HDY_ARG(radii[k] >= 1 && (k == 0 || radii[k] > radii[k - 1]), "%s: radii must increase strictly from 1 (radii[%d]=%d)", who, k, radii[k]);
     HDY_ARG(radii[K - 1] <= cell_units, "%s: the largest radius %d passes cell_units=%d", who, radii[K - 1], cell_units);
     const int ncells = ncx * ncy;
-    HDY_ARG(cell_start_elems == (long long)ncells + 1, "%s: cell_start_elems=%lld, the call reads ncx * ncy + 1 = %d", who, cell_start_elems, ncells + 1);
+    HDY_CHECKED(check_cell_start(who, cell_start_elems, ncells, "reads"));
     HDY_ARG(counts_elems == (long long)N * K * C, "%s: counts_elems=%lld, the call writes N * K * C = %d * %d * %d", who, counts_elems, N, K, C);
     HDY_ARG(near_d2_elems == (long long)N * C, "%s: near_d2_elems=%lld, the call writes N * C = %d * %d", who, near_d2_elems, N, C);
     HDY_ARG(near_row_elems == (long long)N * C, "%s: near_row_elems=%lld, the call writes N * C = %d * %d", who, near_row_elems, N, C);
@@ -236,8 +205,7 @@ int hdy_spatial_neighbors(const int* pts, long long pts_elems, int N, const int*
 int hdy_spatial_density(const int* pts, long long pts_elems, int N, int g_units, int gx, int gy, int C, int* grid, long long grid_elems,
                         void* stream) {
     const char* who = "spatial_density";
-    const int rc = check_pts(who, pts, pts_elems, N);
-    if (rc != HDY_OK) return rc;
+    HDY_CHECKED(check_pts(who, pts, pts_elems, N));
     HDY_ARG(C >= 1 && C <= MAXC, "%s: C=%d outside [1, %d]", who, C, MAXC);
     HDY_ARG(g_units >= 1, "%s: g_units=%d must be positive", who, g_units);
     HDY_ARG(gx >= 1 && gy >= 1 && (long long)gx * gy * C < (1ll << 31), "%s: a grid of %d x %d fields of %d classes (sides >= 1, fewer than 2^31 entries)",

@@ -42,8 +42,9 @@ def knn_graph(table_or_result, k, max_px, nc=None, size=None):
     extent = None if size is None else (int(size[1]) * UNITS, int(size[0]) * UNITS)
     if N == 0:
         from . import _ext
-        if not 1 <= k <= _ext.GRAPH_MAX_K:
-            raise ValueError(f'knn_graph: k={k} outside [1, {_ext.GRAPH_MAX_K}]')
+        max_k = _ext.CONSTANTS['HDY_GRAPH_MAX_K']
+        if not 1 <= k <= max_k:
+            raise ValueError(f'knn_graph: k={k} outside [1, {max_k}]')
         row = torch.zeros((0, k), dtype=torch.int32, device=xy.device)
         d2 = torch.zeros((0, k), dtype=torch.int64, device=xy.device)
         count = torch.zeros((0,), dtype=torch.int32, device=xy.device)

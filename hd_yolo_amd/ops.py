@@ -1193,6 +1193,17 @@ def label_areas(label_map, R):
 
 
 # ------------------------------------------------------------------------------------------ label measurement (csrc/measure.hip)
+def _label_rows(who, label_map, R):
+    """(the map contiguous, R) of a non-empty int32 (h, w) label map on the GPU and a row count"""
+    require_gpu(label_map)
+    if label_map.dtype != torch.int32 or label_map.dim() != 2 or label_map.numel() == 0:
+        raise _lib.HdyError(f'{who}: the map must be a non-empty int32 (h, w) tensor, got {label_map.dtype} {tuple(label_map.shape)}')
+    R = int(R)
+    if R < 0:
+        raise _lib.HdyError(f'{who}: negative row count R={R}')
+    return label_map.contiguous(), R
+
+
 def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
     """(sums, extent) of the R labels of an int32 (h, w) label map (hdy_label_measure, include/hdyolo_measure.h): sums int64 (R, 14) = n, sum dx,
     sum dy, sum dx^2, sum dy^2, sum dx dy, boundary edges, edges on the window border, sum R, G, B, sum R^2, G^2, B^2 with dx = j - ox, dy = i - oy;
@@ -1201,14 +1212,8 @@ def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
     None leaves the stain columns zero.  origin: int32 (R, 2) = (ox, oy) per label in map coordinates (None = zeros); hd_yolo_amd/measure.py
     (nucleus_table) turns the sums into the measurements."""
     from . import _ext
-    require_gpu(label_map)
-    if label_map.dtype != torch.int32 or label_map.dim() != 2 or label_map.numel() == 0:
-        raise _lib.HdyError(f'label_measure: the map must be a non-empty int32 (h, w) tensor, got {label_map.dtype} {tuple(label_map.shape)}')
-    lm = label_map.contiguous()
+    lm, R = _label_rows('label_measure', label_map, R)
     h, w = lm.shape
-    R = int(R)
-    if R < 0:
-        raise _lib.HdyError(f'label_measure: negative row count R={R}')
     x0, y0 = (int(v) for v in window)
     ip, nbytes, pitch, pb = None, 0, 0, 0
     if image is not None:
@@ -1223,7 +1228,7 @@ def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
         if origin.dtype != torch.int32 or tuple(origin.shape) != (R, 2) or origin.device != lm.device:
             raise _lib.HdyError(f'label_measure: origin must be an int32 ({R}, 2) tensor on {lm.device}, got {origin.dtype} {tuple(origin.shape)}')
         origin = origin.contiguous()
-    sums = torch.empty((R, _ext.MEASURE_COLS), dtype=torch.int64, device=lm.device)
+    sums = torch.empty((R, _ext.CONSTANTS['HDY_MEASURE_COLS']), dtype=torch.int64, device=lm.device)
     extent = torch.empty((R, 4), dtype=torch.int32, device=lm.device)
     if R:
         _ext.call('hdy_label_measure', lm.data_ptr(), lm.numel(), h, w, ip, nbytes, pitch, pb, x0, y0, ptr(origin), sums.data_ptr(), sums.numel(),
@@ -1233,17 +1238,12 @@ def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
 
 # ------------------------------------------------------------------------------------------ outlines and hulls (csrc/outline.hip)
 def _outline_inputs(who, label_map, R, extent):
-    require_gpu(label_map)
-    if label_map.dtype != torch.int32 or label_map.dim() != 2 or label_map.numel() == 0:
-        raise _lib.HdyError(f'{who}: the map must be a non-empty int32 (h, w) tensor, got {label_map.dtype} {tuple(label_map.shape)}')
-    R = int(R)
-    if R < 0:
-        raise _lib.HdyError(f'{who}: negative row count R={R}')
+    lm, R = _label_rows(who, label_map, R)
     require_gpu(extent)
-    if extent.dtype != torch.int32 or tuple(extent.shape) != (R, 4) or extent.device != label_map.device:
-        raise _lib.HdyError(f'{who}: extent must be an int32 ({R}, 4) tensor on {label_map.device} (ops.label_measure makes it), got '
+    if extent.dtype != torch.int32 or tuple(extent.shape) != (R, 4) or extent.device != lm.device:
+        raise _lib.HdyError(f'{who}: extent must be an int32 ({R}, 4) tensor on {lm.device} (ops.label_measure makes it), got '
                             f'{extent.dtype} {tuple(extent.shape)} on {extent.device}')
-    return label_map.contiguous(), R, extent.contiguous()
+    return lm, R, extent.contiguous()
 
 
 def label_outline(label_map, R, extent):
@@ -1313,14 +1313,25 @@ def _spatial_pts(xy, cls32, order=None):
     return (pts if order is None else pts[order]).contiguous()
 
 
+def _sorted_points(who, pts, cell_start=None):
+    """check points in cell order (contiguous int32 (N, 4) on the GPU) and, when given, their cell_start"""
+    require_gpu(pts)
+    if cell_start is not None:
+        require_gpu(cell_start)
+    if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_contiguous():
+        raise _lib.HdyError(f'{who}: pts must be a contiguous int32 (N, 4) tensor, got {pts.dtype} {tuple(pts.shape)}')
+    if cell_start is not None and (cell_start.dtype != torch.int32 or cell_start.dim() != 1 or not cell_start.is_contiguous()
+                                   or cell_start.device != pts.device):
+        raise _lib.HdyError(f'{who}: cell_start must be a contiguous int32 vector on {pts.device}, got {cell_start.dtype} '
+                            f'{tuple(cell_start.shape)}')
+
+
 def spatial_cells(pts, cell_units, ncx, ncy):
     """(cell_start int32 (ncx * ncy + 1,), status int32 (1,)) of points in cell order (hdy_spatial_cells, include/hdyolo_spatial.h): pts int32
     (N, 4) = (x, y, class, original row) sorted by cell, absent points last.  status is a device word, non-zero when pts is not in cell order;
     nothing is read back."""
     from . import _ext
-    require_gpu(pts)
-    if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_contiguous():
-        raise _lib.HdyError(f'spatial_cells: pts must be a contiguous int32 (N, 4) tensor, got {pts.dtype} {tuple(pts.shape)}')
+    _sorted_points('spatial_cells', pts)
     ncx, ncy = int(ncx), int(ncy)
     cell_start = torch.empty((max(ncx * ncy, 0) + 1,), dtype=torch.int32, device=pts.device)
     status = torch.empty((1,), dtype=torch.int32, device=pts.device)
@@ -1337,13 +1348,7 @@ def spatial_neighbors_sorted(pts, cell_start, cell_units, ncx, ncy, radii_units,
     """(counts int32 (N, K, C), near_d2 int64 (N, C), near_row int32 (N, C)) from points in cell order and their cell_start
     (hdy_spatial_neighbors): the second half of spatial_neighbors, rows of the outputs = the points' original rows."""
     from . import _ext
-    require_gpu(pts)
-    require_gpu(cell_start)
-    if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_contiguous():
-        raise _lib.HdyError(f'spatial_neighbors: pts must be a contiguous int32 (N, 4) tensor, got {pts.dtype} {tuple(pts.shape)}')
-    if cell_start.dtype != torch.int32 or cell_start.dim() != 1 or not cell_start.is_contiguous() or cell_start.device != pts.device:
-        raise _lib.HdyError(f'spatial_neighbors: cell_start must be a contiguous int32 vector on {pts.device}, got {cell_start.dtype} '
-                            f'{tuple(cell_start.shape)}')
+    _sorted_points('spatial_neighbors', pts, cell_start)
     radii = [int(r) for r in radii_units]
     N, K, C = pts.shape[0], len(radii), int(C)
     dev = pts.device
@@ -1358,6 +1363,28 @@ def spatial_neighbors_sorted(pts, cell_start, cell_units, ncx, ncy, radii_units,
 
 
 SPATIAL_GRID_SIDE = 4096        # spatial_neighbors: at most this many cells along a side, whatever the extent (score_slide's bound)
+
+
+def _cell_index(who, xy, cls32, N, cell_units, default_cell, extent_units, info):
+    """(pts, cell_start, cell, ncx, ncy), the leading arguments of the *_sorted calls: the first half of spatial_neighbors and spatial_knn, whose
+    docstrings state it.  default_cell(mx, my): the cell side when cell_units is None, from the largest coordinates the grid covers."""
+    present = (xy >= 0).all(1)
+    if extent_units is None:
+        mx, my = torch.where(present[:, None], xy, 0).amax(0).tolist() if N else (0, 0)
+    else:
+        mx, my = (max(int(v) - 1, 0) for v in extent_units)
+    cell = default_cell(mx, my) if cell_units is None else int(cell_units)
+    if cell < 1:
+        raise _lib.HdyError(f'{who}: cell_units={cell} must be positive')
+    ncx, ncy = mx // cell + 1, my // cell + 1
+    cx = torch.div(xy[:, 0], cell, rounding_mode='floor').clamp(max=ncx - 1)
+    cy = torch.div(xy[:, 1], cell, rounding_mode='floor').clamp(max=ncy - 1)
+    cid = torch.where(present, cy.to(torch.int64) * ncx + cx, ncx * ncy)          # absent points behind every cell
+    pts = _spatial_pts(xy, cls32, torch.sort(cid, stable=True)[1])
+    cell_start, status = spatial_cells(pts, cell, ncx, ncy)
+    if info is not None:
+        info.update(status=status, cell_units=cell, ncx=ncx, ncy=ncy, pts=pts, cell_start=cell_start)
+    return pts, cell_start, cell, ncx, ncy
 
 
 def spatial_neighbors(xy_units, cls, C, radii_units, cell_units=None, extent_units=None, info=None):
@@ -1375,23 +1402,8 @@ def spatial_neighbors(xy_units, cls, C, radii_units, cell_units=None, extent_uni
     radii = [int(r) for r in radii_units]
     if not radii:
         raise _lib.HdyError('spatial_neighbors: no radii')
-    present = (xy >= 0).all(1)
-    if extent_units is None:
-        mx, my = torch.where(present[:, None], xy, 0).amax(0).tolist() if N else (0, 0)
-    else:
-        mx, my = (max(int(v) - 1, 0) for v in extent_units)
-    cell = max(radii[-1], -(-(max(mx, my) + 1) // SPATIAL_GRID_SIDE), 1) if cell_units is None else int(cell_units)
-    if cell < 1:
-        raise _lib.HdyError(f'spatial_neighbors: cell_units={cell} must be positive')
-    ncx, ncy = mx // cell + 1, my // cell + 1
-    cx = torch.div(xy[:, 0], cell, rounding_mode='floor').clamp(max=ncx - 1)
-    cy = torch.div(xy[:, 1], cell, rounding_mode='floor').clamp(max=ncy - 1)
-    cid = torch.where(present, cy.to(torch.int64) * ncx + cx, ncx * ncy)          # absent points behind every cell
-    pts = _spatial_pts(xy, cls32, torch.sort(cid, stable=True)[1])
-    cell_start, status = spatial_cells(pts, cell, ncx, ncy)
-    if info is not None:
-        info.update(status=status, cell_units=cell, ncx=ncx, ncy=ncy, pts=pts, cell_start=cell_start)
-    return spatial_neighbors_sorted(pts, cell_start, cell, ncx, ncy, radii, C)
+    default_cell = (lambda mx, my: max(radii[-1], -(-(max(mx, my) + 1) // SPATIAL_GRID_SIDE), 1))
+    return spatial_neighbors_sorted(*_cell_index('spatial_neighbors', xy, cls32, N, cell_units, default_cell, extent_units, info), radii, C)
 
 
 def spatial_density(xy_units, cls, C, g_units, gx, gy):
@@ -1418,13 +1430,7 @@ def spatial_knn_sorted(pts, cell_start, cell_units, ncx, ncy, k, max_radius_unit
     """(nbr_row int32 (N, k), nbr_d2 int64 (N, k), nbr_count int32 (N,)) from points in cell order and their cell_start (hdy_graph_knn,
     include/hdyolo_graph.h): the second half of spatial_knn, rows of the outputs = the points' original rows."""
     from . import _ext
-    require_gpu(pts)
-    require_gpu(cell_start)
-    if pts.dtype != torch.int32 or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_contiguous():
-        raise _lib.HdyError(f'spatial_knn: pts must be a contiguous int32 (N, 4) tensor, got {pts.dtype} {tuple(pts.shape)}')
-    if cell_start.dtype != torch.int32 or cell_start.dim() != 1 or not cell_start.is_contiguous() or cell_start.device != pts.device:
-        raise _lib.HdyError(f'spatial_knn: cell_start must be a contiguous int32 vector on {pts.device}, got {cell_start.dtype} '
-                            f'{tuple(cell_start.shape)}')
+    _sorted_points('spatial_knn', pts, cell_start)
     N, k = pts.shape[0], int(k)
     dev = pts.device
     nbr_row = torch.empty((N, max(k, 0)), dtype=torch.int32, device=dev)
@@ -1443,7 +1449,7 @@ def knn_cell_units(N, k, max_radius_units, mx, my, fill=KNN_CELL_FILL):
     import math
     from . import _ext
     want = math.isqrt(int((mx + 1) * (my + 1) * fill * max(int(k), 1)) // max(int(N), 1))
-    return max(want, -(-int(max_radius_units) // _ext.GRAPH_MAX_RINGS), -(-(max(mx, my) + 1) // SPATIAL_GRID_SIDE), 1)
+    return max(want, -(-int(max_radius_units) // _ext.CONSTANTS['HDY_GRAPH_MAX_RINGS']), -(-(max(mx, my) + 1) // SPATIAL_GRID_SIDE), 1)
 
 
 def spatial_knn(xy_units, k, max_radius_units, cls=None, C=None, cell_units=None, extent_units=None, info=None):
@@ -1464,23 +1470,8 @@ def spatial_knn(xy_units, k, max_radius_units, cls=None, C=None, cell_units=None
         cls, C = torch.zeros((xy_units.shape[0] if xy_units.dim() else 0,), dtype=torch.int32, device=xy_units.device), 1
     xy, cls32, N, C = _spatial_inputs('spatial_knn', xy_units, cls, C)
     k, rmax = int(k), int(max_radius_units)
-    present = (xy >= 0).all(1)
-    if extent_units is None:
-        mx, my = torch.where(present[:, None], xy, 0).amax(0).tolist() if N else (0, 0)
-    else:
-        mx, my = (max(int(v) - 1, 0) for v in extent_units)
-    cell = knn_cell_units(N, k, rmax, mx, my) if cell_units is None else int(cell_units)
-    if cell < 1:
-        raise _lib.HdyError(f'spatial_knn: cell_units={cell} must be positive')
-    ncx, ncy = mx // cell + 1, my // cell + 1
-    cx = torch.div(xy[:, 0], cell, rounding_mode='floor').clamp(max=ncx - 1)
-    cy = torch.div(xy[:, 1], cell, rounding_mode='floor').clamp(max=ncy - 1)
-    cid = torch.where(present, cy.to(torch.int64) * ncx + cx, ncx * ncy)          # absent points behind every cell
-    pts = _spatial_pts(xy, cls32, torch.sort(cid, stable=True)[1])
-    cell_start, status = spatial_cells(pts, cell, ncx, ncy)
-    if info is not None:
-        info.update(status=status, cell_units=cell, ncx=ncx, ncy=ncy, pts=pts, cell_start=cell_start)
-    return spatial_knn_sorted(pts, cell_start, cell, ncx, ncy, k, rmax)
+    default_cell = (lambda mx, my: knn_cell_units(N, k, rmax, mx, my))
+    return spatial_knn_sorted(*_cell_index('spatial_knn', xy, cls32, N, cell_units, default_cell, extent_units, info), k, rmax)
 
 
 def knn_mutual(nbr_row):

@@ -196,6 +196,35 @@ def test_coordinates_beyond_the_extent_and_repeats():
         run(xy, cls, 4, 0)
 
 
+def test_spatial_neighbors_and_spatial_knn_build_one_cell_index():
+    """the same points, cell side and extent: the two calls sort the points into the same cells (ops._cell_index) and launch what they always did"""
+    xy, cls = ref.mixed(np.random.default_rng(23), 200, 256)
+    assert (xy < 0).any(1).sum() >= 3 and ((cls < 0) | (cls >= 3)).sum() >= 3                 # a few absent, a few out of class
+    txy, tcls = torch.from_numpy(xy).to(DEV), torch.from_numpy(cls).to(DEV)
+    grid = dict(cell_units=R, extent_units=(256 * ref.UNITS, 256 * ref.UNITS))
+    neigh, knn = {}, {}
+    _lib.dispatch_log(reset=True)
+    ops.spatial_neighbors(txy, tcls, 3, (R // 2, R), info=neigh, **grid)
+    got = ops.spatial_knn(txy, 4, R, cls=tcls, C=3, info=knn, **grid)
+    assert _lib.dispatch_log() == ['spatial_cells', 'spatial_neighbors', 'spatial_cells', 'graph_knn']
+    assert sorted(neigh) == sorted(knn) == ['cell_start', 'cell_units', 'ncx', 'ncy', 'pts', 'status']
+    assert torch.equal(neigh['pts'], knn['pts']) and torch.equal(neigh['cell_start'], knn['cell_start'])
+    assert (neigh['ncx'], neigh['ncy']) == (knn['ncx'], knn['ncy']) == (4, 4) and neigh['cell_units'] == knn['cell_units'] == R
+    assert tuple(knn['pts'].shape) == (200, 4) and tuple(knn['cell_start'].shape) == (17,) and int(knn['cell_start'][-1]) == int((xy >= 0).all(1).sum())
+    assert int(neigh['status']) == 0 and int(knn['status']) == 0
+    same([t.cpu().numpy() for t in got], ref.knn(xy, counted(cls), 4, R))
+    # no points: neither call raises or launches, and the index is the same empty one
+    none_xy, none_cls = txy[:0], tcls[:0]
+    neigh, knn = {}, {}
+    _lib.dispatch_log(reset=True)
+    a = ops.spatial_neighbors(none_xy, none_cls, 3, (R // 2, R), info=neigh, **grid)
+    b = ops.spatial_knn(none_xy, 4, R, cls=none_cls, C=3, info=knn, **grid)
+    assert _lib.dispatch_log() == []
+    assert [tuple(t.shape) for t in a] == [(0, 2, 3), (0, 3), (0, 3)] and [tuple(t.shape) for t in b] == [(0, 4), (0, 4), (0,)]
+    assert torch.equal(neigh['pts'], knn['pts']) and torch.equal(neigh['cell_start'], knn['cell_start']) and not knn['cell_start'].any()
+    assert (neigh['ncx'], neigh['ncy']) == (knn['ncx'], knn['ncy']) == (4, 4)
+
+
 def test_row_permutation():
     """permuting the rows permutes counts and distances; the rows map through the permutation wherever distances are distinct, and among equal
     distances the lowest NEW row comes first: the permuted call is checked against the restatement on the permuted rows"""

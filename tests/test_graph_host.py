@@ -139,7 +139,8 @@ def lib():
 def test_extension_header_parses_and_is_bound(lib):
     from hd_yolo_amd import _ext
     path = os.path.join(ROOT, 'include', 'hdyolo_graph.h')
-    assert _ext.GRAPH_HEADER == path
+    ext = _ext.EXTENSIONS['graph']
+    assert ext.header == path
     hdr = _header.read(path)
     assert sorted(hdr.functions) == ['hdy_graph_knn', 'hdy_graph_mutual', 'hdy_graph_revision']
     assert not hdr.structs
@@ -152,20 +153,56 @@ def test_extension_header_parses_and_is_bound(lib):
                                                            'max_radius', 'nbr_row', 'nbr_row_elems', 'nbr_d2', 'nbr_d2_elems', 'nbr_count',
                                                            'nbr_count_elems', 'stream']
     assert [p[0] for p in hdr.params['hdy_graph_mutual']] == ['nbr_row', 'nbr_row_elems', 'N', 'k', 'mutual', 'mutual_elems', 'stream']
-    earlier = (_lib.SIGNATURES, _ext.SIGNATURES, _ext.SPATIAL_SIGNATURES, _ext.OUTLINE_SIGNATURES)
     for name, (res, args) in hdr.functions.items():
         fn = getattr(lib, name)                                            # exported by the built library ...
         assert fn.restype is res and list(fn.argtypes) == args, name      # ... and bound by _ext
-        assert not any(name in table for table in earlier)
-    assert _ext.GRAPH_SIGNATURES == hdr.functions and _ext.GRAPH_PARAMS == hdr.params and _ext.GRAPH_CONSTANTS == hdr.constants
-    assert lib.hdy_graph_revision() == _ext.GRAPH_REVISION == 1 and _ext.GRAPH_MAX_K == 16 and _ext.GRAPH_MAX_RINGS == 16
-    assert not any(k.startswith('HDY_GRAPH') for k in list(_lib.CONSTANTS) + list(_ext.CONSTANTS) + list(_ext.SPATIAL_CONSTANTS)
-                   + list(_ext.OUTLINE_CONSTANTS))
-    assert 'graph.hip' in build.SOURCES and list(_ext._EXTENSIONS)[-1] == 'hdyolo_graph.h'
-    # the earlier extensions keep their tables
-    assert sorted(_ext.SIGNATURES) == ['hdy_label_measure', 'hdy_measure_revision'] and len(_ext.SPATIAL_SIGNATURES) == 4
-    assert sorted(_ext.OUTLINE_SIGNATURES) == ['hdy_label_hull', 'hdy_label_outline_count', 'hdy_label_outline_write', 'hdy_outline_revision']
-    assert _ext.SPATIAL_CONSTANTS['HDY_SPATIAL_REVISION'] == 1 and len(_ext.SPATIAL_CONSTANTS) == 6 and len(_ext.OUTLINE_CONSTANTS) == 3
+        assert name not in _lib.SIGNATURES                                 # the numbered ABI does not know the extension
+        assert _ext.SIGNATURES[name] == (res, args) and _ext.PARAMS[name] == hdr.params[name]
+    assert (ext.functions, ext.params, ext.constants) == (hdr.functions, hdr.params, hdr.constants)
+    assert (ext.revision_fn, ext.revision_macro) == ('hdy_graph_revision', 'HDY_GRAPH_REVISION')
+    assert lib.hdy_graph_revision() == ext.revision == 1
+    assert _ext.CONSTANTS['HDY_GRAPH_MAX_K'] == 16 and _ext.CONSTANTS['HDY_GRAPH_MAX_RINGS'] == 16
+    assert not any(k.startswith('HDY_GRAPH') for k in _lib.CONSTANTS)
+    assert 'graph.hip' in build.SOURCES and list(_ext.EXTENSIONS)[-1] == 'graph'
+
+
+def test_graph_knn_shares_the_point_and_grid_checks_of_spatial_neighbors(lib):
+    """hdy_graph_knn and hdy_spatial_neighbors answer a bad pts, grid or cell_start with one text, up to the name in front of it (the checks of
+    csrc/spatial_common.h), and in the same order when several arguments are bad"""
+    lib.hdy_dispatch_log_reset()
+    radii = (ctypes.c_int * 3)(10, 50, 100)
+    NEIGH = dict(pts=FAKE, pts_elems=40, N=10, cell_start=FAKE, cell_start_elems=13, cell_units=100, ncx=4, ncy=3, radii=radii, K=3, C=2, counts=FAKE,
+                 counts_elems=60, near_d2=FAKE, near_d2_elems=20, near_row=FAKE, near_row_elems=20)
+
+    def texts(**kw):
+        rc, knn = _knn(lib, **kw)
+        assert rc == _lib.EINVAL, kw
+        a = dict(NEIGH)
+        a.update(kw)
+        assert lib.hdy_spatial_neighbors(*(a[n] for n in NEIGH), None) == _lib.EINVAL, kw
+        neigh = lib.hdy_last_error()
+        assert knn.startswith(b'graph_knn: ') and neigh.startswith(b'spatial_neighbors: '), (knn, neigh)
+        return knn[len(b'graph_knn: '):], neigh[len(b'spatial_neighbors: '):]
+
+    cases = [({'pts': None}, b'null pts pointer'), ({'pts': FAKE + 4}, b'misaligned pts pointer (16 bytes)'),
+             ({'pts': FAKE + 8}, b'misaligned pts pointer (16 bytes)'),
+             ({'N': -1}, b'negative count (N=-1, pts_elems=40)'), ({'pts_elems': -40}, b'negative count (N=10, pts_elems=-40)'),
+             ({'pts_elems': 39}, b'pts_elems=39, the call reads 4 * N = 4 * 10'), ({'pts_elems': 44}, b'pts_elems=44, the call reads 4 * N = 4 * 10'),
+             ({'cell_units': 0}, b'cell_units=0 must be positive'), ({'cell_units': -3}, b'cell_units=-3 must be positive'),
+             ({'ncx': 0}, b'a grid of 0 x 3 cells (sides >= 1, at most 16777216 cells)'),
+             ({'ncy': -1}, b'a grid of 4 x -1 cells (sides >= 1, at most 16777216 cells)'),
+             ({'ncx': 4097, 'ncy': 4096}, b'a grid of 4097 x 4096 cells (sides >= 1, at most 16777216 cells)'),
+             ({'cell_start_elems': 12}, b'cell_start_elems=12, the call reads ncx * ncy + 1 = 13'),
+             ({'cell_start_elems': 14}, b'cell_start_elems=14, the call reads ncx * ncy + 1 = 13'),
+             ({'cell_start_elems': -1}, b'cell_start_elems=-1, the call reads ncx * ncy + 1 = 13'),
+             # several bad arguments: pts before the grid, cell_units before the sides, the grid before cell_start
+             ({'pts': None, 'cell_units': 0}, b'null pts pointer'), ({'pts_elems': 39, 'ncx': 0}, b'pts_elems=39, the call reads 4 * N = 4 * 10'),
+             ({'N': -1, 'pts': FAKE + 4}, b'negative count (N=-1, pts_elems=40)'), ({'cell_units': 0, 'ncx': 0}, b'cell_units=0 must be positive'),
+             ({'ncy': 0, 'cell_start_elems': 5}, b'a grid of 4 x 0 cells (sides >= 1, at most 16777216 cells)')]
+    for kw, want in cases:
+        knn, neigh = texts(**kw)
+        assert knn == neigh == want, (kw, knn, neigh)
+    assert _lib.dispatch_log() == []
 
 
 KNN = dict(pts=FAKE, pts_elems=40, N=10, cell_start=FAKE, cell_start_elems=13, cell_units=100, ncx=4, ncy=3, k=4, max_radius=300, nbr_row=FAKE,

@@ -2,6 +2,7 @@
 (tests/measure_ref.py) against each other and against answers derived by hand, nucleus_table on CPU tensors against the numpy restatement of its
 formulas, the extension header and its binding, the ABI surface of hdy_label_measure (invalid calls answered by status and message before
 anything is dereferenced or launched) and the two file formats of save_nucleus_table."""
+import ctypes
 import math
 import os
 
@@ -143,9 +144,9 @@ def lib():
 
 def test_extension_header_parses_and_is_bound(lib):
     from hd_yolo_amd import _ext
-    import ctypes
     path = os.path.join(ROOT, 'include', 'hdyolo_measure.h')
-    assert _ext.MEASURE_HEADER == path
+    ext = _ext.EXTENSIONS['measure']
+    assert ext.header == path
     hdr = _header.read(path)
     assert sorted(hdr.functions) == ['hdy_label_measure', 'hdy_measure_revision'] and not hdr.structs
     assert hdr.constants == {'HDY_MEASURE_REVISION': 1, 'HDY_MEASURE_COLS': 14, 'HDY_MEASURE_MAX_SIDE': 1 << 29}
@@ -157,9 +158,51 @@ def test_extension_header_parses_and_is_bound(lib):
         fn = getattr(lib, name)                                            # exported by the built library ...
         assert fn.restype is res and list(fn.argtypes) == args, name      # ... and bound by _ext
         assert name not in _lib.SIGNATURES                                 # the numbered ABI does not know the extension
-    assert lib.hdy_measure_revision() == _ext.MEASURE_REVISION == hdr.constants['HDY_MEASURE_REVISION']
+        assert _ext.SIGNATURES[name] == (res, args) and _ext.PARAMS[name] == hdr.params[name]
+    assert (ext.functions, ext.params, ext.constants) == (hdr.functions, hdr.params, hdr.constants)
+    assert (ext.revision_fn, ext.revision_macro) == ('hdy_measure_revision', 'HDY_MEASURE_REVISION')
+    assert lib.hdy_measure_revision() == ext.revision == hdr.constants['HDY_MEASURE_REVISION'] == 1
     assert not any(k.startswith('HDY_MEASURE') for k in _lib.CONSTANTS)
-    assert _ext.MEASURE_COLS == hmeasure.COLS == ref.COLS
+    assert _ext.CONSTANTS['HDY_MEASURE_COLS'] == hmeasure.COLS == ref.COLS == 14
+
+
+def test_every_extension_keeps_its_tables_and_a_name_belongs_to_one_header(lib):
+    """the tables of every extension header side by side: what each declares, that no name is declared twice (among them or with
+    include/hdyolo.h), and that the import refuses a header which breaks that"""
+    from hd_yolo_amd import _ext
+    want = {'measure': (['hdy_label_measure', 'hdy_measure_revision'], 3),
+            'spatial': (['hdy_spatial_cells', 'hdy_spatial_density', 'hdy_spatial_neighbors', 'hdy_spatial_revision'], 6),
+            'outline': (['hdy_label_hull', 'hdy_label_outline_count', 'hdy_label_outline_write', 'hdy_outline_revision'], 3),
+            'graph': (['hdy_graph_knn', 'hdy_graph_mutual', 'hdy_graph_revision'], 3)}
+    assert list(_ext.EXTENSIONS) == list(want) == list(_header.EXTENSION_NAMES)                 # oldest first, graph last
+    for short, (functions, n_constants) in want.items():
+        ext = _ext.EXTENSIONS[short]
+        assert sorted(ext.functions) == functions and sorted(ext.params) == functions and len(ext.constants) == n_constants
+        assert ext.header == os.path.join(ROOT, 'include', f'hdyolo_{short}.h') == _header.extension_header(short)
+        assert (ext.revision_fn, ext.revision_macro) == (f'hdy_{short}_revision', f'HDY_{short.upper()}_REVISION')
+        assert ext.revision == ext.constants[ext.revision_macro] == getattr(lib, ext.revision_fn)() == 1
+        assert all(k.startswith(f'HDY_{short.upper()}_') for k in ext.constants)
+        for table, base in (('functions', _lib.SIGNATURES), ('constants', _lib.CONSTANTS)):
+            for name in getattr(ext, table):
+                assert name not in base and [s for s, e in _ext.EXTENSIONS.items() if name in getattr(e, table)] == [short], name
+    exts = list(_ext.EXTENSIONS.values())
+    assert _ext.SIGNATURES == {n: v for e in exts for n, v in e.functions.items()} and len(_ext.SIGNATURES) == 2 + 4 + 4 + 3
+    assert _ext.PARAMS == {n: v for e in exts for n, v in e.params.items()} and sorted(_ext.PARAMS) == sorted(_ext.SIGNATURES)
+    assert _ext.CONSTANTS == {n: v for e in exts for n, v in e.constants.items()} and len(_ext.CONSTANTS) == 3 + 6 + 3 + 3
+    _ext.check_disjoint(_ext.EXTENSIONS)                                                         # the tables as they are pass
+    graph = _ext.EXTENSIONS['graph']
+    for doctored, word in ((graph._replace(functions=dict(graph.functions, hdy_spatial_cells=graph.functions['hdy_graph_mutual'])),
+                            'hdy_spatial_cells is declared by include/hdyolo_spatial.h and by include/hdyolo_graph.h'),
+                           (graph._replace(constants=dict(graph.constants, HDY_MEASURE_COLS=14)),
+                            'HDY_MEASURE_COLS is declared by include/hdyolo_measure.h and by include/hdyolo_graph.h'),
+                           (graph._replace(functions=dict(graph.functions, hdy_last_error=(ctypes.c_char_p, []))),
+                            'hdy_last_error is declared by include/hdyolo.h and by include/hdyolo_graph.h'),
+                           (graph._replace(constants=dict(graph.constants, HDY_ABI_VERSION=1)),
+                            'HDY_ABI_VERSION is declared by include/hdyolo.h and by include/hdyolo_graph.h')):
+        with pytest.raises(_lib.HdyError) as e:
+            _ext.check_disjoint(dict(_ext.EXTENSIONS, graph=doctored))
+        assert word in str(e.value)
+    assert 'hdy_spatial_cells' not in graph.functions and 'HDY_MEASURE_COLS' not in graph.constants      # the copies were doctored, not the tables
 
 
 def _call(lib, **kw):

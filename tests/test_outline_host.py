@@ -185,7 +185,8 @@ def lib():
 def test_extension_header_parses_and_is_bound(lib):
     from hd_yolo_amd import _ext
     path = os.path.join(ROOT, 'include', 'hdyolo_outline.h')
-    assert _ext.OUTLINE_HEADER == path
+    ext = _ext.EXTENSIONS['outline']
+    assert ext.header == path
     hdr = _header.read(path)
     assert sorted(hdr.functions) == ['hdy_label_hull', 'hdy_label_outline_count', 'hdy_label_outline_write', 'hdy_outline_revision']
     assert not hdr.structs
@@ -200,12 +201,12 @@ def test_extension_header_parses_and_is_bound(lib):
     for name, (res, args) in hdr.functions.items():
         fn = getattr(lib, name)                                            # exported by the built library ...
         assert fn.restype is res and list(fn.argtypes) == args, name      # ... and bound by _ext
-        assert name not in _lib.SIGNATURES and name not in _ext.SIGNATURES and name not in _ext.SPATIAL_SIGNATURES
-    assert _ext.OUTLINE_SIGNATURES == hdr.functions and _ext.OUTLINE_PARAMS == hdr.params and _ext.OUTLINE_CONSTANTS == hdr.constants
-    assert lib.hdy_outline_revision() == _ext.OUTLINE_REVISION == 1 and _ext.OUTLINE_MAX_SIDE == ref.MAX_SIDE == 1024
-    assert not any(k.startswith('HDY_OUTLINE') for k in list(_lib.CONSTANTS) + list(_ext.CONSTANTS) + list(_ext.SPATIAL_CONSTANTS))
-    # the earlier extensions keep their tables
-    assert sorted(_ext.SIGNATURES) == ['hdy_label_measure', 'hdy_measure_revision'] and len(_ext.SPATIAL_SIGNATURES) == 4
+        assert name not in _lib.SIGNATURES                                 # the numbered ABI does not know the extension
+        assert _ext.SIGNATURES[name] == (res, args) and _ext.PARAMS[name] == hdr.params[name]
+    assert (ext.functions, ext.params, ext.constants) == (hdr.functions, hdr.params, hdr.constants)
+    assert (ext.revision_fn, ext.revision_macro) == ('hdy_outline_revision', 'HDY_OUTLINE_REVISION')
+    assert lib.hdy_outline_revision() == ext.revision == 1 and _ext.CONSTANTS['HDY_OUTLINE_MAX_SIDE'] == ref.MAX_SIDE == 1024
+    assert not any(k.startswith('HDY_OUTLINE') for k in _lib.CONSTANTS)
 
 
 COMMON = dict(map=FAKE, map_elems=20 * 30, h=20, w=30, extent=FAKE, extent_elems=4 * 5, R=5)

@@ -145,7 +145,8 @@ def lib():
 def test_extension_header_parses_and_is_bound(lib):
     from hd_yolo_amd import _ext
     path = os.path.join(ROOT, 'include', 'hdyolo_spatial.h')
-    assert _ext.SPATIAL_HEADER == path
+    ext = _ext.EXTENSIONS['spatial']
+    assert ext.header == path
     hdr = _header.read(path)
     assert sorted(hdr.functions) == ['hdy_spatial_cells', 'hdy_spatial_density', 'hdy_spatial_neighbors', 'hdy_spatial_revision'] and not hdr.structs
     assert hdr.constants == {'HDY_SPATIAL_REVISION': 1, 'HDY_SPATIAL_SUBPIXEL': 16, 'HDY_SPATIAL_MAX_CLASSES': 16, 'HDY_SPATIAL_MAX_RADII': 4,
@@ -158,13 +159,14 @@ def test_extension_header_parses_and_is_bound(lib):
     for name, (res, args) in hdr.functions.items():
         fn = getattr(lib, name)                                            # exported by the built library ...
         assert fn.restype is res and list(fn.argtypes) == args, name      # ... and bound by _ext
-        assert name not in _lib.SIGNATURES and name not in _ext.SIGNATURES          # neither the numbered ABI nor the first extension knows it
-    assert _ext.SPATIAL_SIGNATURES == hdr.functions and _ext.SPATIAL_PARAMS == hdr.params and _ext.SPATIAL_CONSTANTS == hdr.constants
-    assert lib.hdy_spatial_revision() == _ext.SPATIAL_REVISION == 1
-    assert _ext.SPATIAL_SUBPIXEL == spatial.UNITS and (_ext.SPATIAL_MAX_CLASSES, _ext.SPATIAL_MAX_RADII) == (16, 4)
-    assert not any(k.startswith('HDY_SPATIAL') for k in _lib.CONSTANTS) and not any(k.startswith('HDY_SPATIAL') for k in _ext.CONSTANTS)
-    # the first extension keeps its tables and its meaning
-    assert sorted(_ext.SIGNATURES) == ['hdy_label_measure', 'hdy_measure_revision'] and _ext.MEASURE_COLS == 14 and lib.hdy_measure_revision() == 1
+        assert name not in _lib.SIGNATURES                                 # the numbered ABI does not know the extension
+        assert _ext.SIGNATURES[name] == (res, args) and _ext.PARAMS[name] == hdr.params[name]
+    assert (ext.functions, ext.params, ext.constants) == (hdr.functions, hdr.params, hdr.constants)
+    assert (ext.revision_fn, ext.revision_macro) == ('hdy_spatial_revision', 'HDY_SPATIAL_REVISION')
+    assert lib.hdy_spatial_revision() == ext.revision == 1
+    c = _ext.CONSTANTS
+    assert c['HDY_SPATIAL_SUBPIXEL'] == spatial.UNITS and (c['HDY_SPATIAL_MAX_CLASSES'], c['HDY_SPATIAL_MAX_RADII']) == (16, 4)
+    assert not any(k.startswith('HDY_SPATIAL') for k in _lib.CONSTANTS)
 
 
 def _radii(*r):
