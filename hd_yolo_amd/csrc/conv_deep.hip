@@ -678,6 +678,11 @@ bool hdy_conv_deep_plan(const ConvShape& s, ConvPlan* p) {
     if (hdy_opt(HDY_OPT_NO_DEEP) || s.dtype != HDY_BF16 || s.stem || (!s.dense && !walk)) return false;
     if (!conv_is(s, 1, 1, 0) && !hdy_opt(HDY_OPT_DEEP_ALL)) return false;
     if (s.C % 64 != 0 || s.K < 128 || s.K % 8 != 0) return false;
+    // the loader's row offsets are unsigned, from the window origin of a tile's first row, with the tap as the descriptor's scalar offset: an
+    // output row more than one pixel wider (or an output taller) than what it reads puts a later row's origin before the first one's, and its
+    // taps would all be dropped by the range check (conv_dispatch.hip hdy_conv_launch, `ascending`; the generic kernel's per-lane form serves these)
+    const int mul = walk ? 1 : s.stride;
+    if ((long long)(s.Wo - 1) * mul > s.W || (long long)(s.Ho - 1) * mul >= s.H) return false;
     // measured at the yolov5s bench shapes (B = 64, scripts/probes/dgrad_walk.py): 105 / 80 / 62 / 48 us here against 94 / 86 / 59 / 51 us for
     // conv_igemm.hip's 128-row walk, and 12.37-12.45 against 12.30 ms in the train step.  Opt-in.
     // HDY_DEEP_WALK: 0 never, 1 always, 2 (default) where it measured faster: 256 or more gradient channels out (256<-512 @40x40 80.5 vs 85.9 us, 256<-256 47.5 vs 51.1)

@@ -95,7 +95,12 @@ static int hdy_conv_launch(ConvArgs a, const ConvShape& s, int out_f32, hipStrea
     a.UH = uh1 - a.uh0; a.UW = uw1 - a.uw0;
     HDY_ARG(a.UH * a.UW <= 31, "conv: %d x %d tap window beyond the loader's 31 tap bits", a.UH, a.UW);
     HDY_ARG(((long long)(a.UH + 1) * a.Win + a.UW) * a.ldx * (dtype == HDY_BF16 ? 2 : 4) < (1LL << 28), "conv: tap window spans too many bytes");
-    a.utap = a.C % BKE == 0 ? 1 : 0;
+    // The loader's per-row offsets are unsigned, from the window origin of the tile's FIRST row.  Where an output row is more than one pixel
+    // wider than what it reads (pad > S / 2, or the data gradient of a layer padded by less than (S - 1) / 2), or likewise taller, a later
+    // row's origin lies BEFORE the first one's.  The per-lane form adds the tap to the offset in 32 bits, which wraps back into range; the
+    // whole-tap form hands the tap to the descriptor as a scalar offset, and the range check then drops every tap of such a row (zeros).
+    const bool ascending = (long long)(a.Wo - 1) * a.iw_mul <= a.Win && (long long)(a.Ho - 1) * a.ih_mul < a.Hin;
+    a.utap = (a.C % BKE == 0 && ascending) ? 1 : 0;
     hdy_magic((unsigned)(a.Ho * a.Wo), &a.mg_howo, &a.sh_howo);
     hdy_magic((unsigned)a.Wo, &a.mg_wo, &a.sh_wo);
     hdy_magic((unsigned)a.C, &a.mg_c, &a.sh_c);
@@ -152,6 +157,11 @@ static int dgrad_impl(const void* dy, int lddy, const void* w_packed_dgrad, void
         a.Kdp = round_up(R * S * K, bke(dtype));
         return hdy_conv_launch(a, dgrad_shape(N, H, W, C, K, R, S, stride, pad, dtype), 0, (hipStream_t)stream);
     }
+    // checked for both axes before anything starts: found inside the loop of launches below, the classes before the empty one had already
+    // written their pixels of dx when the call failed
+    for (int ca = 0; ca < 2; ++ca)
+        HDY_ARG(class_axis(R, pad, ca).taps && class_axis(S, pad, ca).taps,
+                "conv_dgrad: kernel %dx%d pad %d leaves a parity class without taps (unsupported)", R, S, pad);
     const int rows_total = round_up(C, hdy_conv_bn_tile(C));
     size_t off = 0;
     // One launch walking the four parity classes per spatial tile (conv_igemm.hip, `walk`): every class has the same Ho x Wo when H and W
@@ -182,9 +192,6 @@ static int dgrad_impl(const void* dy, int lddy, const void* w_packed_dgrad, void
             ConvArgs c = a;
             c.Ho = (H - ca + 1) / 2; c.Wo = (W - cb + 1) / 2;
             c.oh_mul = c.ow_mul = 2; c.oh_off = ca; c.ow_off = cb; c.dense_out = 0;
-            if (!ah.taps || !aw.taps) {
-                HDY_ARG(false, "conv_dgrad: kernel %dx%d pad %d leaves a parity class without taps (unsupported)", R, S, pad);
-            }
             if (c.Ho <= 0 || c.Wo <= 0) continue;
             c.dh0 = ah.d0; c.dw0 = aw.d0; c.TH = ah.taps; c.TW = aw.taps;
             c.Kdp = round_up(ah.taps * aw.taps * K, bke(dtype));

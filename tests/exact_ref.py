@@ -5,10 +5,10 @@ the fp32 MFMA path and in a bf16 output up to |v| <= 256 — so the result does 
 tile order or the kernel family, and the test of a kernel becomes equality with a float64 convolution on the CPU.  One wrong, missing or
 doubled product term anywhere in the tensor fails it, and so does one pixel too many or too few in a BatchNorm statistics slab.
 
-Operands of a case (N, H, W, C, K, R, stride, pad), all from seeded generators:
+Operands of a case (N, H, W, C, K, R, stride, pad) — or, with a rectangular window, (N, H, W, C, K, R, S, stride, pad) — all from seeded generators:
 
     x        integers in [-2, 2]                     dy       integers in [-1, 1]
-    w        +-1 with probability pw, else 0:        pw = min(1, V / (2 T)),  T = max(C, K) R R,  V = min(300, 8e6 / M),  M = N Ho Wo
+    w        +-1 with probability pw, else 0:        pw = min(1, V / (2 T)),  T = max(C, K) R S,  V = min(300, 8e6 / M),  M = N Ho Wo
     scale    cycles through 0.5, 1, 2, -1            shift    integers in [-8, 8]
     res, acc integers in [-4, 4]  (the residual operand and what an accumulating call finds in its output)
     stem     (6x6 / stride 2 / pad 2 over 3 channels) image values are integers in [0, 2] and T = 108
@@ -44,10 +44,18 @@ def ints(shape, lo, hi, seed):
     return torch.randint(lo, hi + 1, shape, generator=g).double()
 
 
-def weight_density(case, stem=False):
+def window(case):
+    """(N, H, W, C, K, R, S, stride, pad) of a case given with a square window (8 numbers) or a rectangular one (9)"""
+    if len(case) == 9:
+        return tuple(case)
     N, H, W, C, K, R, stride, pad = case
-    M = N * out_dim(H, R, stride, pad) * out_dim(W, R, stride, pad)
-    T = 108 if stem else max(C, K) * R * R
+    return (N, H, W, C, K, R, R, stride, pad)
+
+
+def weight_density(case, stem=False):
+    N, H, W, C, K, R, S, stride, pad = window(case)
+    M = N * out_dim(H, R, stride, pad) * out_dim(W, S, stride, pad)
+    T = 108 if stem else max(C, K) * R * S
     V = min(300.0, 8.0e6 / M)
     return min(1.0, V / (2.0 * T))
 
@@ -64,15 +72,15 @@ class Exact:
 def reference(case, stem=False):
     """Operands and everything the legs compare against, computed once per case (the cache holds the last two cases: tests that share a
     case run back to back).  Nothing in it may be modified by a test."""
-    N, H, W, C, K, R, stride, pad = case
-    Ho, Wo = out_dim(H, R, stride, pad), out_dim(W, R, stride, pad)
+    N, H, W, C, K, R, S, stride, pad = window(case)
+    Ho, Wo = out_dim(H, R, stride, pad), out_dim(W, S, stride, pad)
     e = Exact()
     e.case, e.stem, e.Ho, e.Wo, e.M = case, stem, Ho, Wo, N * Ho * Wo
     e.pw = weight_density(case, stem)
     e.x = ints((N, C, H, W), 0, 2, 1) if stem else ints((N, C, H, W), -2, 2, 1)
     g = torch.Generator().manual_seed(2)
-    keep = (torch.rand((K, C, R, R), generator=g) < e.pw).double()
-    e.w = (ints((K, C, R, R), 0, 1, 3) * 2 - 1) * keep
+    keep = (torch.rand((K, C, R, S), generator=g) < e.pw).double()
+    e.w = (ints((K, C, R, S), 0, 1, 3) * 2 - 1) * keep
     e.dy = ints((N, K, Ho, Wo), -1, 1, 5)
     e.scale = torch.tensor([SCALES[k % 4] for k in range(K)], dtype=torch.float64)
     e.shift = ints((K,), -8, 8, 6)
@@ -175,10 +183,80 @@ def case_lists():
     return tk.CONV_CASES, tk.DEEP_CASES, tk.WGRAD_DEEP_CASES, tk.RES_CASES, stem, patch
 
 
+def round_up(n, m):
+    return (n + m - 1) // m * m
+
+
+def in_slice(ref_nhwc, pitch, off, poison):
+    """float64 [N][H][W][pitch]: `ref_nhwc` in lanes off .. off + K of a buffer whose other lanes hold `poison` — what a whole pitched buffer
+    must equal after a call that writes the channel slice only, so that one `assert_exact` covers the values and the guard lanes"""
+    full = torch.full(tuple(ref_nhwc.shape[:3]) + (pitch,), float(poison), dtype=torch.float64)
+    full[..., off:off + ref_nhwc.shape[3]] = ref_nhwc
+    return full
+
+
+def uncovered(case):
+    """(first row, first column) of x that lies under no window of the case (H, W where every row / column is covered)"""
+    N, H, W, C, K, R, S, stride, pad = window(case)
+    return (min(H, (out_dim(H, R, stride, pad) - 1) * stride + R - pad), min(W, (out_dim(W, S, stride, pad) - 1) * stride + S - pad))
+
+
+# ---- the call forms outside the backbone's and neck's layer table (tests/test_gpu_exact_forms.py), all (N, H, W, C, K, R, S, stride, pad)
+# ragged K, written as a channel slice: detection logits (K = na * no), mask logits, segmentation logits; their backward pads K with zeros
+RAGGED_CASES = [
+    (2, 28, 28, 256, 3, 1, 1, 1, 0),
+    (2, 12, 12, 64, 1, 1, 1, 1, 0),
+    (2, 20, 20, 128, 27, 1, 1, 1, 0),
+    (1, 8, 8, 64, 255, 1, 1, 1, 0),
+    (1, 9, 11, 32, 18, 3, 3, 1, 1),
+]
+# 2x2 / stride 2 / pad 0: the mask head's ConvTranspose2d (its data gradient), that layer's backward (its forward) and its weight gradient
+DECONV_CASES = [
+    (2, 28, 28, 256, 256, 2, 2, 2, 0),       # the head's own
+    (1, 10, 6, 16, 24, 2, 2, 2, 0),
+    (2, 12, 20, 64, 32, 2, 2, 2, 0),
+    (1, 11, 7, 16, 24, 2, 2, 2, 0),          # odd sides: the last row and the last column of x lie under no window
+]
+WINDOW_CASES = [
+    (1, 12, 12, 16, 16, 5, 5, 1, 2),
+    (2, 16, 16, 16, 32, 5, 5, 2, 2),         # parity classes of 3 and 2 taps per axis
+    (2, 10, 12, 32, 32, 3, 3, 1, 0),
+    (2, 12, 12, 32, 32, 3, 3, 2, 0),         # an uncovered last row and column, even sides
+    (1, 13, 11, 32, 32, 3, 3, 2, 0),         # odd sides, stride 2, no padding
+    (1, 8, 8, 16, 16, 3, 3, 1, 2),           # pad > R // 2: the output is larger than the input, pad' = 0 in the data gradient
+    # an output row wider than the input row + 1: from a tile that begins in the last column (m = 384 = image 3, row 4, column 10 of 11) the
+    # window origin of the next output row lies BEFORE the tile's — a negative offset in the generic loader, whose k-blocks are whole taps
+    # here (C = 64); forward for the first, data gradient (dy is the narrow tensor, K = 64 its channels) for the second
+    (4, 8, 9, 64, 16, 3, 3, 1, 2),
+    (4, 10, 11, 16, 64, 3, 3, 1, 0),
+    (2, 9, 12, 32, 24, 1, 3, 1, 0),          # R != S
+    (2, 12, 9, 24, 32, 3, 1, 1, 1),
+    (1, 11, 13, 24, 40, 5, 3, 1, 1),
+    (2, 12, 12, 32, 32, 4, 4, 2, 1),         # two taps in every parity class
+    (2, 14, 14, 256, 256, 3, 3, 1, 1),       # the mask head's maps: H and W are no multiples of 8
+    (3, 14, 14, 64, 64, 3, 3, 1, 1),
+    (1, 6, 6, 8, 8, 3, 3, 1, 1),             # the smallest legal layer: one partly filled tile in every direction
+]
+WINDOW_FWD_WGRAD_CASES = [(2, 12, 12, 32, 32, 1, 1, 2, 0)]      # 1x1 / stride 2: its data gradient is refused (a parity class without taps)
+WINDOW_F32_CASES = [(2, 16, 16, 4, 8, 5, 5, 2, 2)]              # C = 4, fp32's vector: a 32-element k-block spans eight taps
+# shapes a filter- or patch-resident family takes with a bf16 output and hands on with an fp32 one
+DECLINED_CASES = [
+    (2, 16, 32, 64, 64, 3, 3, 1, 1),
+    (2, 32, 64, 32, 64, 3, 3, 2, 1),
+    (2, 40, 40, 128, 128, 3, 3, 1, 1),
+]
+# refused by hdy_conv_fwd (7 x 7 = 49 taps against the loader's 31 tap bits): kept here so that its preconditions are checked all the same
+REFUSED_WINDOW_CASE = (1, 20, 20, 8, 16, 7, 7, 2, 3)
+# a layer the deep-pipelined family takes (with its tile minimum lifted) and the same layer with output rows wider than the input's + 1, which it must not
+DEEP_CONTROL_CASE, DESCENDING_DEEP_CASE = (4, 8, 9, 64, 128, 3, 3, 1, 1), (4, 8, 9, 64, 128, 3, 3, 1, 2)
+FORM_CASES = (RAGGED_CASES + DECONV_CASES + WINDOW_CASES + WINDOW_FWD_WGRAD_CASES + WINDOW_F32_CASES + DECLINED_CASES + [REFUSED_WINDOW_CASE] +
+              [DEEP_CONTROL_CASE, DESCENDING_DEEP_CASE])
+
+
 def all_shapes():
     """every distinct (case, stem) the exact tests build a reference for"""
     conv, deep, wdeep, res, stem, patch = case_lists()
     shapes = [(c, False) for c in list(conv) + list(deep) + list(wdeep)]
     shapes += [((N, H, W, C, K, R, 1, R // 2), False) for N, H, W, C, K, R, _, _ in res]
     shapes += [(stem_case(*s), True) for s in list(stem) + list(patch)]
-    return sorted(set(shapes))
+    return sorted(set(shapes)) + [(c, False) for c in FORM_CASES]

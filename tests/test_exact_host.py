@@ -1,5 +1,5 @@
 """CPU side of the exact convolution tests (tests/exact_ref.py): the preconditions of the integer-operand recipe
-hold for every convolution shape of the parity tests, and the comparer rejects — with the right coordinates — the errors the parity tests' criterion
+hold for every convolution shape of the parity tests and for every call form of tests/test_gpu_exact_forms.py (exact_ref.FORM_CASES), and the comparer rejects — with the right coordinates — the errors the parity tests' criterion
 (`assert_close` with TOL[bf16] = 1.5e-2 of the tensor's maximum, 1e-3 of the largest BatchNorm sum) lets through.  Every shape is checked
 (about 20 s of float64 convolutions in all); none is left out."""
 import re
@@ -163,6 +163,71 @@ def test_one_pixel_added_twice_into_a_statistics_slab():
     assert msg and re.search(r'slab 0\.\.0, stat 0\.\.1', msg), msg
     msg = rejected(lambda: X.assert_exact(doubled(lane_ok[0], k1), ref_slabs, 'slabs', X.AXES_STAT))
     assert msg and '2 of ' in msg and f'slab {lane_ok[0] // 128}..{lane_ok[0] // 128}, stat 0..1, k {k1}..{k1}' in msg, msg
+
+
+def test_every_form_case_is_among_the_checked_shapes():
+    every = {c for c, _ in SHAPES}
+    groups = (X.RAGGED_CASES, X.DECONV_CASES, X.WINDOW_CASES, X.WINDOW_FWD_WGRAD_CASES, X.WINDOW_F32_CASES, X.DECLINED_CASES, [X.REFUSED_WINDOW_CASE, X.DEEP_CONTROL_CASE, X.DESCENDING_DEEP_CASE])
+    assert all(len(c) == 9 and c in every and c in X.FORM_CASES for g in groups for c in g)
+    assert X.window((2, 20, 20, 64, 32, 1, 1, 0)) == (2, 20, 20, 64, 32, 1, 1, 1, 0)
+    e, sq = X.reference((1, 6, 6, 8, 8, 3, 3, 1, 1)), X.reference((1, 6, 6, 8, 8, 3, 1, 1))
+    assert torch.equal(e.w, sq.w) and torch.equal(e.y, sq.y), 'a square window stated with 9 numbers is the case stated with 8'
+    assert X.uncovered((1, 11, 7, 16, 24, 2, 2, 2, 0)) == (10, 6) and X.uncovered((1, 13, 11, 32, 32, 3, 3, 2, 0)) == (13, 11)
+
+
+def test_one_tap_of_a_5x5_window_dropped():
+    case = (1, 12, 12, 16, 16, 5, 5, 1, 2)
+    e = X.reference(case)
+    ref = X.nhwc(e.y)
+    assert rejected(lambda: X.assert_exact(ref.to(BF16), ref, 'y')) is None
+    for r, s in ((0, 0), (2, 2), (4, 3)):                        # a corner tap (inside the image for interior pixels only), the centre, any other
+        w = e.w.clone()
+        assert w[:, :, r, s].abs().sum() > 0
+        w[:, :, r, s] = 0
+        got = X.nhwc(F.conv2d(e.x, w, None, 1, 2)).to(BF16)
+        msg = rejected(lambda: X.assert_exact(got, ref, 'y'))
+        assert msg and ' elements differ' in msg, (r, s)
+    # ... and a single product term of one tap at one pixel
+    k, c = next((k, c) for k in range(16) for c in range(16) if e.w[k, c, 4, 3] != 0 and e.x[0, c, 5 + 4 - 2, 6 + 3 - 2] != 0)
+    got = ref.to(BF16)
+    got[0, 5, 6, k] -= (e.w[k, c, 4, 3] * e.x[0, c, 7, 7]).to(BF16)
+    msg = rejected(lambda: X.assert_exact(got, ref, 'y'))
+    assert msg and '1 of ' in msg and f'n 0..0, y 5..5, x 6..6, channel {k}..{k}' in msg, msg
+
+
+def test_nonzero_row_behind_k_in_a_padded_weight_gradient():
+    """K = 27 padded to 32: rows 27 .. 31 of the gradient are zero, and one value there — what a kernel that did not mask its zero channels,
+    or a reduction that read a row too far, would leave — is named"""
+    e = X.reference((2, 20, 20, 128, 27, 1, 1, 1, 0))
+    ref = torch.cat([e.dw, torch.zeros((5, 128, 1, 1), dtype=torch.float64)])
+    got = ref.float()
+    assert rejected(lambda: X.assert_exact(got, ref, 'dw', X.AXES_W)) is None
+    got[27, 100, 0, 0] = 1.0
+    msg = rejected(lambda: X.assert_exact(got, ref, 'dw', X.AXES_W))
+    assert msg and '1 of ' in msg and 'k 27..27, c 100..100, r 0..0, s 0..0' in msg, msg
+    got = ref.float()
+    got[31] = float('nan')                                       # a row the call never wrote
+    msg = rejected(lambda: X.assert_exact(got, ref, 'dw', X.AXES_W))
+    assert msg and '128 of ' in msg and 'k 31..31' in msg, msg
+
+
+def test_changed_guard_lane_of_a_channel_slice():
+    """K = 27 in lanes 1 .. 28 of a 30-lane buffer: the lane in front of the slice, the first lane behind it (where a vector store of the last
+    whole group of channels would land) and the slice itself are all under the one comparison"""
+    e = X.reference((2, 20, 20, 128, 27, 1, 1, 1, 0))
+    want = X.in_slice(X.nhwc(e.y), 30, 1, 5.0)
+    assert want.shape == (2, 20, 20, 30) and (want[..., 0] == 5.0).all() and (want[..., 28:] == 5.0).all() and torch.equal(want[..., 1:28], X.nhwc(e.y))
+    got = want.float()
+    assert rejected(lambda: X.assert_exact(got, want, 'y')) is None
+    for lane in (0, 28, 29):
+        bad = got.clone()
+        bad[1, 19, 19, lane] = 0.0
+        msg = rejected(lambda: X.assert_exact(bad, want, 'y'))
+        assert msg and '1 of ' in msg and f'n 1..1, y 19..19, x 19..19, channel {lane}..{lane}' in msg and 'got 0.0 want 5.0' in msg, msg
+    # an fp32 result rounded through bf16 on its way out: 301 becomes 302
+    big = X.nhwc(e.y + 301.0)
+    assert rejected(lambda: X.assert_exact(big.float(), big, 'y')) is None
+    assert ' elements differ' in rejected(lambda: X.assert_exact(big.to(BF16).float(), big, 'y'))
 
 
 def test_comparer_sees_nan_and_shape_and_inexact_references():

@@ -11,6 +11,8 @@ Legs of a case: forward raw with statistic slabs (SUM y and SUM y^2 equal the in
 with a pitched residual; SiLU alone and with the residual (the pre-activation is exact, only the activation's rounding remains); ReLU; data
 gradient written and accumulated; weight gradient into stacked grad_a / grad_b, written and accumulated.  Buffers as in the parity tests:
 pitched channel slices with poison outside, NaN-filled packs, statistic slabs, weight-gradient workspaces and outputs that are only written.
+The call forms outside the backbone's and neck's layer table (ragged K, fp32 output from bf16 operands, padded K, general windows) live in
+tests/test_gpu_exact_forms.py.
 
 Two legs are not equalities, by the kernels' design:
   * SiLU: u / (1 + exp(-u)) with the fp32 hardware exponential, then one bf16 rounding — within one bf16 ulp of the float64 value (a half-ulp
@@ -49,13 +51,13 @@ class Layer:
 
     def __init__(self, e, dtype):
         self.e, self.dtype = e, dtype
-        N, H, W, C, K, R, stride, pad = e.case
-        self.geo = (K, R, R, stride, pad)
+        N, H, W, C, K, R, S, stride, pad = X.window(e.case)
+        self.geo = (K, R, S, stride, pad)
         self.stem_hw = (H, W) if e.stem else None
         self.scale, self.shift = e.scale.float().to(DEV), e.shift.float().to(DEV)
         self.wdev = e.w.float().to(DEV)
         kind = ops.PACK_STEM if e.stem else ops.PACK_FWD
-        self.wp = ops.pack_alloc(K, C, R, R, stride, pad, kind, dtype, DEV).fill_(NAN)              # the pack must write every element (padding too)
+        self.wp = ops.pack_alloc(K, C, R, S, stride, pad, kind, dtype, DEV).fill_(NAN)              # the pack must write every element (padding too)
         if e.stem:
             self.xd = torch.full((N, H + 4, W + 4, 4), NAN, dtype=dtype, device=DEV)                # the prep pass must write every element
             ops.run([ops.rec_stem_prep(e.x.float().to(DEV), self.xd), ops.rec_pack(self.wdev, None, stride, pad, kind, self.wp)])
@@ -103,16 +105,19 @@ def check_silu(got, u, res, dtype, what):
                                               f'= {idx}: got {got[idx].item()!r}, want {ref[idx].item()!r}')
 
 
-def exact_conv(case, dtype, legs=ALL_LEGS, stem=False, fwd_family=None, relu_family=None):
+def exact_conv(case, dtype, legs=ALL_LEGS, stem=False, fwd_family=None, relu_family=None, prepare=None):
     """The legs of one case against the float64 reference.  `fwd_family`: what the dispatch log of every forward leg but ReLU must contain
     (a string, or a predicate of the log); `relu_family`: the same for the ReLU leg (default: none of the families without a ReLU instance).
+    `prepare`: called with the Layer before its first launch (tests/test_gpu_exact_forms.py poisons what no window covers).
     Returns the logs of (forward with statistics, data gradient, weight gradient) like the parity tests' conv_case."""
     e = X.reference(case, stem)
     X.check_preconditions(e)
-    N, H, W, C, K, R, stride, pad = case
+    N, H, W, C, K, R, S, stride, pad = X.window(case)
     Ho, Wo = e.Ho, e.Wo
     tag = f'{case} {dname(dtype)}'
     L = Layer(e, dtype)
+    if prepare is not None:
+        prepare(L)
 
     def ran(log, want, what):
         if want is None:
@@ -122,7 +127,7 @@ def exact_conv(case, dtype, legs=ALL_LEGS, stem=False, fwd_family=None, relu_fam
 
     log_fwd, log_dgrad, log_wgrad = [], [], []
     if 'fwd' in legs:
-        mt = ops.stat_slabs(N, H, W, C, K, R, R, stride, pad, dtype)
+        mt = ops.stat_slabs(N, H, W, C, K, R, S, stride, pad, dtype)
         stats = torch.full((mt + 1, 2, K), NAN, dtype=torch.float32, device=DEV)                # every slab must be written, and none behind them
         y, log_fwd = L.forward(stats=stats[:mt])
         ran(log_fwd, fwd_family, 'forward with statistics')
@@ -157,22 +162,23 @@ def exact_conv(case, dtype, legs=ALL_LEGS, stem=False, fwd_family=None, relu_fam
         if 'wgrad' in legs:
             log_wgrad = wgrad_legs(e, L.xd, to_dev_nhwc(e.dy, dtype), dtype, tag, stem_hw=(H, W))
         return log_fwd, log_dgrad, log_wgrad
-    if K % 8 or C % 8 or not ('dgrad' in legs or 'wgrad' in legs):
+    ve = 8 if dtype == BF16 else 4                                  # the gradient kernels move whole vectors of channels
+    if K % ve or C % ve or not ('dgrad' in legs or 'wgrad' in legs):
         return log_fwd, log_dgrad, log_wgrad
     dyd = to_dev_nhwc(e.dy, dtype, ld=K + 8, off=0)
     if 'dgrad' in legs:
-        wpd = ops.pack_alloc(K, C, R, R, stride, pad, ops.PACK_DGRAD, dtype, DEV).fill_(NAN)
+        wpd = ops.pack_alloc(K, C, R, S, stride, pad, ops.PACK_DGRAD, dtype, DEV).fill_(NAN)
         ops.run([ops.rec_pack(L.wdev, None, stride, pad, ops.PACK_DGRAD, wpd)])
         dxbuf = torch.full((N, H, W, C + 8), 5.0, dtype=dtype, device=DEV)
         dx = dxbuf[..., 8:]
         dx.fill_(NAN)
         _lib.dispatch_log(reset=True)
-        ops.run([ops.rec_conv_dgrad(dyd, wpd, dx, R, R, stride, pad)])
+        ops.run([ops.rec_conv_dgrad(dyd, wpd, dx, R, S, stride, pad)])
         log_dgrad = _lib.dispatch_log(reset=True)
         assert_exact(dx.cpu(), nhwc(e.dx), f'{tag} data gradient {log_dgrad}')
         assert (dxbuf[..., :8].float() == 5.0).all(), 'the data gradient wrote outside the channel slice'
         dx2 = nhwc(e.dx_acc).to(dtype).to(DEV)
-        ops.run([ops.rec_conv_dgrad(dyd, wpd, dx2, R, R, stride, pad, accumulate=True)])
+        ops.run([ops.rec_conv_dgrad(dyd, wpd, dx2, R, S, stride, pad, accumulate=True)])
         log2 = _lib.dispatch_log(reset=True)
         assert log2 == log_dgrad, f'{tag}: the accumulating data gradient ran {log2}, the writing one {log_dgrad}'
         assert_exact(dx2.cpu(), nhwc(e.dx + e.dx_acc), f'{tag} data gradient, accumulated {log2}')
@@ -182,11 +188,11 @@ def exact_conv(case, dtype, legs=ALL_LEGS, stem=False, fwd_family=None, relu_fam
 
 
 def wgrad_legs(e, xd, dyd, dtype, tag, stem_hw=None):
-    N, H, W, C, K, R, stride, pad = e.case
-    ws = torch.full((ops.wgrad_ws_bytes(N, H, W, C, K, R, R, stride, pad, dtype, stem=stem_hw is not None) // 4 + 1,), NAN, dtype=torch.float32, device=DEV)
+    N, H, W, C, K, R, S, stride, pad = X.window(e.case)
+    ws = torch.full((ops.wgrad_ws_bytes(N, H, W, C, K, R, S, stride, pad, dtype, stem=stem_hw is not None) // 4 + 1,), NAN, dtype=torch.float32, device=DEV)
     ka = K // 2 if K >= 16 else K
-    ga = torch.full((ka, C, R, R), NAN, dtype=torch.float32, device=DEV)
-    gb = torch.full((K - ka, C, R, R), NAN, dtype=torch.float32, device=DEV) if ka < K else None
+    ga = torch.full((ka, C, R, S), NAN, dtype=torch.float32, device=DEV)
+    gb = torch.full((K - ka, C, R, S), NAN, dtype=torch.float32, device=DEV) if ka < K else None
     logs = []
     for acc in (False, True):
         if acc:
@@ -195,7 +201,7 @@ def wgrad_legs(e, xd, dyd, dtype, tag, stem_hw=None):
             if gb is not None:
                 gb.fill_(2.0)
         _lib.dispatch_log(reset=True)
-        ops.run([ops.rec_conv_wgrad(xd, dyd, ga, gb, R, R, stride, pad, ws, accumulate=acc, stem_hw=stem_hw)])
+        ops.run([ops.rec_conv_wgrad(xd, dyd, ga, gb, R, S, stride, pad, ws, accumulate=acc, stem_hw=stem_hw)])
         logs.append(_lib.dispatch_log(reset=True))
         how = 'accumulated' if acc else 'written'
         assert_exact(ga.cpu(), e.dw[:ka], f'{tag} weight gradient a, {how} {logs[-1]}', AXES_W)
