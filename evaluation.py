@@ -322,6 +322,28 @@ def slide_nucleus_outlines(result, window=None):
 
 
 @torch.no_grad()
+def slide_nucleus_texture(result, slide, window=None, stain='hematoxylin', levels=16):
+    """One task's result with its 'label_map' and 'nuclei' (slide_nucleus_table) and the 8-bit `slide` the map was drawn on ((H, W, 3 | 4)
+    uint8) -> the texture columns of hd_yolo_amd/texture.py's texture_table, float64 device tensors with one row per detection: the
+    statistics of the nucleus's levels of `stain` ('tex_level_mean', '_std', '_skewness', '_kurtosis', '_entropy', '_min', '_median', '_max'),
+    the mean and the range over four directions of the 13 Haralick features of its co-occurrence matrices ('tex_contrast_mean',
+    'tex_contrast_range', ...) and 'tex_flags'.  stain: 'hematoxylin', 'eosin', 'residual' (colour deconvolution), 'gray', 'r', 'g', 'b'; levels
+    8, 16 or 32.  The extents are the table's 'bbox': nothing is measured again.  window = (x0, y0, w, h): the part of the slide the map
+    holds, as it was given to slide_nucleus_table.  One pass per 16 384 nuclei (ops.label_texture); nothing is read back."""
+    from hd_yolo_amd import texture as htexture
+    lm, table = result.get('label_map'), result.get('nuclei')
+    if lm is None or table is None:
+        raise ValueError("slide_nucleus_texture: the result needs 'label_map' and 'nuclei' (inference_on_slide(..., label_map=True, measure=True))")
+    if slide is None or slide.dtype != torch.uint8:
+        raise ValueError('slide_nucleus_texture: the texture is that of the 8-bit slide under the map ((H, W, 3 | 4) uint8)')
+    x0, y0 = (0, 0) if window is None else (int(window[0]), int(window[1]))
+    n = table['area']
+    shift = torch.tensor([x0, y0, x0, y0], dtype=torch.int64, device=lm.device)
+    extent = torch.where((n > 0)[:, None], table['bbox'] - shift, table['bbox']).to(torch.int32)        # nucleus_table shifted the rows that own pixels
+    return htexture.texture_table(lm, len(n), extent, slide, window=(x0, y0), stain=stain, levels=levels)
+
+
+@torch.no_grad()
 def slide_cell_graph(result, k, max_px, nc=None, mode='union'):
     """One task's result -> its cell graph (hd_yolo_amd/graph.py: knn_graph and edges), a dict of device tensors: 'knn_row' int32 (N, k), the
     rows of the k <= 16 nearest other nuclei within max_px pixels of the result's coordinates, nearest first, ties by the lowest row, -1
@@ -576,6 +598,7 @@ def main():
     ap.add_argument('--outlines', action='store_true', help='--measure: outline every nucleus as a polygon and add the hull descriptors: solidity, convexity, Feret diameters (slide_nucleus_outlines)')
     ap.add_argument('--polygons', default='', help='--outlines: write the polygons to this .geojson or .npz file (save_polygons)')
     ap.add_argument('--graph', default='', help='--measure: K,PX, e.g. 8,64: join every nucleus to its K <= 16 nearest nuclei within PX pixels (slide_cell_graph)')
+    ap.add_argument('--texture', nargs='?', const='hematoxylin', default='', metavar='STAIN', help='--measure --u8: chromatin texture of every nucleus on this stain (hematoxylin, eosin, residual, gray, r, g, b): level statistics and Haralick features as tex_* columns of the table (slide_nucleus_texture)')
     ap.add_argument('--graph-file', default='', help='--graph: write the cell graph to this .npz file (save_cell_graph)')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
@@ -628,6 +651,8 @@ def main():
             ap.error('--graph needs --measure')
         if opt.graph_file and not knn:
             ap.error('--graph-file needs --graph')
+        if opt.texture and not (opt.measure and opt.u8):
+            ap.error('--texture needs --measure and --u8')
         if opt.masks:
             cfg = synth.make_cfg('n', 2)
             cfg['headers'][0][3][3] = 1                                   # one mask class: the mask model of tests/test_gpu_mask.py
@@ -704,6 +729,17 @@ def main():
                             xy = torch.stack([v['nuclei']['centroid_x'], v['nuclei']['centroid_y']], 1)
                             save_cell_graph(opt.graph_file, cg, xy=xy, labels=v.get('labels'))
                             print(f'cell graph written to {opt.graph_file}')
+                    if opt.texture:
+                        torch.cuda.synchronize()
+                        t0 = time.time()
+                        tx = slide_nucleus_texture(v, slide, stain=opt.texture)
+                        torch.cuda.synchronize()
+                        dtt = (time.time() - t0) * 1e3
+                        held = ~torch.isnan(tx['tex_contrast_mean'])
+                        medt = lambda c: float(c[held].median()) if bool(held.any()) else float('nan')
+                        print(f'texture {opt.slide}x{opt.slide}, task {k}: {int(held.sum())} nuclei textured on {opt.texture}, median contrast '
+                              f'{medt(tx["tex_contrast_mean"]):.3f}, median entropy {medt(tx["tex_entropy_mean"]):.3f} in {dtt:.2f} ms')
+                        v['nuclei'].update(tx)
                     if opt.table:
                         save_nucleus_table(opt.table, v['nuclei'])
                         print(f'nucleus table written to {opt.table}')

@@ -1292,6 +1292,57 @@ def label_hull(label_map, R, extent):
     return hull_i, hull_f
 
 
+# ------------------------------------------------------------------------------------------ texture counts (csrc/texture.hip)
+TEXTURE_OFFSETS = ((0, 1), (-1, 1), (-1, 0), (-1, -1))        # (di, dj): 0, 45, 90 and 135 degrees at distance 1
+
+
+def label_texture(label_map, R, extent, image, lut, levels=16, offsets=TEXTURE_OFFSETS, window=(0, 0), rows=None):
+    """(hist int32 (n, levels), glcm int32 (n, D, levels, levels), flags int32 (n,)) of the labels row0 .. row0 + n - 1 of an int32 (h, w) label
+    map (hdy_label_texture, include/hdyolo_texture.h); rows = (row0, n), None = all R.  Per label, over its entries inside its box: the
+    histogram of the pixels' levels and, per offset (di, dj), the symmetric co-occurrence matrix of the levels of the pairs of entries of the
+    label that lie that far apart.  extent: the int32 (R, 4) boxes of ops.label_measure on the same map.  image: the 8-bit slide as slide_u8
+    takes it, of which the map covers the window at (x0, y0) = window.  lut: int32 (3, 256), level = clamp((lut[0][R] + lut[1][G] + lut[2][B])
+    >> 16, 0, levels - 1) (hd_yolo_amd/texture.py: stain_lut); levels 8, 16 or 32; at most 4 offsets of reach 4.  flags: 0 measured, 1 the
+    label owns nothing, 2 a box side above 1024 (zeros).  One pass, integer-exact, nothing is read back."""
+    from . import _ext
+    who = 'label_texture'
+    lm, R, extent = _outline_inputs(who, label_map, R, extent)
+    h, w = lm.shape
+    dev = lm.device
+    x0, y0 = (int(v) for v in window)
+    if image is None:
+        raise _lib.HdyError(f'{who}: the pass needs the 8-bit image under the map')
+    ip, pitch, pb, H, W = slide_u8(image)
+    if image.device != dev:
+        raise _lib.HdyError(f'{who}: the map is on {dev}, the image on {image.device}')
+    if x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise _lib.HdyError(f'{who}: the {h} x {w} map at window origin {(x0, y0)} leaves the {H} x {W} image')
+    nbytes = (H - 1) * pitch + W * pb                         # from the first byte of the view to the last byte of its last pixel
+    require_gpu(lut)
+    if lut.dtype != torch.int32 or tuple(lut.shape) != (3, 256) or lut.device != dev:
+        raise _lib.HdyError(f'{who}: lut must be an int32 (3, 256) tensor on {dev}, got {lut.dtype} {tuple(lut.shape)} on {lut.device}')
+    lut = lut.contiguous()
+    levels = int(levels)
+    if levels not in (8, 16, 32):
+        raise _lib.HdyError(f'{who}: levels={levels} (8, 16 or 32)')
+    offs = [(int(di), int(dj)) for di, dj in offsets]
+    D = len(offs)
+    if not 1 <= D <= _ext.LATER['texture'].constants['HDY_TEXTURE_MAX_OFFSETS']:
+        raise _lib.HdyError(f'{who}: {D} offsets (1 to {_ext.LATER["texture"].constants["HDY_TEXTURE_MAX_OFFSETS"]})')
+    row0, n = (0, R) if rows is None else (int(v) for v in rows)
+    if row0 < 0 or n < 0 or row0 + n > R:
+        raise _lib.HdyError(f'{who}: rows=({row0}, {n}) outside the {R} labels')
+    hist = torch.empty((n, levels), dtype=torch.int32, device=dev)
+    glcm = torch.empty((n, D, levels, levels), dtype=torch.int32, device=dev)
+    flags = torch.empty((n,), dtype=torch.int32, device=dev)
+    host_offsets = (ctypes.c_int * (2 * D))(*(v for o in offs for v in o))        # a host array: the entry point reads it before it returns
+    if n:
+        _ext.call('hdy_label_texture', lm.data_ptr(), lm.numel(), h, w, ip, nbytes, pitch, pb, x0, y0, extent.data_ptr(), extent.numel(), R,
+                  lut.data_ptr(), lut.numel(), levels, host_offsets, 2 * D, D, row0, n, hist.data_ptr(), hist.numel(), glcm.data_ptr(),
+                  glcm.numel(), flags.data_ptr(), flags.numel(), stream_ptr())
+    return hist, glcm, flags
+
+
 # ------------------------------------------------------------------------------------------ neighbourhood features (csrc/spatial.hip)
 def _spatial_inputs(who, xy_units, cls, C):
     """(xy int32 (N, 2) contiguous, class int32 (N,) with every class outside [0, C) as -1) of a point set on the GPU"""
