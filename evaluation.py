@@ -293,6 +293,19 @@ def slide_neighborhood(result, nc, radii_px, field_px=None):
     return spatial.neighborhood(table, nc, radii_px, field_px=field_px, size=None if lm is None else tuple(lm.shape))
 
 
+def _map_and_extents(who, result, window):
+    """(label map, nuclei table, R, extent, x0, y0) of one task's result: the int32 (R, 4) boxes of the table's 'bbox' in the map's own
+    coordinates, as the label passes read them, and the origin of `window` = (x0, y0, w, h) on the slide (None: the map starts at (0, 0))"""
+    lm, table = result.get('label_map'), result.get('nuclei')
+    if lm is None or table is None:
+        raise ValueError(f"{who}: the result needs 'label_map' and 'nuclei' (inference_on_slide(..., label_map=True, measure=True))")
+    x0, y0 = (0, 0) if window is None else (int(window[0]), int(window[1]))
+    n = table['area']
+    shift = torch.tensor([x0, y0, x0, y0], dtype=torch.int64, device=lm.device)
+    extent = torch.where((n > 0)[:, None], table['bbox'] - shift, table['bbox']).to(torch.int32)        # nucleus_table shifted the rows that own pixels
+    return lm, table, len(n), extent, x0, y0
+
+
 @torch.no_grad()
 def slide_nucleus_outlines(result, window=None):
     """One task's result with its 'label_map' and 'nuclei' (slide_nucleus_table) -> (shape columns, (offsets, verts)): the columns of
@@ -303,18 +316,11 @@ def slide_nucleus_outlines(result, window=None):
     to slide_nucleus_table.  Three passes (ops.label_outline: count and write; ops.label_hull); the number of vertices is read back once, to size verts."""
     from hd_yolo_amd import ops
     from hd_yolo_amd import outline as houtline
-    lm, table = result.get('label_map'), result.get('nuclei')
-    if lm is None or table is None:
-        raise ValueError("slide_nucleus_outlines: the result needs 'label_map' and 'nuclei' (inference_on_slide(..., label_map=True, measure=True))")
-    x0, y0 = (0, 0) if window is None else (int(window[0]), int(window[1]))
-    n = table['area']
-    R = len(n)
-    shift = torch.tensor([x0, y0, x0, y0], dtype=torch.int64, device=lm.device)
-    extent = torch.where((n > 0)[:, None], table['bbox'] - shift, table['bbox']).to(torch.int32)        # nucleus_table shifted the rows that own pixels
+    lm, table, R, extent, x0, y0 = _map_and_extents('slide_nucleus_outlines', result, window)
     offsets, verts, counts = ops.label_outline(lm, R, extent)
     hull_i, hull_f = ops.label_hull(lm, R, extent)
     sums = torch.zeros((R, 7), dtype=torch.int64, device=lm.device)
-    sums[:, 0], sums[:, 6] = n, table['perimeter_edges']
+    sums[:, 0], sums[:, 6] = table['area'], table['perimeter_edges']
     columns = houtline.shape_table(sums, counts, hull_i, hull_f)
     if x0 or y0:
         verts = verts + torch.tensor([x0, y0], dtype=torch.int32, device=lm.device)
@@ -331,16 +337,10 @@ def slide_nucleus_texture(result, slide, window=None, stain='hematoxylin', level
     8, 16 or 32.  The extents are the table's 'bbox': nothing is measured again.  window = (x0, y0, w, h): the part of the slide the map
     holds, as it was given to slide_nucleus_table.  One pass per 16 384 nuclei (ops.label_texture); nothing is read back."""
     from hd_yolo_amd import texture as htexture
-    lm, table = result.get('label_map'), result.get('nuclei')
-    if lm is None or table is None:
-        raise ValueError("slide_nucleus_texture: the result needs 'label_map' and 'nuclei' (inference_on_slide(..., label_map=True, measure=True))")
+    lm, _, R, extent, x0, y0 = _map_and_extents('slide_nucleus_texture', result, window)
     if slide is None or slide.dtype != torch.uint8:
         raise ValueError('slide_nucleus_texture: the texture is that of the 8-bit slide under the map ((H, W, 3 | 4) uint8)')
-    x0, y0 = (0, 0) if window is None else (int(window[0]), int(window[1]))
-    n = table['area']
-    shift = torch.tensor([x0, y0, x0, y0], dtype=torch.int64, device=lm.device)
-    extent = torch.where((n > 0)[:, None], table['bbox'] - shift, table['bbox']).to(torch.int32)        # nucleus_table shifted the rows that own pixels
-    return htexture.texture_table(lm, len(n), extent, slide, window=(x0, y0), stain=stain, levels=levels)
+    return htexture.texture_table(lm, R, extent, slide, window=(x0, y0), stain=stain, levels=levels)
 
 
 @torch.no_grad()

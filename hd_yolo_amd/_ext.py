@@ -1,16 +1,13 @@
-"""ctypes binding of the extension headers of libhdyolo_hip.so (include/hdyolo_measure.h, include/hdyolo_spatial.h, include/hdyolo_outline.h,
-include/hdyolo_graph.h: _header.EXTENSION_NAMES) and of those added since (include/hdyolo_texture.h: _header.LATER_EXTENSION_NAMES).
+"""ctypes binding of the extension headers of libhdyolo_hip.so (include/hdyolo_<name>.h for every name of _header.EXTENSION_NAMES: measure,
+spatial, outline, graph, texture).
 
 include/hdyolo.h is the numbered ABI and _lib.py its binding; an extension header declares further entry points of the same library under a
 revision of its own, read by the same reader (_header.read(path)) and bound here on the handle _lib.load() returns.  _lib.SIGNATURES,
 _lib.CONSTANTS and HDY_ABI_VERSION know nothing of them.  No CPU fallback: a library without the symbols, or of another revision, raises.
 
 EXTENSIONS maps an extension's short name to its tables; SIGNATURES, PARAMS and CONSTANTS are their unions.  A name belongs to one header:
-the import fails when two of them, or one of them and include/hdyolo.h, declare the same function or constant.
-
-LATER is a second dict of the same tuples for the headers of _header.LATER_EXTENSION_NAMES: load() binds and checks them like the first, call()
-reaches their entry points, and a name still belongs to one header across both dicts.  The unions above stay those of EXTENSIONS; the
-tables of a later header are read from LATER[name] (LATER['texture'].constants['HDY_TEXTURE_MAX_SIDE']).
+the import fails when two of them, or one of them and include/hdyolo.h, declare the same function or constant.  A new header is one more
+name in _header.EXTENSION_NAMES.
 """
 import os
 from collections import namedtuple
@@ -21,12 +18,11 @@ from ._header import HdyError
 # functions, params, constants: as _header.Header's; revision_fn returns the library's revision, revision_macro states the one bound here
 Extension = namedtuple('Extension', 'header functions params constants revision_fn revision revision_macro')
 
-EXTENSIONS, LATER = {}, {}
-for _table, _names in ((EXTENSIONS, _header.EXTENSION_NAMES), (LATER, _header.LATER_EXTENSION_NAMES)):
-    for _name, _macro in ((n, f'HDY_{n.upper()}_REVISION') for n in _names):
-        _path = _header.extension_header(_name)
-        _h = _header.read(_path)
-        _table[_name] = Extension(_path, _h.functions, _h.params, _h.constants, f'hdy_{_name}_revision', _h.constants[_macro], _macro)
+EXTENSIONS = {}
+for _name, _macro in ((n, f'HDY_{n.upper()}_REVISION') for n in _header.EXTENSION_NAMES):
+    _path = _header.extension_header(_name)
+    _h = _header.read(_path)
+    EXTENSIONS[_name] = Extension(_path, _h.functions, _h.params, _h.constants, f'hdy_{_name}_revision', _h.constants[_macro], _macro)
 
 
 def check_disjoint(extensions):
@@ -39,7 +35,7 @@ def check_disjoint(extensions):
             owner[name] = os.path.basename(ext.header)
 
 
-check_disjoint({**EXTENSIONS, **LATER})
+check_disjoint(EXTENSIONS)
 SIGNATURES = {n: v for e in EXTENSIONS.values() for n, v in e.functions.items()}
 PARAMS = {n: v for e in EXTENSIONS.values() for n, v in e.params.items()}
 CONSTANTS = {n: v for e in EXTENSIONS.values() for n, v in e.constants.items()}
@@ -53,7 +49,7 @@ def load():
     lib = _lib.load()
     if _bound is not lib:
         rebuild = 'rebuild with `python -m hd_yolo_amd.build --force`'
-        for ext in (*EXTENSIONS.values(), *LATER.values()):
+        for ext in EXTENSIONS.values():
             header = os.path.basename(ext.header)
             for name, (res, args) in ext.functions.items():
                 fn = getattr(lib, name, None)

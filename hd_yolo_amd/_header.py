@@ -16,8 +16,7 @@ import re
 from collections import namedtuple
 
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'hdyolo.h')
-EXTENSION_NAMES = ('measure', 'spatial', 'outline', 'graph')      # the extension headers, oldest first: _ext.py binds them, build.py watches them
-LATER_EXTENSION_NAMES = ('texture',)      # extension headers added since: bound by _ext.LATER beside _ext.EXTENSIONS, watched by build.py alike
+EXTENSION_NAMES = ('measure', 'spatial', 'outline', 'graph', 'texture')      # the extension headers, oldest first: _ext.py binds them, build.py watches them
 SCALARS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'long long': ctypes.c_longlong, 'unsigned long long': ctypes.c_ulonglong,
            'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double}
 POINTEES = set(SCALARS) | {'void', 'char', 'unsigned char', 'unsigned short', 'uint16_t'}       # what a pointer may point at, beside a structure

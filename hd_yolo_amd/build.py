@@ -25,7 +25,7 @@ def _newer(a, bs):
 def build(force=False, verbose=True):
     os.makedirs(OUT, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith('.h')] + [_header.HEADER_PATH]
-    headers += [_header.extension_header(n) for n in _header.EXTENSION_NAMES + _header.LATER_EXTENSION_NAMES]
+    headers += [_header.extension_header(n) for n in _header.EXTENSION_NAMES]
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 
     def compile_one(src):

@@ -61,7 +61,10 @@ void hdy_note_dispatch(const char* what);
         }                                  \
     } while (0)
 
-#define HDY_LAUNCH_CHECK(what)                                                       \
+// return a failed check's status from the entry point (the check has set the error text)
+#define HDY_CHECKED(call) do { const int rc__ = (call); if (rc__ != HDY_OK) return rc__; } while (0)
+
+#define HDY_LAUNCH_CHECK(what)                                                      \
     do {                                                                             \
         hipError_t e__ = hipGetLastError();                                          \
         if (e__ != hipSuccess) {                                                     \

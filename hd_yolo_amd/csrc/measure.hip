@@ -26,7 +26,7 @@
 // barriers and a shuffle scan that came first took 1.55 x as long.
 //
 // Contract: no allocation, everything on the passed stream, no host synchronisation; all argument checks before any launch.
-#include "common.h"
+#include "label_common.h"
 #include "hdyolo_measure.h"
 
 namespace {
@@ -47,9 +47,7 @@ static_assert(COLS == 14 && (SLOTS & (SLOTS - 1)) == 0 && ROWS * WAVES == TH && 
 struct Args {
     const int* map;
     int h, w;
-    const unsigned char* img;
-    long long row_stride;
-    int ps, x0, y0;
+    Image im;                                    // im.img null: no stain sums
     const int* origin;
     u64* sums;
     int* extent;
@@ -151,13 +149,13 @@ __global__ __launch_bounds__(THREADS) void measure_kernel(const Args a) {
             tile[ly * LW + lx] = (gi >= 0 && gi < a.h && gj >= 0 && gj < a.w) ? a.map[(long long)gi * a.w + gj] : -1;
         }
         unsigned px[ROWS];
-        if (a.img) {
+        if (a.im.img) {
 #pragma unroll
             for (int k = 0; k < ROWS; ++k) {
                 const int gi = i0 + k, gj = j0 + lane;
                 px[k] = 0;
                 if (gi < a.h && gj < a.w) {
-                    const unsigned char* p = a.img + ((long long)a.y0 + gi) * a.row_stride + ((long long)a.x0 + gj) * a.ps;
+                    const unsigned char* p = a.im.pixel(gi, gj);
                     px[k] = (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16;
                 }
             }
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(THREADS) void measure_kernel(const Args a) {
             const int edges = __popcll(__ballot(row[-LW] != c) & m) + __popcll(__ballot(row[LW] != c) & m) +
                               __popcll(__ballot(row[-1] != c) & m) + __popcll(__ballot(row[1] != c) & m);
             unsigned st[5] = {0, 0, 0, 0, 0};                                    // the run's R | G << 16, B, R^2, G^2, B^2 sums (first lane)
-            if (a.img) {                                                         // kernel-uniform
+            if (a.im.img) {                                                      // kernel-uniform
                 const unsigned p = valid ? px[k] : 0u;
                 const unsigned cr = p & 255u, cg = (p >> 8) & 255u, cb = p >> 16;
                 // wave-wide sums: colour <= 64 * 255 < 2^16, square <= 64 * 255^2 < 2^32: neither the packed fields nor the words overflow
@@ -220,7 +218,7 @@ __global__ __launch_bounds__(THREADS) void measure_kernel(const Args a) {
                 if (s >= 0) {
 #pragma unroll
                     for (int q = 0; q < COLS / 2; ++q)
-                        if (q < 4 || a.img) atomicAdd(&vals[s * (COLS / 2) + q], (u64)v[2 * q] | (u64)v[2 * q + 1] << 32);
+                        if (q < 4 || a.im.img) atomicAdd(&vals[s * (COLS / 2) + q], (u64)v[2 * q] | (u64)v[2 * q + 1] << 32);
                     atomicMin(&ext[4 * s], gj);
                     atomicMax(&ext[4 * s + 1], gj + L - 1);
                     atomicOr(&ext[4 * s + 2], 1 << k);
@@ -278,31 +276,19 @@ int hdy_label_measure(const int* map, long long map_elems, int h, int w, const u
                       int pixel_stride, int x0, int y0, const int* origin, long long* sums, long long sums_elems, int* extent,
                       long long extent_elems, int R, void* stream) {
     const char* who = "label_measure";
-    HDY_ARG(R >= 0 && map_elems >= 0 && sums_elems >= 0 && extent_elems >= 0, "%s: negative count (R=%d, map_elems=%lld, sums_elems=%lld, extent_elems=%lld)",
-            who, R, map_elems, sums_elems, extent_elems);
-    HDY_ARG(h >= 1 && w >= 1 && h <= HDY_MEASURE_MAX_SIDE && w <= HDY_MEASURE_MAX_SIDE, "%s: window %d x %d outside [1, %d]", who, h, w,
-            HDY_MEASURE_MAX_SIDE);
-    HDY_ARG(map_elems == (long long)h * w, "%s: map_elems=%lld, the call reads h * w = %d * %d", who, map_elems, h, w);
+    HDY_ARG(sums_elems >= 0, "%s: negative count (sums_elems=%lld)", who, sums_elems);
+    HDY_CHECKED(check_map(who, map_elems, h, w, HDY_MEASURE_MAX_SIDE));
+    HDY_CHECKED(check_extent(who, extent_elems, R, "writes"));
     HDY_ARG(sums_elems == (long long)HDY_MEASURE_COLS * R, "%s: sums_elems=%lld, the call writes %d * R = %d * %d", who, sums_elems,
             HDY_MEASURE_COLS, HDY_MEASURE_COLS, R);
-    HDY_ARG(extent_elems == 4ll * R, "%s: extent_elems=%lld, the call writes 4 * R = 4 * %d", who, extent_elems, R);
     HDY_ARG(R == 0 || (map && sums && extent), "%s: null map, sums or extent pointer", who);
     HDY_ARG(((uintptr_t)sums & 7) == 0 && (((uintptr_t)map | (uintptr_t)origin | (uintptr_t)extent) & 3) == 0,
             "%s: misaligned pointer (sums 8 bytes; map, origin, extent 4 bytes)", who);
-    if (image) {
-        HDY_ARG(pixel_stride == 3 || pixel_stride == 4, "%s: pixel_stride=%d (3 or 4)", who, pixel_stride);
-        HDY_ARG(row_stride > 0, "%s: row_stride=%lld must be positive", who, row_stride);
-        HDY_ARG(x0 >= 0 && y0 >= 0, "%s: negative image window origin (%d, %d)", who, x0, y0);
-        HDY_ARG(image_bytes >= 0, "%s: negative image_bytes=%lld", who, image_bytes);
-        const unsigned __int128 last = (unsigned __int128)((long long)y0 + h - 1) * (unsigned long long)row_stride +
-                                       (unsigned __int128)((long long)x0 + w - 1) * (unsigned)pixel_stride + 2;
-        HDY_ARG(last < (unsigned __int128)image_bytes, "%s: the image window (%d, %d) + %d x %d at row_stride=%lld, pixel_stride=%d leaves image_bytes=%lld",
-                who, x0, y0, w, h, row_stride, pixel_stride, image_bytes);
-    }
+    if (image) HDY_CHECKED(check_image(who, h, w, image_bytes, row_stride, pixel_stride, x0, y0));
     if (R == 0) return HDY_OK;
     hipStream_t st = (hipStream_t)stream;
     Args a = {};
-    a.map = map; a.h = h; a.w = w; a.img = image; a.row_stride = row_stride; a.ps = pixel_stride; a.x0 = x0; a.y0 = y0;
+    a.map = map; a.h = h; a.w = w; a.im = {image, row_stride, pixel_stride, x0, y0};
     a.origin = origin; a.sums = (u64*)sums; a.extent = extent; a.R = R;
     a.tiles_x = (w + TW - 1) / TW;
     a.tiles = (long long)a.tiles_x * ((h + TH - 1) / TH);

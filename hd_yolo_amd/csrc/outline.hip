@@ -20,7 +20,7 @@
 // and 0.65 ms beside 1.44 ms of hdy_label_measure on the same map; the hull is bound by the waves a CU holds, hence its two instances.
 //
 // Contract: no allocation, everything on the passed stream, no host synchronisation; all argument checks before any launch.
-#include "common.h"
+#include "label_common.h"
 #include "hdyolo_outline.h"
 
 namespace {
@@ -34,31 +34,7 @@ constexpr int GROUP = 4;                         // map rows of a box whose load
 constexpr int SMALL_LV = 128, SMALL_THREADS = 256;
 constexpr int BIG_LV = MAX_SIDE + 1, BIG_THREADS = 64;
 constexpr int MAX_BLOCKS = 1 << 16;
-enum { FLAG_EMPTY = 1, FLAG_SIDE = 2, FLAG_EXTENT = 4 };
-
-struct Box {
-    int x0, y0, bw, bh, flag;
-};
-
-// the label's extent clamped into the window; flag 1 / 2 when there is nothing to do
-__host__ __device__ __forceinline__ Box clamped_box(const int* __restrict__ extent, int r, int h, int w) {
-    const int* e = extent + 4 * (size_t)r;
-    const int ex0 = e[0], ey0 = e[1], ex1 = e[2], ey1 = e[3];
-    Box b;
-    b.x0 = ex0 > 0 ? ex0 : 0;
-    b.y0 = ey0 > 0 ? ey0 : 0;
-    const int x1 = ex1 < w - 1 ? ex1 : w - 1, y1 = ey1 < h - 1 ? ey1 : h - 1;
-    // x0 may be up to 2^31 - 1 and x1 down to -2^31: compare before subtracting
-    b.flag = (x1 < b.x0 || y1 < b.y0) ? FLAG_EMPTY : 0;
-    b.bw = b.flag ? 0 : x1 - b.x0 + 1;
-    b.bh = b.flag ? 0 : y1 - b.y0 + 1;
-    if (!b.flag && (b.bw > MAX_SIDE || b.bh > MAX_SIDE)) b.flag = FLAG_SIDE;
-    return b;
-}
-
-__host__ __device__ __forceinline__ bool owns(const int* __restrict__ map, int h, int w, int i, int j, int r) {
-    return (unsigned)i < (unsigned)h && (unsigned)j < (unsigned)w && map[(long long)i * w + j] == r;
-}
+enum { FLAG_EXTENT = 4 };                       // beside FLAG_EMPTY and FLAG_SIDE: the extent was not this map's
 
 // the pixel to the right of the crack that leaves corner (x, y) in direction d (0: +x, 1: +y, 2: -x, 3: -y; y points down), as (row, column)
 // offsets from (y, x): right of +x is below, right of +y is to the left, right of -x is above, right of -y is to the right
@@ -73,7 +49,7 @@ template <bool WRITE>
 __host__ __device__ __forceinline__ bool walk_label(const int* __restrict__ map, int h, int w, const int* __restrict__ extent, int r,
                                                     long long* __restrict__ counts, const long long* __restrict__ offsets,
                                                     int* __restrict__ verts, long long total) {
-    const Box b = clamped_box(extent, r, h, w);
+    const Box b = clamped_box(extent, r, h, w, MAX_SIDE);
     int flag = b.flag;
     long long V = 0, area2 = 0, L = 0;
     long long lo = 0, hi = 0;                                          // WRITE: the label's rows of verts are [lo, hi)
@@ -165,7 +141,7 @@ __global__ __launch_bounds__(THREADS) void hull_kernel(const int* __restrict__ m
     const long long waves = (long long)gridDim.x * HULL_WAVES;
     for (long long rr = (long long)blockIdx.x * HULL_WAVES + wv; rr < R; rr += waves) {      // wave-uniform
         const int r = (int)rr;
-        const Box b = clamped_box(extent, r, h, w);
+        const Box b = clamped_box(extent, r, h, w, MAX_SIDE);
         if ((b.bh < SMALL_LV) != (LV == SMALL_LV)) continue;           // the other instance's label (flagged labels have bh = 0 or are caught below)
         int flag = b.flag;
         int n0 = 0, n1 = 0;
@@ -285,22 +261,13 @@ __global__ __launch_bounds__(THREADS) void hull_kernel(const int* __restrict__ m
     }
 }
 
-// the checks the three entry points share
-int check_common(const char* who, const int* map, long long map_elems, int h, int w, const int* extent, long long extent_elems, int R) {
-    HDY_ARG(R >= 0 && map_elems >= 0 && extent_elems >= 0, "%s: negative count (R=%d, map_elems=%lld, extent_elems=%lld)", who, R, map_elems,
-            extent_elems);
-    HDY_ARG(h >= 1 && w >= 1 && h <= HDY_OUTLINE_MAX_WINDOW && w <= HDY_OUTLINE_MAX_WINDOW, "%s: window %d x %d outside [1, %d]", who, h, w,
-            HDY_OUTLINE_MAX_WINDOW);
-    HDY_ARG(map_elems == (long long)h * w, "%s: map_elems=%lld, the call reads h * w = %d * %d", who, map_elems, h, w);
-    HDY_ARG(extent_elems == 4ll * R, "%s: extent_elems=%lld, the call reads 4 * R = 4 * %d", who, extent_elems, R);
+// what the three entry points read: the map window, the extent table and their two pointers
+int check_inputs(const char* who, const int* map, long long map_elems, int h, int w, const int* extent, long long extent_elems, int R) {
+    HDY_CHECKED(check_map(who, map_elems, h, w, HDY_OUTLINE_MAX_WINDOW));
+    HDY_CHECKED(check_extent(who, extent_elems, R, "reads"));
     HDY_ARG(R == 0 || (map && extent), "%s: null map or extent pointer", who);
     HDY_ARG((((uintptr_t)map | (uintptr_t)extent) & 3) == 0, "%s: misaligned pointer (map, extent 4 bytes)", who);
     return HDY_OK;
-}
-
-unsigned walk_blocks(int R) {
-    const long long blocks = ((long long)R + WALK_THREADS - 1) / WALK_THREADS;
-    return (unsigned)(blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS);
 }
 
 }  // namespace
@@ -313,12 +280,12 @@ int hdy_label_outline_count(const int* map, long long map_elems, int h, int w, c
                             long long* counts, long long counts_elems, void* stream) {
     const char* who = "label_outline_count";
     HDY_ARG(counts_elems >= 0, "%s: negative count (counts_elems=%lld)", who, counts_elems);
-    if (int rc = check_common(who, map, map_elems, h, w, extent, extent_elems, R)) return rc;
+    HDY_CHECKED(check_inputs(who, map, map_elems, h, w, extent, extent_elems, R));
     HDY_ARG(counts_elems == 4ll * R, "%s: counts_elems=%lld, the call writes 4 * R = 4 * %d", who, counts_elems, R);
     HDY_ARG(R == 0 || counts, "%s: null counts pointer", who);
     HDY_ARG(((uintptr_t)counts & 7) == 0, "%s: misaligned pointer (counts 8 bytes)", who);
     if (R == 0) return HDY_OK;
-    hipLaunchKernelGGL(walk_kernel<false>, dim3(walk_blocks(R)), dim3(WALK_THREADS), 0, (hipStream_t)stream, map, h, w, extent, R, counts,
+    hipLaunchKernelGGL(walk_kernel<false>, dim3(label_blocks(R, WALK_THREADS, MAX_BLOCKS)), dim3(WALK_THREADS), 0, (hipStream_t)stream, map, h, w, extent, R, counts,
                        (const long long*)nullptr, (int*)nullptr, 0ll, (int*)nullptr);
     HDY_LAUNCH_CHECK(who);
     hdy_note_dispatch("label_outline_count");
@@ -329,7 +296,7 @@ int hdy_label_outline_write(const int* map, long long map_elems, int h, int w, c
                             const long long* offsets, long long offsets_elems, int* verts, long long verts_elems, int* status, void* stream) {
     const char* who = "label_outline_write";
     HDY_ARG(offsets_elems >= 0 && verts_elems >= 0, "%s: negative count (offsets_elems=%lld, verts_elems=%lld)", who, offsets_elems, verts_elems);
-    if (int rc = check_common(who, map, map_elems, h, w, extent, extent_elems, R)) return rc;
+    HDY_CHECKED(check_inputs(who, map, map_elems, h, w, extent, extent_elems, R));
     HDY_ARG(offsets_elems == (long long)R + 1, "%s: offsets_elems=%lld, the call reads R + 1 = %d + 1", who, offsets_elems, R);
     HDY_ARG((verts_elems & 1) == 0, "%s: verts_elems=%lld is odd, a vertex is two entries", who, verts_elems);
     HDY_ARG(R == 0 || (offsets && status && (verts || verts_elems == 0)), "%s: null offsets, verts or status pointer", who);
@@ -338,7 +305,7 @@ int hdy_label_outline_write(const int* map, long long map_elems, int h, int w, c
     if (R == 0) return HDY_OK;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(clear_status_kernel, dim3(1), dim3(1), 0, st, status);
-    hipLaunchKernelGGL(walk_kernel<true>, dim3(walk_blocks(R)), dim3(WALK_THREADS), 0, st, map, h, w, extent, R, (long long*)nullptr, offsets,
+    hipLaunchKernelGGL(walk_kernel<true>, dim3(label_blocks(R, WALK_THREADS, MAX_BLOCKS)), dim3(WALK_THREADS), 0, st, map, h, w, extent, R, (long long*)nullptr, offsets,
                        verts, verts_elems / 2, status);
     HDY_LAUNCH_CHECK(who);
     hdy_note_dispatch("label_outline_write");
@@ -349,16 +316,15 @@ int hdy_label_hull(const int* map, long long map_elems, int h, int w, const int*
                    long long hull_i_elems, double* hull_f, long long hull_f_elems, void* stream) {
     const char* who = "label_hull";
     HDY_ARG(hull_i_elems >= 0 && hull_f_elems >= 0, "%s: negative count (hull_i_elems=%lld, hull_f_elems=%lld)", who, hull_i_elems, hull_f_elems);
-    if (int rc = check_common(who, map, map_elems, h, w, extent, extent_elems, R)) return rc;
+    HDY_CHECKED(check_inputs(who, map, map_elems, h, w, extent, extent_elems, R));
     HDY_ARG(hull_i_elems == 4ll * R, "%s: hull_i_elems=%lld, the call writes 4 * R = 4 * %d", who, hull_i_elems, R);
     HDY_ARG(hull_f_elems == 2ll * R, "%s: hull_f_elems=%lld, the call writes 2 * R = 2 * %d", who, hull_f_elems, R);
     HDY_ARG(R == 0 || (hull_i && hull_f), "%s: null hull_i or hull_f pointer", who);
     HDY_ARG((((uintptr_t)hull_i | (uintptr_t)hull_f) & 7) == 0, "%s: misaligned pointer (hull_i, hull_f 8 bytes)", who);
     if (R == 0) return HDY_OK;
-    const long long small = ((long long)R + SMALL_THREADS / 64 - 1) / (SMALL_THREADS / 64), big = ((long long)R + BIG_THREADS / 64 - 1) / (BIG_THREADS / 64);
-    hipLaunchKernelGGL((hull_kernel<SMALL_LV, SMALL_THREADS>), dim3((unsigned)(small < MAX_BLOCKS ? small : MAX_BLOCKS)), dim3(SMALL_THREADS), 0,
+    hipLaunchKernelGGL((hull_kernel<SMALL_LV, SMALL_THREADS>), dim3(label_blocks(R, SMALL_THREADS / 64, MAX_BLOCKS)), dim3(SMALL_THREADS), 0,
                        (hipStream_t)stream, map, h, w, extent, R, hull_i, hull_f);
-    hipLaunchKernelGGL((hull_kernel<BIG_LV, BIG_THREADS>), dim3((unsigned)(big < MAX_BLOCKS ? big : MAX_BLOCKS)), dim3(BIG_THREADS), 0,
+    hipLaunchKernelGGL((hull_kernel<BIG_LV, BIG_THREADS>), dim3(label_blocks(R, BIG_THREADS / 64, MAX_BLOCKS)), dim3(BIG_THREADS), 0,
                        (hipStream_t)stream, map, h, w, extent, R, hull_i, hull_f);
     HDY_LAUNCH_CHECK(who);
     hdy_note_dispatch("label_hull");

@@ -5,9 +5,6 @@
 #include "common.h"
 #include "hdyolo_spatial.h"
 
-// return a failed check's status from the entry point (the check has set the error text)
-#define HDY_CHECKED(call) do { const int rc__ = (call); if (rc__ != HDY_OK) return rc__; } while (0)
-
 namespace {
 
 struct Grid { int cell, ncx, ncy, ncells; };

@@ -15,7 +15,7 @@
 // or 2 to the diagonal cell.  The finished table goes out with plain coalesced stores; a flagged label stores zeros.
 //
 // Contract: no allocation, everything on the passed stream, no host synchronisation; all argument checks before any launch.
-#include "common.h"
+#include "label_common.h"
 #include "hdyolo_texture.h"
 
 namespace {
@@ -29,9 +29,7 @@ static_assert(MAXD == 4 && HDY_TEXTURE_MAX_LEVELS == 32, "the LDS budget below i
 struct Args {
     const int* map;
     int h, w;
-    const unsigned char* img;
-    long long row_stride;
-    int ps, x0, y0;
+    Image im;
     const int* extent;
     const int* lut;
     int D;
@@ -43,7 +41,7 @@ struct Args {
 };
 
 template <int L> __device__ __forceinline__ int level_of(const Args& a, const int* lut, int i, int j) {
-    const unsigned char* p = a.img + ((long long)a.y0 + i) * a.row_stride + ((long long)a.x0 + j) * a.ps;
+    const unsigned char* p = a.im.pixel(i, j);
     const unsigned t = (unsigned)lut[p[0]] + (unsigned)lut[256 + p[1]] + (unsigned)lut[512 + p[2]];       // modulo 2^32
     const int v = (int)t >> SHIFT;                                                                         // floor(t / 2^SHIFT)
     return v < 0 ? 0 : v > L - 1 ? L - 1 : v;
@@ -66,14 +64,11 @@ template <int L, int THREADS> __global__ __launch_bounds__(THREADS) void texture
 
     for (long long q = (long long)blockIdx.x * WAVES + wv; q < a.rows; q += (long long)gridDim.x * WAVES) {
         const int r = a.row0 + (int)q;
-        const int* e = a.extent + 4 * (size_t)r;
-        const int bx0 = max(e[0], 0), by0 = max(e[1], 0), bx1 = min(e[2], a.w - 1), by1 = min(e[3], a.h - 1);
-        const long long bw = (long long)bx1 - bx0 + 1, bh = (long long)by1 - by0 + 1;      // garbage extents: the differences may pass 32 bits
-        const int flag = (bw < 1 || bh < 1) ? 1 : (bw > MAX_SIDE || bh > MAX_SIDE) ? 2 : 0;
+        const Box b = clamped_box(a.extent, r, a.h, a.w, MAX_SIDE);
         int* gq = a.glcm + (size_t)q * used;
         int* hq = a.hist + (size_t)q * L;
-        if (lane == 0) a.flags[q] = flag;
-        if (flag) {                                          // wave-uniform
+        if (lane == 0) a.flags[q] = b.flag;
+        if (b.flag) {                                        // wave-uniform
             for (int k = lane; k < used; k += 64) gq[k] = 0;
             if (lane < L) hq[lane] = 0;
             continue;
@@ -84,21 +79,22 @@ template <int L, int THREADS> __global__ __launch_bounds__(THREADS) void texture
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 
         int sh = 6;                                          // cw = 1 << sh columns per step, 64 >> sh rows
-        while (sh > 0 && (1 << (sh - 1)) >= (int)bw) --sh;
+        while (sh > 0 && (1 << (sh - 1)) >= b.bw) --sh;
         const int cw = 1 << sh, rp = 64 >> sh;
         const int li = lane >> sh, lj = lane & (cw - 1);
-        for (int ib = by0; ib <= by1; ib += rp) {
+        const int bx1 = b.x0 + b.bw - 1, by1 = b.y0 + b.bh - 1;
+        for (int ib = b.y0; ib <= by1; ib += rp) {
             const int i = ib + li;
-            for (int jb = bx0; jb <= bx1; jb += cw) {
+            for (int jb = b.x0; jb <= bx1; jb += cw) {
                 const int j = jb + lj;
-                if (i > by1 || j > bx1 || a.map[(long long)i * a.w + j] != r) continue;
+                if (i > by1 || j > bx1 || a.map[(long long)i * a.w + j] != r) continue;      // inside the window: the box is clamped
                 const int lv = level_of<L>(a, lut_s, i, j);
                 atomicAdd(&hist[lv], 1);
 #pragma unroll
                 for (int d = 0; d < MAXD; ++d) {                                 // unrolled: the offsets stay in scalar registers
                     if (d >= a.D) break;
                     const int ni = i + a.di[d], nj = j + a.dj[d];
-                    if (ni < 0 || ni >= a.h || nj < 0 || nj >= a.w || a.map[(long long)ni * a.w + nj] != r) continue;
+                    if (!owns(a.map, a.h, a.w, ni, nj, r)) continue;
                     const int nl = level_of<L>(a, lut_s, ni, nj);
                     int* m = acc + d * L * L;
                     if (nl == lv) {
@@ -121,8 +117,7 @@ template <int L, int THREADS> __global__ __launch_bounds__(THREADS) void texture
 }
 
 template <int L, int THREADS> void launch(const Args& a, hipStream_t st) {
-    const long long blocks = ((long long)a.rows + THREADS / 64 - 1) / (THREADS / 64);
-    hipLaunchKernelGGL((texture_kernel<L, THREADS>), dim3((unsigned)(blocks < MAX_BLOCKS ? blocks : MAX_BLOCKS)), dim3(THREADS), 0, st, a);
+    hipLaunchKernelGGL((texture_kernel<L, THREADS>), dim3(label_blocks(a.rows, THREADS / 64, MAX_BLOCKS)), dim3(THREADS), 0, st, a);
 }
 
 }  // namespace
@@ -136,15 +131,11 @@ int hdy_label_texture(const int* map, long long map_elems, int h, int w, const u
                       int levels, const int* offsets, long long offsets_elems, int D, int row0, int rows, int* hist, long long hist_elems,
                       int* glcm, long long glcm_elems, int* flags, long long flags_elems, void* stream) {
     const char* who = "label_texture";
-    HDY_ARG(R >= 0 && map_elems >= 0 && extent_elems >= 0 && lut_elems >= 0 && offsets_elems >= 0 && hist_elems >= 0 && glcm_elems >= 0 &&
-                flags_elems >= 0,
-            "%s: negative count (R=%d, map_elems=%lld, extent_elems=%lld, lut_elems=%lld, offsets_elems=%lld, hist_elems=%lld, glcm_elems=%lld, "
-            "flags_elems=%lld)",
-            who, R, map_elems, extent_elems, lut_elems, offsets_elems, hist_elems, glcm_elems, flags_elems);
-    HDY_ARG(h >= 1 && w >= 1 && h <= HDY_TEXTURE_MAX_WINDOW && w <= HDY_TEXTURE_MAX_WINDOW, "%s: window %d x %d outside [1, %d]", who, h, w,
-            HDY_TEXTURE_MAX_WINDOW);
-    HDY_ARG(map_elems == (long long)h * w, "%s: map_elems=%lld, the call reads h * w = %d * %d", who, map_elems, h, w);
-    HDY_ARG(extent_elems == 4ll * R, "%s: extent_elems=%lld, the call reads 4 * R = 4 * %d", who, extent_elems, R);
+    HDY_ARG(lut_elems >= 0 && offsets_elems >= 0 && hist_elems >= 0 && glcm_elems >= 0 && flags_elems >= 0,
+            "%s: negative count (lut_elems=%lld, offsets_elems=%lld, hist_elems=%lld, glcm_elems=%lld, flags_elems=%lld)", who, lut_elems,
+            offsets_elems, hist_elems, glcm_elems, flags_elems);
+    HDY_CHECKED(check_map(who, map_elems, h, w, HDY_TEXTURE_MAX_WINDOW));
+    HDY_CHECKED(check_extent(who, extent_elems, R, "reads"));
     HDY_ARG(lut_elems == 768, "%s: lut_elems=%lld, the call reads 3 * 256 = 768", who, lut_elems);
     HDY_ARG(levels == 8 || levels == 16 || levels == 32, "%s: levels=%d (8, 16 or 32)", who, levels);
     HDY_ARG(D >= 1 && D <= HDY_TEXTURE_MAX_OFFSETS, "%s: D=%d outside [1, %d]", who, D, HDY_TEXTURE_MAX_OFFSETS);
@@ -168,18 +159,11 @@ int hdy_label_texture(const int* map, long long map_elems, int h, int w, const u
     HDY_ARG(rows == 0 || (hist && glcm && flags), "%s: null hist, glcm or flags pointer", who);
     HDY_ARG((((uintptr_t)map | (uintptr_t)extent | (uintptr_t)lut | (uintptr_t)hist | (uintptr_t)glcm | (uintptr_t)flags) & 3) == 0,
             "%s: misaligned pointer (map, extent, lut, hist, glcm, flags 4 bytes)", who);
-    HDY_ARG(pixel_stride == 3 || pixel_stride == 4, "%s: pixel_stride=%d (3 or 4)", who, pixel_stride);
-    HDY_ARG(row_stride > 0, "%s: row_stride=%lld must be positive", who, row_stride);
-    HDY_ARG(x0 >= 0 && y0 >= 0, "%s: negative image window origin (%d, %d)", who, x0, y0);
-    HDY_ARG(image_bytes >= 0, "%s: negative image_bytes=%lld", who, image_bytes);
-    const unsigned __int128 last = (unsigned __int128)((long long)y0 + h - 1) * (unsigned long long)row_stride +
-                                   (unsigned __int128)((long long)x0 + w - 1) * (unsigned)pixel_stride + 2;
-    HDY_ARG(last < (unsigned __int128)image_bytes, "%s: the image window (%d, %d) + %d x %d at row_stride=%lld, pixel_stride=%d leaves image_bytes=%lld",
-            who, x0, y0, w, h, row_stride, pixel_stride, image_bytes);
+    HDY_CHECKED(check_image(who, h, w, image_bytes, row_stride, pixel_stride, x0, y0));
     if (R == 0 || rows == 0) return HDY_OK;
     hipStream_t st = (hipStream_t)stream;
     Args a = {};
-    a.map = map; a.h = h; a.w = w; a.img = image; a.row_stride = row_stride; a.ps = pixel_stride; a.x0 = x0; a.y0 = y0;
+    a.map = map; a.h = h; a.w = w; a.im = {image, row_stride, pixel_stride, x0, y0};
     a.extent = extent; a.lut = lut; a.D = D; a.row0 = row0; a.rows = rows; a.hist = hist; a.glcm = glcm; a.flags = flags;
     for (int d = 0; d < MAXD; ++d) {
         a.di[d] = offsets[2 * (d < D ? d : D - 1)];

@@ -30,7 +30,9 @@ import os
 
 import torch
 
-COLS = 14
+from . import _ext
+
+COLS = _ext.CONSTANTS['HDY_MEASURE_COLS']
 
 
 def nucleus_table(sums, extent, origin=None, offset=(0, 0), labels=None, scores=None, stain=True):

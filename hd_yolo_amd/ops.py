@@ -13,8 +13,9 @@ import threading
 
 import torch
 
-from . import _lib
+from . import _ext, _lib
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, BF16, F32, PACK_DGRAD, PACK_FWD, PACK_STEM  # noqa: F401
+from .texture import OFFSETS as TEXTURE_OFFSETS  # noqa: F401  the default offsets of label_texture and of texture.texture_table
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03     # metayolo/models/utils_torch.py:47-49
 
@@ -1193,15 +1194,38 @@ def label_areas(label_map, R):
 
 
 # ------------------------------------------------------------------------------------------ label measurement (csrc/measure.hip)
-def _label_rows(who, label_map, R):
-    """(the map contiguous, R) of a non-empty int32 (h, w) label map on the GPU and a row count"""
+def _label_inputs(who, label_map, R, extent=None):
+    """(the map contiguous, R, the extent contiguous) of a non-empty int32 (h, w) label map on the GPU, a row count and, where the pass reads
+    one, the int32 (R, 4) extent table on the map's device"""
     require_gpu(label_map)
     if label_map.dtype != torch.int32 or label_map.dim() != 2 or label_map.numel() == 0:
         raise _lib.HdyError(f'{who}: the map must be a non-empty int32 (h, w) tensor, got {label_map.dtype} {tuple(label_map.shape)}')
     R = int(R)
     if R < 0:
         raise _lib.HdyError(f'{who}: negative row count R={R}')
-    return label_map.contiguous(), R
+    lm = label_map.contiguous()
+    if extent is not None:
+        require_gpu(extent)
+        if extent.dtype != torch.int32 or tuple(extent.shape) != (R, 4) or extent.device != lm.device:
+            raise _lib.HdyError(f'{who}: extent must be an int32 ({R}, 4) tensor on {lm.device} (ops.label_measure makes it), got '
+                                f'{extent.dtype} {tuple(extent.shape)} on {extent.device}')
+        extent = extent.contiguous()
+    return lm, R, extent
+
+
+def _image_window(who, image, lm, window):
+    """(ip, nbytes, pitch, pb, x0, y0) as the label passes take the 8-bit image under the map: the view slide_u8 accepts, on the map's device,
+    of which the map covers the window at (x0, y0) = window; image None gives a null pointer and zeros"""
+    x0, y0 = (int(v) for v in window)
+    if image is None:
+        return None, 0, 0, 0, x0, y0
+    h, w = lm.shape
+    ip, pitch, pb, H, W = slide_u8(image)
+    if image.device != lm.device:
+        raise _lib.HdyError(f'{who}: the map is on {lm.device}, the image on {image.device}')
+    if x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise _lib.HdyError(f'{who}: the {h} x {w} map at window origin {(x0, y0)} leaves the {H} x {W} image')
+    return ip, (H - 1) * pitch + W * pb, pitch, pb, x0, y0        # nbytes: from the first byte of the view to the last byte of its last pixel
 
 
 def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
@@ -1211,18 +1235,9 @@ def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
     image: the 8-bit slide as slide_u8 takes it ((H, W, 3 | 4) uint8, any row stride), of which the map covers the window at (x0, y0) = window;
     None leaves the stain columns zero.  origin: int32 (R, 2) = (ox, oy) per label in map coordinates (None = zeros); hd_yolo_amd/measure.py
     (nucleus_table) turns the sums into the measurements."""
-    from . import _ext
-    lm, R = _label_rows('label_measure', label_map, R)
+    lm, R, _ = _label_inputs('label_measure', label_map, R)
     h, w = lm.shape
-    x0, y0 = (int(v) for v in window)
-    ip, nbytes, pitch, pb = None, 0, 0, 0
-    if image is not None:
-        ip, pitch, pb, H, W = slide_u8(image)
-        if image.device != lm.device:
-            raise _lib.HdyError(f'label_measure: the map is on {lm.device}, the image on {image.device}')
-        if x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
-            raise _lib.HdyError(f'label_measure: the {h} x {w} map at window origin {(x0, y0)} leaves the {H} x {W} image')
-        nbytes = (H - 1) * pitch + W * pb                     # from the first byte of the view to the last byte of its last pixel
+    window = _image_window('label_measure', image, lm, window)
     if origin is not None:
         require_gpu(origin)
         if origin.dtype != torch.int32 or tuple(origin.shape) != (R, 2) or origin.device != lm.device:
@@ -1231,21 +1246,12 @@ def label_measure(label_map, R, image=None, window=(0, 0), origin=None):
     sums = torch.empty((R, _ext.CONSTANTS['HDY_MEASURE_COLS']), dtype=torch.int64, device=lm.device)
     extent = torch.empty((R, 4), dtype=torch.int32, device=lm.device)
     if R:
-        _ext.call('hdy_label_measure', lm.data_ptr(), lm.numel(), h, w, ip, nbytes, pitch, pb, x0, y0, ptr(origin), sums.data_ptr(), sums.numel(),
+        _ext.call('hdy_label_measure', lm.data_ptr(), lm.numel(), h, w, *window, ptr(origin), sums.data_ptr(), sums.numel(),
                   extent.data_ptr(), extent.numel(), R, stream_ptr())
     return sums, extent
 
 
 # ------------------------------------------------------------------------------------------ outlines and hulls (csrc/outline.hip)
-def _outline_inputs(who, label_map, R, extent):
-    lm, R = _label_rows(who, label_map, R)
-    require_gpu(extent)
-    if extent.dtype != torch.int32 or tuple(extent.shape) != (R, 4) or extent.device != lm.device:
-        raise _lib.HdyError(f'{who}: extent must be an int32 ({R}, 4) tensor on {lm.device} (ops.label_measure makes it), got '
-                            f'{extent.dtype} {tuple(extent.shape)} on {extent.device}')
-    return lm, R, extent.contiguous()
-
-
 def label_outline(label_map, R, extent):
     """(offsets int64 (R + 1,), verts int32 (total, 2), counts int64 (R, 4)) of the R labels of an int32 (h, w) label map: the outer boundary
     of every label's first 4-connected component as a closed polygon of lattice corners (x, y), clockwise on screen, the start corner first
@@ -1254,8 +1260,7 @@ def label_outline(label_map, R, extent):
     verts[offsets[r]:offsets[r + 1]].  Two launches (hdy_label_outline_count, hdy_label_outline_write) with torch.cumsum between them on the
     device.  `total`, the number of vertices, is the one scalar of the result this call reads back: it sizes verts.  The status word of the
     writing pass (non-zero when the second walk disagrees with the first) is read once the pass is queued and raises."""
-    from . import _ext
-    lm, R, extent = _outline_inputs('label_outline', label_map, R, extent)
+    lm, R, extent = _label_inputs('label_outline', label_map, R, extent)
     h, w = lm.shape
     dev = lm.device
     counts = torch.empty((R, 4), dtype=torch.int64, device=dev)
@@ -1281,8 +1286,7 @@ def label_hull(label_map, R, extent):
     convex hull of all pixel squares of every label, fragments included, holes ignored.  hull_i = {hull vertices, twice the hull area, squared
     maximum Feret diameter, flags as label_outline's}, exact; hull_f = {hull perimeter, minimum Feret diameter}.  extent: ops.label_measure's.
     One pass, nothing is read back."""
-    from . import _ext
-    lm, R, extent = _outline_inputs('label_hull', label_map, R, extent)
+    lm, R, extent = _label_inputs('label_hull', label_map, R, extent)
     h, w = lm.shape
     hull_i = torch.empty((R, 4), dtype=torch.int64, device=lm.device)
     hull_f = torch.empty((R, 2), dtype=torch.float64, device=lm.device)
@@ -1293,9 +1297,6 @@ def label_hull(label_map, R, extent):
 
 
 # ------------------------------------------------------------------------------------------ texture counts (csrc/texture.hip)
-TEXTURE_OFFSETS = ((0, 1), (-1, 1), (-1, 0), (-1, -1))        # (di, dj): 0, 45, 90 and 135 degrees at distance 1
-
-
 def label_texture(label_map, R, extent, image, lut, levels=16, offsets=TEXTURE_OFFSETS, window=(0, 0), rows=None):
     """(hist int32 (n, levels), glcm int32 (n, D, levels, levels), flags int32 (n,)) of the labels row0 .. row0 + n - 1 of an int32 (h, w) label
     map (hdy_label_texture, include/hdyolo_texture.h); rows = (row0, n), None = all R.  Per label, over its entries inside its box: the
@@ -1304,20 +1305,13 @@ def label_texture(label_map, R, extent, image, lut, levels=16, offsets=TEXTURE_O
     takes it, of which the map covers the window at (x0, y0) = window.  lut: int32 (3, 256), level = clamp((lut[0][R] + lut[1][G] + lut[2][B])
     >> 16, 0, levels - 1) (hd_yolo_amd/texture.py: stain_lut); levels 8, 16 or 32; at most 4 offsets of reach 4.  flags: 0 measured, 1 the
     label owns nothing, 2 a box side above 1024 (zeros).  One pass, integer-exact, nothing is read back."""
-    from . import _ext
     who = 'label_texture'
-    lm, R, extent = _outline_inputs(who, label_map, R, extent)
+    lm, R, extent = _label_inputs(who, label_map, R, extent)
     h, w = lm.shape
     dev = lm.device
-    x0, y0 = (int(v) for v in window)
     if image is None:
         raise _lib.HdyError(f'{who}: the pass needs the 8-bit image under the map')
-    ip, pitch, pb, H, W = slide_u8(image)
-    if image.device != dev:
-        raise _lib.HdyError(f'{who}: the map is on {dev}, the image on {image.device}')
-    if x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
-        raise _lib.HdyError(f'{who}: the {h} x {w} map at window origin {(x0, y0)} leaves the {H} x {W} image')
-    nbytes = (H - 1) * pitch + W * pb                         # from the first byte of the view to the last byte of its last pixel
+    window = _image_window(who, image, lm, window)
     require_gpu(lut)
     if lut.dtype != torch.int32 or tuple(lut.shape) != (3, 256) or lut.device != dev:
         raise _lib.HdyError(f'{who}: lut must be an int32 (3, 256) tensor on {dev}, got {lut.dtype} {tuple(lut.shape)} on {lut.device}')
@@ -1327,8 +1321,8 @@ def label_texture(label_map, R, extent, image, lut, levels=16, offsets=TEXTURE_O
         raise _lib.HdyError(f'{who}: levels={levels} (8, 16 or 32)')
     offs = [(int(di), int(dj)) for di, dj in offsets]
     D = len(offs)
-    if not 1 <= D <= _ext.LATER['texture'].constants['HDY_TEXTURE_MAX_OFFSETS']:
-        raise _lib.HdyError(f'{who}: {D} offsets (1 to {_ext.LATER["texture"].constants["HDY_TEXTURE_MAX_OFFSETS"]})')
+    if not 1 <= D <= _ext.CONSTANTS['HDY_TEXTURE_MAX_OFFSETS']:
+        raise _lib.HdyError(f'{who}: {D} offsets (1 to {_ext.CONSTANTS["HDY_TEXTURE_MAX_OFFSETS"]})')
     row0, n = (0, R) if rows is None else (int(v) for v in rows)
     if row0 < 0 or n < 0 or row0 + n > R:
         raise _lib.HdyError(f'{who}: rows=({row0}, {n}) outside the {R} labels')
@@ -1337,7 +1331,7 @@ def label_texture(label_map, R, extent, image, lut, levels=16, offsets=TEXTURE_O
     flags = torch.empty((n,), dtype=torch.int32, device=dev)
     host_offsets = (ctypes.c_int * (2 * D))(*(v for o in offs for v in o))        # a host array: the entry point reads it before it returns
     if n:
-        _ext.call('hdy_label_texture', lm.data_ptr(), lm.numel(), h, w, ip, nbytes, pitch, pb, x0, y0, extent.data_ptr(), extent.numel(), R,
+        _ext.call('hdy_label_texture', lm.data_ptr(), lm.numel(), h, w, *window, extent.data_ptr(), extent.numel(), R,
                   lut.data_ptr(), lut.numel(), levels, host_offsets, 2 * D, D, row0, n, hist.data_ptr(), hist.numel(), glcm.data_ptr(),
                   glcm.numel(), flags.data_ptr(), flags.numel(), stream_ptr())
     return hist, glcm, flags
@@ -1381,7 +1375,6 @@ def spatial_cells(pts, cell_units, ncx, ncy):
     """(cell_start int32 (ncx * ncy + 1,), status int32 (1,)) of points in cell order (hdy_spatial_cells, include/hdyolo_spatial.h): pts int32
     (N, 4) = (x, y, class, original row) sorted by cell, absent points last.  status is a device word, non-zero when pts is not in cell order;
     nothing is read back."""
-    from . import _ext
     _sorted_points('spatial_cells', pts)
     ncx, ncy = int(ncx), int(ncy)
     cell_start = torch.empty((max(ncx * ncy, 0) + 1,), dtype=torch.int32, device=pts.device)
@@ -1398,7 +1391,6 @@ def spatial_cells(pts, cell_units, ncx, ncy):
 def spatial_neighbors_sorted(pts, cell_start, cell_units, ncx, ncy, radii_units, C):
     """(counts int32 (N, K, C), near_d2 int64 (N, C), near_row int32 (N, C)) from points in cell order and their cell_start
     (hdy_spatial_neighbors): the second half of spatial_neighbors, rows of the outputs = the points' original rows."""
-    from . import _ext
     _sorted_points('spatial_neighbors', pts, cell_start)
     radii = [int(r) for r in radii_units]
     N, K, C = pts.shape[0], len(radii), int(C)
@@ -1460,7 +1452,6 @@ def spatial_neighbors(xy_units, cls, C, radii_units, cell_units=None, extent_uni
 def spatial_density(xy_units, cls, C, g_units, gx, gy):
     """grid int32 (gy, gx, C): the present points of class c in [0, C) whose position falls into field (y // g_units, x // g_units)
     (hdy_spatial_density); points outside the gx x gy fields, absent points and query-only points are not counted.  Integer adds only."""
-    from . import _ext
     xy, cls32, N, C = _spatial_inputs('spatial_density', xy_units, cls, C)
     gx, gy = int(gx), int(gy)
     pts = _spatial_pts(xy, cls32)
@@ -1480,7 +1471,6 @@ KNN_CELL_FILL = 0.25            # spatial_knn's default cell aims at this many t
 def spatial_knn_sorted(pts, cell_start, cell_units, ncx, ncy, k, max_radius_units):
     """(nbr_row int32 (N, k), nbr_d2 int64 (N, k), nbr_count int32 (N,)) from points in cell order and their cell_start (hdy_graph_knn,
     include/hdyolo_graph.h): the second half of spatial_knn, rows of the outputs = the points' original rows."""
-    from . import _ext
     _sorted_points('spatial_knn', pts, cell_start)
     N, k = pts.shape[0], int(k)
     dev = pts.device
@@ -1498,7 +1488,6 @@ def knn_cell_units(N, k, max_radius_units, mx, my, fill=KNN_CELL_FILL):
     spread evenly holds fill * k of them, floored by ceil(max_radius / HDY_GRAPH_MAX_RINGS) (the ring bound of hdy_graph_knn) and by
     ceil(extent / SPATIAL_GRID_SIDE)."""
     import math
-    from . import _ext
     want = math.isqrt(int((mx + 1) * (my + 1) * fill * max(int(k), 1)) // max(int(N), 1))
     return max(want, -(-int(max_radius_units) // _ext.CONSTANTS['HDY_GRAPH_MAX_RINGS']), -(-(max(mx, my) + 1) // SPATIAL_GRID_SIDE), 1)
 
@@ -1528,7 +1517,6 @@ def spatial_knn(xy_units, k, max_radius_units, cls=None, C=None, cell_units=None
 def knn_mutual(nbr_row):
     """mutual int32 (N, k) of nbr_row int32 (N, k) (hdy_graph_mutual): entry (p, s) is 1 when q = nbr_row[p, s] is a row and p is among q's
     neighbours, else 0.  Any content of nbr_row is safe."""
-    from . import _ext
     require_gpu(nbr_row)
     if nbr_row.dtype != torch.int32 or nbr_row.dim() != 2:
         raise _lib.HdyError(f'knn_mutual: nbr_row must be an int32 (N, k) tensor, got {nbr_row.dtype} {tuple(nbr_row.shape)}')

@@ -13,7 +13,9 @@ Everything is tensor arithmetic around the two device calls: no loop over rows, 
 """
 import torch
 
-UNITS = 16          # HDY_SPATIAL_SUBPIXEL
+from . import _ext
+
+UNITS = _ext.CONSTANTS['HDY_SPATIAL_SUBPIXEL']
 
 
 def to_units(xy_px):

@@ -34,11 +34,13 @@ A direction without pairs (sum(glcm) = 0: a single pixel, a flagged label) gives
 """
 import torch
 
+from . import _ext
+
 FEATURES = ('asm', 'contrast', 'correlation', 'variance', 'idm', 'sum_average', 'sum_variance', 'sum_entropy', 'entropy', 'difference_variance',
             'difference_entropy', 'imc1', 'imc2')
 INTENSITY = ('level_mean', 'level_std', 'level_skewness', 'level_kurtosis', 'level_entropy', 'level_min', 'level_median', 'level_max')
 OFFSETS = ((0, 1), (-1, 1), (-1, 0), (-1, -1))                # (di, dj): 0, 45, 90 and 135 degrees at distance 1
-SHIFT = 16                                                    # HDY_TEXTURE_SHIFT
+SHIFT = _ext.CONSTANTS['HDY_TEXTURE_SHIFT']
 ENTRY_BOUND = 1 << 28                                         # three entries below it cannot wrap the pass's 32-bit sum
 RUIFROK_H, RUIFROK_E = (0.65, 0.70, 0.29), (0.07, 0.99, 0.11)
 REC601 = (0.299, 0.587, 0.114)

@@ -163,7 +163,7 @@ def test_extension_header_parses_and_is_bound(lib):
     assert lib.hdy_graph_revision() == ext.revision == 1
     assert _ext.CONSTANTS['HDY_GRAPH_MAX_K'] == 16 and _ext.CONSTANTS['HDY_GRAPH_MAX_RINGS'] == 16
     assert not any(k.startswith('HDY_GRAPH') for k in _lib.CONSTANTS)
-    assert 'graph.hip' in build.SOURCES and list(_ext.EXTENSIONS)[-1] == 'graph'
+    assert 'graph.hip' in build.SOURCES and list(_ext.EXTENSIONS)[3] == 'graph'
 
 
 def test_graph_knn_shares_the_point_and_grid_checks_of_spatial_neighbors(lib):

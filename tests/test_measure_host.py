@@ -173,8 +173,9 @@ def test_every_extension_keeps_its_tables_and_a_name_belongs_to_one_header(lib):
     want = {'measure': (['hdy_label_measure', 'hdy_measure_revision'], 3),
             'spatial': (['hdy_spatial_cells', 'hdy_spatial_density', 'hdy_spatial_neighbors', 'hdy_spatial_revision'], 6),
             'outline': (['hdy_label_hull', 'hdy_label_outline_count', 'hdy_label_outline_write', 'hdy_outline_revision'], 3),
-            'graph': (['hdy_graph_knn', 'hdy_graph_mutual', 'hdy_graph_revision'], 3)}
-    assert list(_ext.EXTENSIONS) == list(want) == list(_header.EXTENSION_NAMES)                 # oldest first, graph last
+            'graph': (['hdy_graph_knn', 'hdy_graph_mutual', 'hdy_graph_revision'], 3),
+            'texture': (['hdy_label_texture', 'hdy_texture_revision'], 7)}
+    assert list(_ext.EXTENSIONS) == list(want) == list(_header.EXTENSION_NAMES)                 # oldest first, texture last
     for short, (functions, n_constants) in want.items():
         ext = _ext.EXTENSIONS[short]
         assert sorted(ext.functions) == functions and sorted(ext.params) == functions and len(ext.constants) == n_constants
@@ -186,9 +187,9 @@ def test_every_extension_keeps_its_tables_and_a_name_belongs_to_one_header(lib):
             for name in getattr(ext, table):
                 assert name not in base and [s for s, e in _ext.EXTENSIONS.items() if name in getattr(e, table)] == [short], name
     exts = list(_ext.EXTENSIONS.values())
-    assert _ext.SIGNATURES == {n: v for e in exts for n, v in e.functions.items()} and len(_ext.SIGNATURES) == 2 + 4 + 4 + 3
+    assert _ext.SIGNATURES == {n: v for e in exts for n, v in e.functions.items()} and len(_ext.SIGNATURES) == 2 + 4 + 4 + 3 + 2
     assert _ext.PARAMS == {n: v for e in exts for n, v in e.params.items()} and sorted(_ext.PARAMS) == sorted(_ext.SIGNATURES)
-    assert _ext.CONSTANTS == {n: v for e in exts for n, v in e.constants.items()} and len(_ext.CONSTANTS) == 3 + 6 + 3 + 3
+    assert _ext.CONSTANTS == {n: v for e in exts for n, v in e.constants.items()} and len(_ext.CONSTANTS) == 3 + 6 + 3 + 3 + 7
     _ext.check_disjoint(_ext.EXTENSIONS)                                                         # the tables as they are pass
     graph = _ext.EXTENSIONS['graph']
     for doctored, word in ((graph._replace(functions=dict(graph.functions, hdy_spatial_cells=graph.functions['hdy_graph_mutual'])),

@@ -15,6 +15,8 @@ from scipy.spatial import ConvexHull
 
 import measure_ref as mref
 import outline_ref as ref
+from test_measure_host import _call as _measure      # the same 20 x 30 map of 5 labels as COMMON below
+from test_texture_host import _call as _texture
 from hd_yolo_amd import _header, _lib, build
 from hd_yolo_amd import outline as houtline
 
@@ -236,8 +238,9 @@ def _hull(lib, **kw):
     return rc, lib.hdy_last_error()
 
 
-@pytest.mark.parametrize('call', [_count, _write, _hull], ids=['count', 'write', 'hull'])
+@pytest.mark.parametrize('call', [_count, _write, _hull, _measure, _texture], ids=['count', 'write', 'hull', 'measure', 'texture'])
 def test_the_checks_all_three_share(lib, call):
+    """the map and extent checks of csrc/label_common.h, through the three entry points here and those of hdy_label_measure and hdy_label_texture"""
     lib.hdy_dispatch_log_reset()
     for kw in ({'map': None}, {'extent': None}):
         rc, msg = call(lib, **kw)

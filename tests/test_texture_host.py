@@ -1,6 +1,6 @@
 """CPU tests of the texture pass's specification and surroundings: the numpy restatements of include/hdyolo_texture.h against each other and
 against hand-derived cases, the features of hd_yolo_amd/texture.py against their loop restatement, the header and its binding through
-_ext.LATER, every argument check of hdy_label_texture (reached with fake pointers: nothing launches), and stain_lut over all 2^24 colours."""
+_ext.EXTENSIONS, every argument check of hdy_label_texture (reached with fake pointers: nothing launches), and stain_lut over all 2^24 colours."""
 import ctypes
 import math
 import os
@@ -154,8 +154,8 @@ def lib():
 def test_texture_header_parses_and_is_bound_beside_the_four(lib):
     from hd_yolo_amd import _ext
     path = os.path.join(ROOT, 'include', 'hdyolo_texture.h')
-    assert _header.LATER_EXTENSION_NAMES == ('texture',) and list(_ext.LATER) == ['texture']
-    ext = _ext.LATER['texture']
+    assert _header.EXTENSION_NAMES[-1] == 'texture' and list(_ext.EXTENSIONS)[-1] == 'texture'
+    ext = _ext.EXTENSIONS['texture']
     assert ext.header == path == _header.extension_header('texture')
     hdr = _header.read(path)
     assert sorted(hdr.functions) == ['hdy_label_texture', 'hdy_texture_revision'] and not hdr.structs
@@ -169,23 +169,25 @@ def test_texture_header_parses_and_is_bound_beside_the_four(lib):
     for name, (res, args) in hdr.functions.items():
         fn = getattr(lib, name)                                            # exported by the built library ...
         assert fn.restype is res and list(fn.argtypes) == args, name      # ... and bound by _ext.load()
-        assert name not in _lib.SIGNATURES and name not in _ext.SIGNATURES
+        assert name not in _lib.SIGNATURES                                 # the numbered ABI does not know the extension
+        assert _ext.SIGNATURES[name] == (res, args) and _ext.PARAMS[name] == hdr.params[name]
     assert (ext.functions, ext.params, ext.constants) == (hdr.functions, hdr.params, hdr.constants)
     assert (ext.revision_fn, ext.revision_macro) == ('hdy_texture_revision', 'HDY_TEXTURE_REVISION')
     assert lib.hdy_texture_revision() == ext.revision == 1
     assert ext.constants['HDY_TEXTURE_SHIFT'] == htexture.SHIFT == ref.SHIFT and ext.constants['HDY_TEXTURE_MAX_SIDE'] == ref.MAX_SIDE
-    assert not any(k.startswith('HDY_TEXTURE') for k in (*_lib.CONSTANTS, *_ext.CONSTANTS))
-    # the first list is what it was: four headers, 13 functions, 15 constants
-    assert list(_ext.EXTENSIONS) == ['measure', 'spatial', 'outline', 'graph'] == list(_header.EXTENSION_NAMES)
-    assert len(_ext.SIGNATURES) == 13 and len(_ext.PARAMS) == 13 and len(_ext.CONSTANTS) == 15
+    assert not any(k.startswith('HDY_TEXTURE') for k in _lib.CONSTANTS)
+    assert {k: v for k, v in _ext.CONSTANTS.items() if k.startswith('HDY_TEXTURE')} == hdr.constants and len(hdr.constants) == 7
+    # one list: five headers, 15 functions, 22 constants
+    assert list(_ext.EXTENSIONS) == ['measure', 'spatial', 'outline', 'graph', 'texture'] == list(_header.EXTENSION_NAMES)
+    assert len(_ext.SIGNATURES) == 15 and len(_ext.PARAMS) == 15 and len(_ext.CONSTANTS) == 22
     assert 'texture.hip' in build.SOURCES
 
 
 def test_a_name_belongs_to_one_header_across_both_lists():
     from hd_yolo_amd import _ext
-    both = {**_ext.EXTENSIONS, **_ext.LATER}
+    both = dict(_ext.EXTENSIONS)                                          # one table now: the five headers
     _ext.check_disjoint(both)                                             # the tables as they are pass
-    tex = _ext.LATER['texture']
+    tex = both['texture']
     doctored = tex._replace(functions=dict(tex.functions, hdy_label_measure=_ext.SIGNATURES['hdy_label_measure']))
     with pytest.raises(_lib.HdyError) as e:
         _ext.check_disjoint(dict(both, texture=doctored))
@@ -272,6 +274,8 @@ def test_label_texture_image_checks(lib):
                {'row_stride': 1 << 62}):
         rc, msg = _call(lib, **kw)
         assert rc == _lib.EINVAL and b'image' in msg, kw
+    # every check passed and rows = 0: nothing to write, no launch, whatever the other pointers
+    assert _call(lib, rows=0, hist_elems=0, glcm_elems=0, flags_elems=0, map=None, extent=None, lut=None, hist=None, glcm=None, flags=None)[0] == _lib.OK
 
 
 def test_zero_rows_launch_nothing(lib):
