@@ -501,6 +501,15 @@ def slide_orders(pred_boxes, true_boxes):
     return _cell_order(pred_boxes, x0, y0, cell, 4096), _cell_order(true_boxes, x0, y0, cell, 4096)
 
 
+def _score_inputs(who, result, truth, iouv):
+    """what both slide scorers start from: (iouv, or the ten thresholds 0.5 .. 0.95; fp32 scores; prediction labels; truth labels on the scores'
+    device), flat; multi-label sets are refused"""
+    if result['labels'].dim() != 1 or truth['labels'].dim() != 1:
+        raise ValueError(f'{who}: multi-label results must be flattened first (val_nuclei.flatten_onehot_objects)')
+    ps = result['scores'].detach().float().reshape(-1)
+    return torch.linspace(0.5, 0.95, 10) if iouv is None else iouv, ps, result['labels'].detach(), truth['labels'].detach().to(ps.device)
+
+
 @torch.no_grad()
 def score_slide(result, truth, iouv=None, ignore=(-100, -1), info=None):
     """Scores one task's whole-slide result ({'boxes', 'scores', 'labels'}, as inference_on_slide returns it) against the slide's annotations
@@ -510,11 +519,8 @@ def score_slide(result, truth, iouv=None, ignore=(-100, -1), info=None):
     order, and the results are un-permuted.  Returns APMeter.ap_per_class's stats dict plus 'match' (int32 per detection: the row of its
     truth, or -1), 'match_iou' (fp32), 'hit' (threshold bits) and 'live', device tensors in the given order.  `info` receives chunks_visited / chunks_total / workspace_bytes."""
     from hd_yolo_amd import ops
-    iouv = torch.linspace(0.5, 0.95, 10) if iouv is None else iouv
-    if result['labels'].dim() != 1 or truth['labels'].dim() != 1:
-        raise ValueError('score_slide: multi-label results must be flattened first (val_nuclei.flatten_onehot_objects)')
-    pb, ps, pl = result['boxes'].detach().float().reshape(-1, 4), result['scores'].detach().float().reshape(-1), result['labels'].detach()
-    tb, tl = truth['boxes'].detach().float().reshape(-1, 4).to(pb.device), truth['labels'].detach().to(pb.device)
+    iouv, ps, pl, tl = _score_inputs('score_slide', result, truth, iouv)
+    pb, tb = result['boxes'].detach().float().reshape(-1, 4), truth['boxes'].detach().float().reshape(-1, 4).to(ps.device)
     dev, n, m = pb.device, len(pb), len(tb)
     op, ot = slide_orders(pb, tb)
     off = lambda k: torch.tensor([0, k], dtype=torch.int32, device=dev)   # noqa: E731
@@ -524,20 +530,21 @@ def score_slide(result, truth, iouv=None, ignore=(-100, -1), info=None):
     inv[op] = torch.arange(n, device=dev)
     hit, live, match, miou = hit[inv], live[inv], match[inv], miou[inv]
     match = torch.where(match >= 0, ot[match.clamp_min(0).to(torch.int64)].to(torch.int32), match) if m else match
-    stats = _slide_stats(hit, live, ps, pl, tl, iouv, ignore)
-    stats.update(match=match, match_iou=miou, hit=hit, live=live)
-    return stats
+    return _slide_stats(hit, live, match, miou, ps, pl, tl, iouv, ignore)
 
 
-def _slide_stats(hit, live, ps, pl, tl, iouv, ignore):
-    """APMeter.ap_per_class's stats dict from the device's per-detection hit bits and live flags (one copy of each compact array)"""
+def _slide_stats(hit, live, match, miou, ps, pl, tl, iouv, ignore, **more):
+    """APMeter.ap_per_class's stats dict from the device's per-detection hit bits and live flags (one copy of each compact array), plus the
+    per-detection device tensors themselves and whatever `more` the caller adds"""
     from metayolo.models.metrics import ap_curves
     import numpy as np
     thr = np.asarray(iouv.tolist() if hasattr(iouv, 'tolist') else list(iouv), dtype=np.float32)
     bits, keep = hit.cpu().numpy().view(np.uint16), live.cpu().numpy().astype(bool)
     flags = ((bits[:, None] >> np.arange(len(thr), dtype=np.uint16)[None]) & 1).astype(bool)
-    return ap_curves(flags[keep], ps.cpu().numpy()[keep], pl.cpu().numpy().astype(np.int64)[keep], tl.cpu().numpy().astype(np.int64), thr,
-                     [int(v) for v in (ignore or ())])
+    stats = ap_curves(flags[keep], ps.cpu().numpy()[keep], pl.cpu().numpy().astype(np.int64)[keep], tl.cpu().numpy().astype(np.int64), thr,
+                      [int(v) for v in (ignore or ())])
+    stats.update(match=match, match_iou=miou, hit=hit, live=live, **more)
+    return stats
 
 
 @torch.no_grad()
@@ -560,17 +567,12 @@ def score_slide_masks(result, truth, iouv=None, ignore=(-100, -1), summaries=Fal
     detection, object, shared pixels), device tensors.  summaries=True adds 'pq', 'sq', 'dq', 'mpq', 'aji', 'dice' and their counts
     (slide_segmentation_summary), formed from those.  One device-to-host read before the curves (the overlap status)."""
     from hd_yolo_amd import ops
-    iouv = torch.linspace(0.5, 0.95, 10) if iouv is None else iouv
-    if result['labels'].dim() != 1 or truth['labels'].dim() != 1:
-        raise ValueError('score_slide_masks: multi-label results must be flattened first (val_nuclei.flatten_onehot_objects)')
+    iouv, ps, pl, tl = _score_inputs('score_slide_masks', result, truth, iouv)
     if 'label_map' not in result or 'label_map' not in truth:
         raise ValueError("score_slide_masks: both sides need a 'label_map' (inference_on_slide(..., compute_masks=True, label_map=True))")
-    ps, pl = result['scores'].detach().float().reshape(-1), result['labels'].detach()
-    tl = truth['labels'].detach().to(ps.device)
     pairs, pa, ta = ops.label_overlap(result['label_map'], truth['label_map'].to(ps.device), len(ps), len(tl))
     hit, live, match, miou = ops.mask_ap_match(pairs, pa, ta, ps, pl, tl, iouv, ignore=ignore)
-    stats = _slide_stats(hit, live, ps, pl, tl, iouv, ignore)
-    stats.update(match=match, match_iou=miou, hit=hit, live=live, pred_area=pa, true_area=ta, pairs=pairs)
+    stats = _slide_stats(hit, live, match, miou, ps, pl, tl, iouv, ignore, pred_area=pa, true_area=ta, pairs=pairs)
     if summaries:
         stats.update(slide_segmentation_summary(stats, pl, tl))
     return stats

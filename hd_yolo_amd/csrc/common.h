@@ -111,6 +111,18 @@ struct PerDeviceOnce {
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// hipMemsetAsync of `bytes` (none: no call) on the stream; a failure sets the error text and is returned as the HIP status (HDY_CHECKED)
+static inline int hdy_memset_async(const char* who, void* p, int v, size_t bytes, hipStream_t st) {
+    if (bytes == 0) return HDY_OK;
+    const hipError_t e = hipMemsetAsync(p, v, bytes, st);
+    if (e != hipSuccess) {
+        hdy_set_error("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
+        return (int)e;
+    }
+    return HDY_OK;
+}
 
 #ifdef __HIPCC__
 // 16-byte vector <-> 8 bf16 / 4 f32 views

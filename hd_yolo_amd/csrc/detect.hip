@@ -463,13 +463,13 @@ size_t hdy_nms_workspace_bytes(int B, int N) { return (size_t)(B > 0 ? B : 0) * 
 
 // workspace of a call with this max_det: the sort keys, and beyond 4096 kept boxes per tile the kept list itself (20 bytes per entry)
 size_t hdy_nms_workspace_bytes_for(int B, int N, int max_det) {
-    size_t n = (hdy_nms_workspace_bytes(B, N) + 15) & ~(size_t)15;
+    size_t n = up16(hdy_nms_workspace_bytes(B, N));
     if (max_det > MAX_KEEP) n += (size_t)(B > 0 ? B : 0) * (size_t)max_det * 20;
     return n;
 }
 
 static int nms_launch(NmsArgs& a, void* workspace, hipStream_t st, const char* who) {
-    const size_t sort_bytes = (hdy_nms_workspace_bytes(a.B, a.N) + 15) & ~(size_t)15;
+    const size_t sort_bytes = up16(hdy_nms_workspace_bytes(a.B, a.N));
     if (a.max_det > MAX_KEEP) {
         a.kept_g = (float4*)((char*)workspace + sort_bytes);                        
         a.kept_area_g = (float*)(a.kept_g + (size_t)a.B * a.max_det);

@@ -31,7 +31,6 @@ constexpr int THREADS = 256;
 constexpr int ROWS = 4;                          // 64-entry rows a wave has in flight per step
 constexpr u64 EMPTY = ~0ull;                     // no key: p < 2^31, so no pair has it
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline bool pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
 
 struct OArgs {
@@ -126,23 +125,14 @@ __global__ __launch_bounds__(THREADS) void overlap_kernel(const OArgs a) {
     }
 }
 
-struct MArgs {
+// the rule block, and where the mask form's IoU comes from: the pair table, the areas and rule 2's best word per prediction
+struct MArgs : ApRules {
     const u64* keys;
     const unsigned* counts;
     long long slots;
     const int *parea, *tarea;
-    const float* ps;
-    const long long *pl, *tl;
-    const int *prow, *trow;
-    int n_pred, n_true, n_iou, n_ign;
-    float pair_iou;
-    float iouv[16];
-    long long ign[4];
-    unsigned short* hit;
-    unsigned char* live;
-    int* match;
-    float* miou;
-    u64 *best, *claim;
+    int n_pred, n_true;
+    u64* best;
 };
 
 // slot s as a pair: its rows and IoU; false when the slot is empty, out of range, or below pair_iou (NaN included)
@@ -161,8 +151,7 @@ __device__ __forceinline__ bool slot_pair(const MArgs& a, long long s, int& p, i
 }
 
 __device__ __forceinline__ u64 best_key(const MArgs& a, int t, float iou) {
-    const unsigned row = (unsigned)(a.trow ? a.trow[t] : t);
-    return ((u64)__float_as_uint(iou) << 32) | (0xFFFFFFFFu - row);
+    return ((u64)__float_as_uint(iou) << 32) | (0xFFFFFFFFu - (unsigned)a.true_row(t));
 }
 
 __global__ __launch_bounds__(THREADS) void init_kernel(const MArgs a) {
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(THREADS) void best_kernel(const MArgs a) {
     int p, t;
     float iou;
     if (!slot_pair(a, s, p, t, iou)) return;
-    if (ap_ignored(a.ign, a.n_ign, a.pl[p]) || ap_ignored(a.ign, a.n_ign, a.tl[t])) a.live[p] = 1;        // touched (every writer stores 1)
+    if (ap_ignored(a, a.pl[p]) || ap_ignored(a, a.tl[t])) a.live[p] = 1;        // touched (every writer stores 1)
     else atomicMax(&a.best[p], best_key(a, t, iou));
 }
 
@@ -192,27 +181,16 @@ __global__ __launch_bounds__(THREADS) void claim_kernel(const MArgs a) {
     int p, t;
     float iou;
     if (!slot_pair(a, s, p, t, iou)) return;
-    if (ap_ignored(a.ign, a.n_ign, a.pl[p]) || ap_ignored(a.ign, a.n_ign, a.tl[t])) return;
+    if (ap_ignored(a, a.pl[p]) || ap_ignored(a, a.tl[t])) return;
     if (a.best[p] != best_key(a, t, iou)) return;
     a.match[p] = t;
     a.miou[p] = iou;
-    atomicMin(&a.claim[t], ap_claim_key(a.ps[p], (unsigned)(a.prow ? a.prow[p] : p)));
+    atomicMin(&a.claim[t], ap_claim_key(a.ps[p], (unsigned)a.pred_row(p)));
 }
 
 __global__ __launch_bounds__(THREADS) void resolve_kernel(const MArgs a) {
     const int p = blockIdx.x * THREADS + threadIdx.x;
-    if (p >= a.n_pred) return;
-    ap_resolve(p, (unsigned)(a.prow ? a.prow[p] : p), a.ps, a.pl, a.tl, a.claim, a.iouv, a.n_iou, a.hit, a.live, a.match, a.miou);
-}
-
-int memset_async(const char* who, void* p, int v, size_t bytes, hipStream_t st) {
-    if (bytes == 0) return HDY_OK;
-    const hipError_t e = hipMemsetAsync(p, v, bytes, st);
-    if (e != hipSuccess) {
-        hdy_set_error("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
-        return (int)e;
-    }
-    return HDY_OK;
+    if (p < a.n_pred) ap_resolve(a, p);
 }
 
 }  // namespace
@@ -251,11 +229,11 @@ int hdy_label_overlap(const int* pred_map, const int* true_map, long long elems,
     a.keys = (u64*)table; a.counts = (unsigned*)((char*)table + (size_t)slots * 8); a.mask = (unsigned)(slots - 1); a.status = status;
 
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = memset_async(who, a.keys, 0xFF, (size_t)slots * 8, st)) return rc;
-    if (int rc = memset_async(who, a.counts, 0, (size_t)slots * 4, st)) return rc;
-    if (int rc = memset_async(who, status, 0, 8, st)) return rc;
-    if (int rc = memset_async(who, pred_area, 0, (size_t)n_pred * 4, st)) return rc;
-    if (int rc = memset_async(who, true_area, 0, (size_t)n_true * 4, st)) return rc;
+    HDY_CHECKED(hdy_memset_async(who, a.keys, 0xFF, (size_t)slots * 8, st));
+    HDY_CHECKED(hdy_memset_async(who, a.counts, 0, (size_t)slots * 4, st));
+    HDY_CHECKED(hdy_memset_async(who, status, 0, 8, st));
+    HDY_CHECKED(hdy_memset_async(who, pred_area, 0, (size_t)n_pred * 4, st));
+    HDY_CHECKED(hdy_memset_async(who, true_area, 0, (size_t)n_true * 4, st));
     if (elems > 0 && (n_pred > 0 || n_true > 0)) {
         const long long per_block = (long long)THREADS * ROWS;
         const long long blocks = (elems + per_block - 1) / per_block;
@@ -277,30 +255,22 @@ int hdy_mask_ap_match(const void* table, size_t table_bytes, long long slots, co
                       int* match, float* match_iou, void* workspace, size_t ws_bytes, void* stream) {
     const char* who = "mask_ap_match";
     HDY_ARG(n_pred >= 0 && n_true >= 0, "%s: negative count (n_pred=%d, n_true=%d)", who, n_pred, n_true);
-    HDY_ARG(n_iou >= 1 && n_iou <= 16, "%s: n_iou=%d outside [1, 16]", who, n_iou);
-    HDY_ARG(n_ignore >= 0 && n_ignore <= 4, "%s: n_ignore=%d outside [0, 4]", who, n_ignore);
-    HDY_ARG(iouv && (ignore || n_ignore == 0), "%s: null threshold or ignore array (host pointers)", who);
-    HDY_ARG(pair_iou > 0.f && pair_iou <= 1.f, "%s: pair_iou must be in (0, 1]", who);
+    HDY_CHECKED(ap_check_rules(who, n_pred, n_true, pred_scores, pred_labels, pred_row, true_labels, true_row, iouv, n_iou, pair_iou, ignore, n_ignore,
+                               hit, live, match, match_iou));
     HDY_ARG(pow2(slots) && slots <= HDY_OVERLAP_MAX_SLOTS, "%s: slots=%lld is not a power of two in [1, %lld]", who, slots,
             (long long)HDY_OVERLAP_MAX_SLOTS);
     HDY_ARG(table && table_bytes >= hdy_label_overlap_workspace_bytes(slots), "%s: null table or table too small (%zu bytes, %lld slots need %zu)",
             who, table_bytes, slots, hdy_label_overlap_workspace_bytes(slots));
-    HDY_ARG(n_pred == 0 || (pred_area && pred_scores && pred_labels && hit && live && match && match_iou), "%s: null prediction or output pointer", who);
-    HDY_ARG(n_true == 0 || (true_area && true_labels), "%s: null truth pointer", who);
+    HDY_ARG((n_pred == 0 || pred_area) && (n_true == 0 || true_area), "%s: null area pointer", who);
     HDY_ARG(workspace && ws_bytes >= hdy_mask_ap_match_workspace_bytes(n_pred, n_true), "%s: null workspace or workspace too small", who);
     HDY_ARG((((uintptr_t)table | (uintptr_t)workspace) & 15) == 0, "%s: table and workspace must be 16-byte aligned", who);
-    HDY_ARG((((uintptr_t)pred_labels | (uintptr_t)true_labels) & 7) == 0, "%s: labels must be 8-byte aligned", who);
-    HDY_ARG((((uintptr_t)pred_area | (uintptr_t)true_area | (uintptr_t)pred_scores | (uintptr_t)pred_row | (uintptr_t)true_row | (uintptr_t)match |
-              (uintptr_t)match_iou) & 3) == 0 && ((uintptr_t)hit & 1) == 0, "%s: misaligned pointer", who);
+    HDY_ARG((((uintptr_t)pred_area | (uintptr_t)true_area) & 3) == 0, "%s: misaligned pointer", who);
 
     MArgs a;
     a.keys = (const u64*)table; a.counts = (const unsigned*)((const char*)table + (size_t)slots * 8); a.slots = slots;
-    a.parea = pred_area; a.tarea = true_area; a.ps = pred_scores; a.pl = pred_labels; a.tl = true_labels; a.prow = pred_row; a.trow = true_row;
-    a.n_pred = n_pred; a.n_true = n_true; a.n_iou = n_iou; a.n_ign = n_ignore; a.pair_iou = pair_iou;
-    for (int j = 0; j < 16; ++j) a.iouv[j] = j < n_iou ? iouv[j] : 2.f;
-    for (int j = 0; j < 4; ++j) a.ign[j] = j < n_ignore ? ignore[j] : 0;
-    a.hit = hit; a.live = live; a.match = match; a.miou = match_iou;
-    a.best = (u64*)workspace; a.claim = a.best + n_pred;
+    a.parea = pred_area; a.tarea = true_area; a.n_pred = n_pred; a.n_true = n_true; a.best = (u64*)workspace;
+    ap_fill_rules(a, pred_scores, pred_labels, pred_row, true_labels, true_row, iouv, n_iou, pair_iou, ignore, n_ignore, hit, live, match, match_iou,
+                  a.best + n_pred);
 
     hipStream_t st = (hipStream_t)stream;
     const int rows = n_pred > n_true ? n_pred : n_true;

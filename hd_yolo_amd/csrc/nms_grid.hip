@@ -63,7 +63,6 @@ struct Ws {
     size_t bytes;
 };
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 Ws carve(void* base, int M) {
     Ws w;
@@ -536,15 +535,6 @@ int scan_launch(const int* in, int n, int* bsum, int* out, hipStream_t st, const
     return HDY_OK;
 }
 
-#define HDY_HIP_OK(call, who)                                                          \
-    do {                                                                               \
-        hipError_t e__ = (call);                                                       \
-        if (e__ != hipSuccess) {                                                       \
-            hdy_set_error("%s: %s failed: %s", who, #call, hipGetErrorString(e__));    \
-            return (int)e__;                                                           \
-        }                                                                              \
-    } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -562,8 +552,8 @@ int hdy_nms_grid_begin(const float* boxes_scores, int M, void* workspace, size_t
     const Ws w = carve(workspace, M);
     hipStream_t st = (hipStream_t)stream;
     const char* who = "nms_grid_begin";
-    HDY_HIP_OK(hipMemsetAsync(w.hdr, 0, HDR_BYTES, st), who);
-    HDY_HIP_OK(hipMemsetAsync(w.counts, 0, (size_t)w.NB * 4, st), who);
+    HDY_CHECKED(hdy_memset_async(who, w.hdr, 0, HDR_BYTES, st));
+    HDY_CHECKED(hdy_memset_async(who, w.counts, 0, (size_t)w.NB * 4, st));
     hipLaunchKernelGGL(keys_kernel, dim3(min(cdiv(w.P2, 256), KEYS_BLOCKS)), dim3(256), 0, st, boxes_scores, M, w.P2, w.keys, w.hdr);
     hipLaunchKernelGGL(params_kernel, dim3(1), dim3(64), 0, st, w.hdr);
     const int P2 = w.P2, nblk = cdiv(P2, SORT_BLOCK);
@@ -581,7 +571,7 @@ int hdy_nms_grid_begin(const float* boxes_scores, int M, void* workspace, size_t
     HDY_LAUNCH_CHECK(who);
     const int rc = scan_launch<false>(w.counts, w.NB, w.bsum, w.start, st, who);
     if (rc) return rc;
-    HDY_HIP_OK(hipMemsetAsync(w.counts, 0, (size_t)w.NB * 4, st), who);
+    HDY_CHECKED(hdy_memset_async(who, w.counts, 0, (size_t)w.NB * 4, st));
     hipLaunchKernelGGL(scatter_kernel, dim3(gm), dim3(256), 0, st, M, (const int*)w.cellid, (const int*)w.start, w.counts, w.items);
     HDY_LAUNCH_CHECK(who);
     hdy_note_dispatch("nms_grid");

@@ -162,11 +162,7 @@ int hdy_paste_masks(const float* masks, int R, int M, int padding, const float* 
     Args a = make_args(masks, M, padding, boxes);
     a.x0 = 0; a.y0 = 0; a.w = W; a.h = H; a.out = out; a.thr = 0.f;
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(out, 0, (size_t)out_elems * 4, st);
-    if (e != hipSuccess) {
-        hdy_set_error("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
-        return (int)e;
-    }
+    HDY_CHECKED(hdy_memset_async(who, out, 0, (size_t)out_elems * 4, st));
     hipLaunchKernelGGL(paste_kernel<false>, dim3(R), dim3(THREADS), 0, st, a);
     HDY_LAUNCH_CHECK(who);
     hdy_note_dispatch("paste_dense");
@@ -187,11 +183,7 @@ int hdy_paste_label_map(const float* masks, int R, int M, int padding, const flo
     Args a = make_args(masks, M, padding, boxes);
     a.x0 = x0; a.y0 = y0; a.w = w; a.h = h; a.map = (unsigned*)map; a.thr = threshold;
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(map, 0xFF, (size_t)map_elems * 4, st);
-    if (e != hipSuccess) {
-        hdy_set_error("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
-        return (int)e;
-    }
+    HDY_CHECKED(hdy_memset_async(who, map, 0xFF, (size_t)map_elems * 4, st));
     if (R > 0) hipLaunchKernelGGL(paste_kernel<true>, dim3(R), dim3(THREADS), 0, st, a);
     HDY_LAUNCH_CHECK(who);
     hdy_note_dispatch("paste_label");
@@ -205,11 +197,7 @@ int hdy_label_areas(const int* map, long long map_elems, int* areas, int R, void
     HDY_ARG((((uintptr_t)map | (uintptr_t)areas) & 3) == 0, "%s: misaligned pointer", who);
     if (R == 0) return HDY_OK;
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(areas, 0, (size_t)R * 4, st);
-    if (e != hipSuccess) {
-        hdy_set_error("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
-        return (int)e;
-    }
+    HDY_CHECKED(hdy_memset_async(who, areas, 0, (size_t)R * 4, st));
     if (map_elems > 0) {
         const long long blocks = (map_elems + THREADS - 1) / THREADS;
         hipLaunchKernelGGL(areas_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(THREADS), 0, st, map, map_elems, areas, R);

@@ -53,8 +53,6 @@ struct Ws {
     size_t bytes;
 };
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 Ws carve(void* base, int B, int pcap, int tcap) {
     Ws w;
     w.max_blocks = cdiv(pcap, PRED_BLOCK) + B;
@@ -71,15 +69,11 @@ Ws carve(void* base, int B, int pcap, int tcap) {
     return w;
 }
 
-struct Args {
-    const float4* pb; const float* ps; const long long* pl; const int* poff; const int* prow;
-    const float4* tb; const long long* tl; const int* toff; const int* trow;
-    int pcap, tcap, B, tc, prune, n_iou, n_ign, max_blocks, max_chunks;
-    float pair_iou;
-    float iouv[16];
-    long long ign[4];
-    unsigned short* hit; unsigned char* live; int* match; float* miou;
-    Header* hdr; int *blk_off, *chk_off; float4* cbox; int* cflag; u64* claim;
+// the rule block, and where the box form's IoU comes from: boxes, spans, chunking and the workspace arrays
+struct Args : ApRules {
+    const float4 *pb, *tb; const int *poff, *toff;
+    int pcap, tcap, B, tc, prune, max_blocks, max_chunks;
+    Header* hdr; int *blk_off, *chk_off; float4* cbox; int* cflag;
 };
 
 // image i's rows [lo, lo + n) of an array of `cap` rows: offsets clamped, so that any content is memory-safe
@@ -105,8 +99,6 @@ __device__ __forceinline__ int image_of(const int* __restrict__ pre, int B, int 
 __device__ __forceinline__ bool finite4(const float4& b) {
     return fabsf(b.x) <= 3.4028234664e38f && fabsf(b.y) <= 3.4028234664e38f && fabsf(b.z) <= 3.4028234664e38f && fabsf(b.w) <= 3.4028234664e38f;
 }
-
-__device__ __forceinline__ bool ignored(const Args& a, long long label) { return ap_ignored(a.ign, a.n_ign, label); }
 
 // min / max of (x1, y1, x2, y2) and OR of a flag over the wave
 __device__ __forceinline__ void wave_box(float& x1, float& y1, float& x2, float& y2, int& flag) {
@@ -231,7 +223,7 @@ __global__ __launch_bounds__(PRED_BLOCK) void match_kernel(const Args a) {
     if (me.active) {
         b = a.pb[me.p];
         area = __fmul_rn(__fsub_rn(b.z, b.x), __fsub_rn(b.w, b.y));
-        p_ign = ignored(a, a.pl[me.p]);
+        p_ign = ap_ignored(a, a.pl[me.p]);
         if (finite4(b)) { x1 = b.x; y1 = b.y; x2 = b.z; y2 = b.w; }
         else bad = 1;
     }
@@ -279,8 +271,8 @@ __global__ __launch_bounds__(PRED_BLOCK) void match_kernel(const Args a) {
                     const float4 t = a.tb[g];
                     l_box[threadIdx.x] = t;
                     l_area[threadIdx.x] = __fmul_rn(__fsub_rn(t.z, t.x), __fsub_rn(t.w, t.y));
-                    l_row[threadIdx.x] = a.trow ? a.trow[g] : g;
-                    l_ign[threadIdx.x] = ignored(a, a.tl[g]) ? 1 : 0;
+                    l_row[threadIdx.x] = a.true_row(g);
+                    l_ign[threadIdx.x] = ap_ignored(a, a.tl[g]) ? 1 : 0;
                 }
                 __syncthreads();
                 if (!me.active) continue;
@@ -306,10 +298,7 @@ __global__ __launch_bounds__(PRED_BLOCK) void match_kernel(const Args a) {
         a.match[me.p] = best;
         a.miou[me.p] = best_iou;
         a.live[me.p] = touched ? 1 : 0;
-        if (best >= 0) {
-            const unsigned row = (unsigned)(a.prow ? a.prow[me.p] : me.p);
-            atomicMin(&a.claim[best], ap_claim_key(a.ps[me.p], row));
-        }
+        if (best >= 0) atomicMin(&a.claim[best], ap_claim_key(a.ps[me.p], (unsigned)a.pred_row(me.p)));
     }
     if (threadIdx.x == 0 && visited) atomicAdd(&a.hdr->visited, (u64)visited);
 }
@@ -318,9 +307,7 @@ __global__ __launch_bounds__(PRED_BLOCK) void match_kernel(const Args a) {
 __global__ __launch_bounds__(PRED_BLOCK) void resolve_kernel(const Args a) {
     if ((int)blockIdx.x >= a.blk_off[a.B]) return;
     const Mine me = locate(a);
-    if (!me.active) return;
-    const int p = me.p;
-    ap_resolve(p, (unsigned)(a.prow ? a.prow[p] : p), a.ps, a.pl, a.tl, a.claim, a.iouv, a.n_iou, a.hit, a.live, a.match, a.miou);
+    if (me.active) ap_resolve(a, me.p);
 }
 
 }  // namespace
@@ -341,17 +328,12 @@ int hdy_ap_match(const float* pred_boxes, const float* pred_scores, const long l
     HDY_ARG(n_img >= 0 && pred_capacity >= 0 && true_capacity >= 0, "%s: negative count (n_img=%d, pred_capacity=%d, true_capacity=%d)", who, n_img,
             pred_capacity, true_capacity);
     HDY_ARG(n_img <= HDY_AP_MAX_ROWS && pred_capacity <= HDY_AP_MAX_ROWS && true_capacity <= HDY_AP_MAX_ROWS, "%s: a count exceeds %d", who, HDY_AP_MAX_ROWS);
-    HDY_ARG(n_iou >= 1 && n_iou <= 16, "%s: n_iou=%d outside [1, 16]", who, n_iou);
-    HDY_ARG(n_ignore >= 0 && n_ignore <= 4, "%s: n_ignore=%d outside [0, 4]", who, n_ignore);
-    HDY_ARG(iouv && (ignore || n_ignore == 0), "%s: null threshold or ignore array (host pointers)", who);
-    HDY_ARG(pair_iou > 0.f && pair_iou <= 1.f, "%s: pair_iou must be in (0, 1]", who);
+    HDY_CHECKED(ap_check_rules(who, pred_capacity, true_capacity, pred_scores, pred_labels, pred_row, true_labels, true_row, iouv, n_iou, pair_iou,
+                               ignore, n_ignore, hit, live, match, match_iou));
     HDY_ARG(pred_off && true_off, "%s: null offset array", who);
-    HDY_ARG(pred_capacity == 0 || (pred_boxes && pred_scores && pred_labels && hit && live && match && match_iou), "%s: null prediction or output pointer", who);
-    HDY_ARG(true_capacity == 0 || (true_boxes && true_labels), "%s: null truth pointer", who);
+    HDY_ARG((pred_capacity == 0 || pred_boxes) && (true_capacity == 0 || true_boxes), "%s: null box pointer", who);
     HDY_ARG((((uintptr_t)pred_boxes | (uintptr_t)true_boxes) & 15) == 0, "%s: boxes must be 16-byte aligned", who);
-    HDY_ARG((((uintptr_t)pred_labels | (uintptr_t)true_labels) & 7) == 0, "%s: labels must be 8-byte aligned", who);
-    HDY_ARG((((uintptr_t)pred_scores | (uintptr_t)pred_off | (uintptr_t)true_off | (uintptr_t)pred_row | (uintptr_t)true_row | (uintptr_t)match |
-              (uintptr_t)match_iou) & 3) == 0 && ((uintptr_t)hit & 1) == 0, "%s: misaligned pointer", who);
+    HDY_ARG((((uintptr_t)pred_off | (uintptr_t)true_off) & 3) == 0, "%s: misaligned pointer", who);
     HDY_ARG(workspace && ws_bytes >= hdy_ap_match_workspace_bytes(n_img, pred_capacity, true_capacity), "%s: workspace too small", who);
     HDY_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
     const int tc = hdy_opt(HDY_OPT_AP_CHUNK);
@@ -359,25 +341,16 @@ int hdy_ap_match(const float* pred_boxes, const float* pred_scores, const long l
 
     const Ws w = carve(workspace, n_img, pred_capacity, true_capacity);
     Args a;
-    a.pb = (const float4*)pred_boxes; a.ps = pred_scores; a.pl = pred_labels; a.poff = pred_off; a.prow = pred_row;
-    a.tb = (const float4*)true_boxes; a.tl = true_labels; a.toff = true_off; a.trow = true_row;
+    ap_fill_rules(a, pred_scores, pred_labels, pred_row, true_labels, true_row, iouv, n_iou, pair_iou, ignore, n_ignore, hit, live, match, match_iou,
+                  w.claim);
+    a.pb = (const float4*)pred_boxes; a.poff = pred_off; a.tb = (const float4*)true_boxes; a.toff = true_off;
     a.pcap = pred_capacity; a.tcap = true_capacity; a.B = n_img; a.tc = tc ? tc : MAX_CHUNK; a.prune = hdy_opt(HDY_OPT_AP_NO_PRUNE) ? 0 : 1;
-    a.n_iou = n_iou; a.n_ign = n_ignore; a.pair_iou = pair_iou;
     a.max_blocks = w.max_blocks;                                   // = the match and resolve grids
     a.max_chunks = cdiv(true_capacity, a.tc) + n_img;              // = the chunk-box grid (<= the carved w.max_chunks)
-    for (int j = 0; j < 16; ++j) a.iouv[j] = j < n_iou ? iouv[j] : 2.f;
-    for (int j = 0; j < 4; ++j) a.ign[j] = j < n_ignore ? ignore[j] : 0;
-    a.hit = hit; a.live = live; a.match = match; a.miou = match_iou;
-    a.hdr = w.hdr; a.blk_off = w.blk_off; a.chk_off = w.chk_off; a.cbox = w.cbox; a.cflag = w.cflag; a.claim = w.claim;
+    a.hdr = w.hdr; a.blk_off = w.blk_off; a.chk_off = w.chk_off; a.cbox = w.cbox; a.cflag = w.cflag;
 
     hipStream_t st = (hipStream_t)stream;
-    if (true_capacity > 0) {
-        const hipError_t e = hipMemsetAsync(w.claim, 0xFF, (size_t)true_capacity * 8, st);
-        if (e != hipSuccess) {
-            hdy_set_error("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
-            return (int)e;
-        }
-    }
+    HDY_CHECKED(hdy_memset_async(who, w.claim, 0xFF, (size_t)true_capacity * 8, st));
     hipLaunchKernelGGL(setup_kernel, dim3(1), dim3(256), 0, st, a);
     if (true_capacity > 0 && n_img > 0) hipLaunchKernelGGL(chunk_box_kernel, dim3(a.max_chunks), dim3(64), 0, st, a);
     if (pred_capacity > 0 && n_img > 0) {

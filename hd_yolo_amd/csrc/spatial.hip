@@ -153,11 +153,7 @@ int hdy_spatial_cells(const int* pts, long long pts_elems, int N, int cell_units
     HDY_ARG((((uintptr_t)cell_start | (uintptr_t)status) & 3) == 0, "%s: misaligned pointer (cell_start, status 4 bytes)", who);
     if (N == 0) return HDY_OK;
     hipStream_t st = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(status, 0, sizeof(int), st);
-    if (e != hipSuccess) {
-        hdy_set_error("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
-        return (int)e;
-    }
+    HDY_CHECKED(hdy_memset_async(who, status, 0, sizeof(int), st));
     const Grid g = {cell_units, ncx, ncy, ncells};
     const long long items = (long long)ncells + 1 > N ? (long long)ncells + 1 : N;
     hipLaunchKernelGGL(cells_kernel, dim3((unsigned)((items + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, (const i32x4*)pts, N, g, cell_start, status);

@@ -350,8 +350,9 @@ class DeviceAPMeter:
     def __init__(self, labels_text={}, iouv=torch.linspace(0.5, 0.95, 10), ignore=(-100, -1)):
         self.iouv = np.asarray(iouv.tolist() if hasattr(iouv, 'tolist') else list(iouv), dtype=np.float32)
         self.ignore = tuple(int(v) for v in (ignore or ()))
-        if not 1 <= len(self.iouv) <= 16 or len(self.ignore) > 4:
-            raise ValueError('DeviceAPMeter: 1 to 16 IoU thresholds and at most 4 ignored labels')
+        from ... import ops
+        if not 1 <= len(self.iouv) <= ops.AP_MAX_IOU or len(self.ignore) > ops.AP_MAX_IGNORE:
+            raise ValueError(f'DeviceAPMeter: 1 to {ops.AP_MAX_IOU} IoU thresholds and at most {ops.AP_MAX_IGNORE} ignored labels')
         self.labels_text = labels_text
         self.reset()
 
@@ -365,9 +366,22 @@ class DeviceAPMeter:
             raise NotImplementedError('mask IoU: the reference calls get_mask_ious here (metrics.py:275), a function its metrics module neither defines nor imports')
         self.add_batch([output], [target])
 
+    @staticmethod
+    def _offsets(dicts, key, dev):
+        """int32 prefix offsets of the per-image rows under `key`, on the device (lengths are host values: an upload, no read)"""
+        return torch.tensor(np.concatenate(([0], np.cumsum([len(d[key]) for d in dicts]))), dtype=torch.int32, device=dev)
+
+    @staticmethod
+    def _cat(dicts, key, dev, dtype=torch.int64):
+        """the per-image tensors under `key` as one flat tensor of `dtype` on the device"""
+        return torch.cat([d[key].detach().reshape(-1).to(dtype) for d in dicts]).to(dev)
+
+    def _store(self, scores, labels, hit, live, pred_off, tlabels, true_off):
+        self._batches.append((scores, labels, hit, live, pred_off, tlabels, true_off))
+        self._host_cache = None
+
     def add_batch(self, outputs, targets, info=None):
         from ... import ops
-        i32 = lambda counts, dev: torch.tensor(np.concatenate(([0], np.cumsum(counts))), dtype=torch.int32, device=dev)   # noqa: E731
         if isinstance(outputs, tuple):
             boxes, scores, labels, n_keep = outputs[:4]          # (a fifth element: the batch's compact masks, not scored here)
             dev = boxes.device
@@ -380,17 +394,14 @@ class DeviceAPMeter:
                 raise ValueError('DeviceAPMeter: multi-label outputs must be flattened by the caller (val_nuclei.flatten_onehot_objects)')
             dev = outputs[0]['boxes'].device
             boxes = torch.cat([o['boxes'].detach().float().reshape(-1, 4) for o in outputs])
-            scores = torch.cat([o['scores'].detach().float().reshape(-1) for o in outputs])
-            labels = torch.cat([o['labels'].detach().reshape(-1).to(torch.int64) for o in outputs])
-            pred_off = i32([len(o['scores']) for o in outputs], dev)       # shapes are host values: an upload, no read
+            scores, labels = self._cat(outputs, 'scores', dev, torch.float32), self._cat(outputs, 'labels', dev)
+            pred_off = self._offsets(outputs, 'scores', dev)
         if len(targets) != pred_off.numel() - 1:
             raise ValueError(f'DeviceAPMeter: {pred_off.numel() - 1} images of predictions, {len(targets)} of truths')
         tboxes = torch.cat([t['boxes'].detach().float().reshape(-1, 4) for t in targets]).to(dev)
-        tlabels = torch.cat([t['labels'].detach().reshape(-1).to(torch.int64) for t in targets]).to(dev)
-        true_off = i32([len(t['labels']) for t in targets], dev)
+        tlabels, true_off = self._cat(targets, 'labels', dev), self._offsets(targets, 'labels', dev)
         hit, live, _, _ = ops.ap_match(boxes, scores, labels, pred_off, tboxes, tlabels, true_off, self.iouv, ignore=self.ignore, info=info)
-        self._batches.append((scores.detach().float().reshape(-1), labels.detach().reshape(-1).to(torch.int64), hit, live, pred_off, tlabels, true_off))
-        self._host_cache = None
+        self._store(scores.detach().float().reshape(-1), labels.detach().reshape(-1).to(torch.int64), hit, live, pred_off, tlabels, true_off)
 
     def add_batch_masks(self, outputs, targets, size, threshold=0.5, max_pairs=None):
         """A batch scored on mask IoU (ops.label_overlap + ops.mask_ap_match, csrc/mask_score.hip).  `outputs`: per-image dicts with 'boxes',
@@ -412,8 +423,7 @@ class DeviceAPMeter:
             raise ValueError('DeviceAPMeter: multi-label outputs must be flattened by the caller (val_nuclei.flatten_onehot_objects)')
         H, W = int(size[0]), int(size[1])
         dev = outputs[0]['scores'].device
-        i32 = lambda counts: torch.tensor(np.concatenate(([0], np.cumsum(counts))), dtype=torch.int32, device=dev)   # noqa: E731
-        pred_off, true_off = i32([len(o['scores']) for o in outputs]), i32([len(t['labels']) for t in targets])
+        pred_off, true_off = self._offsets(outputs, 'scores', dev), self._offsets(targets, 'labels', dev)
         n_true = int(sum(len(t['labels']) for t in targets))
         pred_map = torch.empty((len(outputs), H, W), dtype=torch.int32, device=dev)
         true_map = torch.empty((len(outputs), H, W), dtype=torch.int32, device=dev)
@@ -423,13 +433,10 @@ class DeviceAPMeter:
             if tuple(inst.shape) != (H, W):
                 raise ValueError(f"DeviceAPMeter: 'instances' of image {i} is {tuple(inst.shape)}, the canvas {(H, W)}")
             true_map[i] = ops._label_map_i32('add_batch_masks', inst.to(dev), 'instances', n_true)
-        scores = torch.cat([o['scores'].detach().float().reshape(-1) for o in outputs])
-        labels = torch.cat([o['labels'].detach().reshape(-1).to(torch.int64) for o in outputs])
-        tlabels = torch.cat([t['labels'].detach().reshape(-1).to(torch.int64) for t in targets]).to(dev)
+        scores, labels, tlabels = self._cat(outputs, 'scores', dev, torch.float32), self._cat(outputs, 'labels', dev), self._cat(targets, 'labels', dev)
         pairs, pa, ta = ops.label_overlap(pred_map, true_map, scores.numel(), tlabels.numel(), seg=(pred_off[:-1], true_off[:-1]), max_pairs=max_pairs)
         hit, live, _, _ = ops.mask_ap_match(pairs, pa, ta, scores, labels, tlabels, self.iouv, ignore=self.ignore)
-        self._batches.append((scores, labels, hit, live, pred_off, tlabels, true_off))
-        self._host_cache = None
+        self._store(scores, labels, hit, live, pred_off, tlabels, true_off)
         counts = segmentation_counts(pairs, pa, ta)                  # rows of different images share no pair: the batch is one pooled image
         self._seg = counts if self._seg is None else {k: self._seg[k] + v for k, v in counts.items()}
 

@@ -68,6 +68,11 @@ def _nbytes(t):
     return 0 if t is None else t.numel() * t.element_size()
 
 
+def _workspace(nbytes, dev):
+    """a 16-byte aligned workspace of at least nbytes (a sizing query's answer), as int64 words"""
+    return torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+
+
 def stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
@@ -953,7 +958,7 @@ def nms_batched(preds, nc, conf_thres, iou_thres, max_det, min_wh=2.0, class_awa
     conf = torch.empty((B, max_det), dtype=torch.float32, device=dev)
     cls = torch.empty((B, max_det), dtype=torch.int32, device=dev)
     wsb = _lib.query('hdy_nms_workspace_bytes_for', B, N, int(max_det))
-    ws = torch.empty(((wsb + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    ws = _workspace(wsb, dev)
     _lib.call('hdy_nms_batched', preds.data_ptr(), B, N, row, nc, float(conf_thres), float(iou_thres), int(max_det), float(min_wh),
               int(class_aware), keep.data_ptr(), n_keep.data_ptr(), boxes.data_ptr(), scores.data_ptr(),
               extra.data_ptr() if nex > 0 else None, conf.data_ptr(), cls.data_ptr(), ws.data_ptr(), ws.numel() * 8, stream_ptr())
@@ -984,7 +989,7 @@ def _nms_launch(boxes, scores, iou_thres, max_det):
     keep = torch.empty((1, max_det), dtype=torch.int64, device=boxes.device)
     n_keep = torch.empty((1,), dtype=torch.int32, device=boxes.device)
     wsb = _lib.query('hdy_nms_workspace_bytes_for', 1, N, int(max_det))
-    ws = torch.empty(((wsb + 15) // 16 * 2,), dtype=torch.int64, device=boxes.device)
+    ws = _workspace(wsb, boxes.device)
     _lib.call('hdy_nms_boxes', bs.data_ptr(), 1, N, float(iou_thres), int(max_det), keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(),
               ws.numel() * 8, stream_ptr())
     return keep[0, :int(n_keep.item())]
@@ -1013,7 +1018,7 @@ def _nms_grid_launch(boxes, scores, iou_thres, max_det, info=None):
     keep = torch.empty((max_det,), dtype=torch.int64, device=dev)
     stat = torch.empty((4,), dtype=torch.int32, device=dev)          # n_keep, then status[3] = undecided, non-finite flag, rounds
     wsb = _lib.query('hdy_nms_grid_workspace_bytes', N)
-    ws = torch.empty(((wsb + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+    ws = _workspace(wsb, dev)
     st = stream_ptr()
     _lib.call('hdy_nms_grid_begin', bs.data_ptr(), N, ws.data_ptr(), ws.numel() * 8, st)
     done, batch = 0, NMS_GRID_FIRST_ROUNDS
@@ -1066,7 +1071,7 @@ def nms(boxes, scores, iou_thres, max_det=None):
 
 # ------------------------------------------------------------------------------------------ detection scoring (csrc/score.hip)
 AP_PRED_BLOCK, AP_TRUE_CHUNK = _lib.CONSTANTS['HDY_AP_PRED_BLOCK'], _lib.CONSTANTS['HDY_AP_TRUE_CHUNK']      # predictions per workgroup, truths per chunk
-AP_MAX_IOU, AP_MAX_IGNORE = 16, 4
+AP_MAX_IOU, AP_MAX_IGNORE = 16, 4                  # thresholds and ignored labels of one call (csrc/ap_common.h)
 
 
 def _i32(t, name, who='ap_match'):
@@ -1078,6 +1083,34 @@ def _i32(t, name, who='ap_match'):
     return t.contiguous()
 
 
+def _ap_rules(iouv, ignore):
+    """(thresholds, their count, ignored labels, their count) as the host arrays the two matchers read"""
+    thr = [float(v) for v in (iouv.tolist() if hasattr(iouv, 'tolist') else iouv)]
+    ign = [int(v) for v in (ignore or ())]
+    return (ctypes.c_float * max(1, len(thr)))(*thr), len(thr), (ctypes.c_longlong * max(1, len(ign)))(*ign), len(ign)
+
+
+def _ap_rows(pred_scores, pred_labels, true_labels):
+    """(fp32 scores, int64 prediction labels, int64 truth labels), flat and contiguous on the scores' device"""
+    require_gpu(pred_scores)
+    ps = pred_scores.detach().float().reshape(-1).contiguous()
+    flat = lambda t: t.detach().reshape(-1).to(torch.int64).contiguous().to(ps.device)   # noqa: E731
+    return ps, flat(pred_labels), flat(true_labels)
+
+
+def _ap_tie_rows(who, pred_row, true_row, NP, NT):
+    """the optional int32 rows of the tie rules, one entry per prediction / truth"""
+    pred_row, true_row = _i32(pred_row, 'pred_row', who), _i32(true_row, 'true_row', who)
+    if (pred_row is not None and pred_row.numel() != NP) or (true_row is not None and true_row.numel() != NT):
+        raise _lib.HdyError(f'{who}: pred_row / true_row must have one entry per row')
+    return pred_row, true_row
+
+
+def _ap_outputs(NP, dev):
+    """hit (16 threshold bits; torch has no unsigned 16-bit arithmetic), live, match, match_iou: one entry per prediction"""
+    return tuple(torch.empty((NP,), dtype=dt, device=dev) for dt in (torch.int16, torch.uint8, torch.int32, torch.float32))
+
+
 def ap_match(pred_boxes, pred_scores, pred_labels, pred_off, true_boxes, true_labels, true_off, iouv, ignore=(-100, -1), pair_iou=0.5,
              pred_row=None, true_row=None, info=None):
     """The matching of APMeter (metayolo/models/metrics.py) for a ragged batch, on the device (hdy_ap_match): image i owns prediction rows
@@ -1086,42 +1119,32 @@ def ap_match(pred_boxes, pred_scores, pred_labels, pred_off, true_boxes, true_la
     (int32 truth row or -1) and match_iou (fp32), one entry per prediction row.  Equal scores inside an image rank lower row first; pred_row /
     true_row (int32) replace the position in both tie rules, so permuted inputs give the permuted results.  No host synchronisation; `info` (a
     dict) receives chunks_visited / chunks_total / workspace_bytes at the price of one read."""
+    who = 'ap_match'
     require_gpu(pred_boxes)
     dev = pred_boxes.device
     pb = pred_boxes.detach().float().reshape(-1, 4).contiguous()
-    ps = pred_scores.detach().float().reshape(-1).contiguous()
-    pl = pred_labels.detach().reshape(-1).to(torch.int64).contiguous()
     tb = true_boxes.detach().float().reshape(-1, 4).contiguous()
-    tl = true_labels.detach().reshape(-1).to(torch.int64).contiguous()
+    ps, pl, tl = _ap_rows(pred_scores, pred_labels, true_labels)
     NP, NT = pb.shape[0], tb.shape[0]
     if not (ps.numel() == NP == pl.numel() and tl.numel() == NT):
-        raise _lib.HdyError('ap_match: boxes, scores and labels disagree in length')
+        raise _lib.HdyError(f'{who}: boxes, scores and labels disagree in length')
     pred_off, true_off = _i32(pred_off, 'pred_off'), _i32(true_off, 'true_off')
     B = pred_off.numel() - 1
     if B < 0 or true_off.numel() != B + 1:
-        raise _lib.HdyError('ap_match: pred_off and true_off must both hold B + 1 entries')
-    pred_row, true_row = _i32(pred_row, 'pred_row'), _i32(true_row, 'true_row')
-    if (pred_row is not None and pred_row.numel() != NP) or (true_row is not None and true_row.numel() != NT):
-        raise _lib.HdyError('ap_match: pred_row / true_row must have one entry per row')
-    thr = [float(v) for v in (iouv.tolist() if hasattr(iouv, 'tolist') else iouv)]
-    ign = [int(v) for v in (ignore or ())]
-    c_thr = (ctypes.c_float * max(1, len(thr)))(*thr)
-    c_ign = (ctypes.c_longlong * max(1, len(ign)))(*ign)
-    hit = torch.empty((NP,), dtype=torch.int16, device=dev)          # 16 threshold bits (torch has no unsigned 16-bit arithmetic)
-    live = torch.empty((NP,), dtype=torch.uint8, device=dev)
-    match = torch.empty((NP,), dtype=torch.int32, device=dev)
-    miou = torch.empty((NP,), dtype=torch.float32, device=dev)
+        raise _lib.HdyError(f'{who}: pred_off and true_off must both hold B + 1 entries')
+    pred_row, true_row = _ap_tie_rows(who, pred_row, true_row, NP, NT)
     wsb = _lib.query('hdy_ap_match_workspace_bytes', B, NP, NT)
     if wsb == 0:
-        raise _lib.HdyError(f'ap_match: counts out of range (B={B}, predictions={NP}, truths={NT})')
-    ws = torch.empty(((wsb + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+        raise _lib.HdyError(f'{who}: counts out of range (B={B}, predictions={NP}, truths={NT})')
+    out, ws = _ap_outputs(NP, dev), _workspace(wsb, dev)
+    c_thr, n_thr, c_ign, n_ign = _ap_rules(iouv, ignore)
     _lib.call('hdy_ap_match', pb.data_ptr(), ps.data_ptr(), pl.data_ptr(), pred_off.data_ptr(), ptr(pred_row), NP, tb.data_ptr(), tl.data_ptr(),
-              true_off.data_ptr(), ptr(true_row), NT, B, c_thr, len(thr), float(pair_iou), c_ign, len(ign), hit.data_ptr(), live.data_ptr(),
-              match.data_ptr(), miou.data_ptr(), ws.data_ptr(), ws.numel() * 8, stream_ptr())
+              true_off.data_ptr(), ptr(true_row), NT, B, c_thr, n_thr, float(pair_iou), c_ign, n_ign, *(t.data_ptr() for t in out), ws.data_ptr(),
+              _nbytes(ws), stream_ptr())
     if info is not None:
         visited, total = ws[:2].tolist()
         info.update(chunks_visited=visited, chunks_total=total, workspace_bytes=wsb)
-    return hit, live, match, miou
+    return out
 
 
 # ------------------------------------------------------------------------------------------ mask paste (csrc/paste.hip)
@@ -1610,18 +1633,12 @@ def mask_ap_match(pairs, pred_area, true_area, pred_scores, pred_labels, true_la
     are no offsets).  IoU = float(inter) / float(area_p + area_t - inter).  Returns hit (16 threshold bits in an int16), live (uint8), match
     (int32 truth row or -1) and match_iou (fp32), one entry per prediction.  No host synchronisation."""
     who = 'mask_ap_match'
-    require_gpu(pred_scores)
-    dev = pred_scores.device
-    ps = pred_scores.detach().float().reshape(-1).contiguous()
-    pl = pred_labels.detach().reshape(-1).to(torch.int64).contiguous()
-    tl = true_labels.detach().reshape(-1).to(torch.int64).contiguous().to(dev)
-    NP, NT = ps.numel(), tl.numel()
+    ps, pl, tl = _ap_rows(pred_scores, pred_labels, true_labels)
+    dev, NP, NT = ps.device, ps.numel(), tl.numel()
     pa, ta = _i32(pred_area, 'pred_area', who), _i32(true_area, 'true_area', who)
     if not (pl.numel() == NP == pa.numel() and ta.numel() == NT):
         raise _lib.HdyError(f'{who}: scores, labels and areas disagree in length')
-    pred_row, true_row = _i32(pred_row, 'pred_row', who), _i32(true_row, 'true_row', who)
-    if (pred_row is not None and pred_row.numel() != NP) or (true_row is not None and true_row.numel() != NT):
-        raise _lib.HdyError(f'{who}: pred_row / true_row must have one entry per row')
+    pred_row, true_row = _ap_tie_rows(who, pred_row, true_row, NP, NT)
     require_gpu(pairs)
     if pairs.dim() != 2 or pairs.shape[1] != 3 or pairs.dtype != torch.int64:
         raise _lib.HdyError(f'{who}: pairs must be an (n, 3) int64 tensor, got {pairs.dtype} {tuple(pairs.shape)}')
@@ -1632,21 +1649,12 @@ def mask_ap_match(pairs, pred_area, true_area, pred_scores, pred_labels, true_la
     keys[n:] = -1
     counts[:n] = pairs[:, 2].to(torch.int32)
     counts[n:] = 0
-    thr = [float(v) for v in (iouv.tolist() if hasattr(iouv, 'tolist') else iouv)]
-    ign = [int(v) for v in (ignore or ())]
-    c_thr = (ctypes.c_float * max(1, len(thr)))(*thr)
-    c_ign = (ctypes.c_longlong * max(1, len(ign)))(*ign)
-    hit = torch.empty((NP,), dtype=torch.int16, device=dev)
-    live = torch.empty((NP,), dtype=torch.uint8, device=dev)
-    match = torch.empty((NP,), dtype=torch.int32, device=dev)
-    miou = torch.empty((NP,), dtype=torch.float32, device=dev)
-    wsb = _lib.query('hdy_mask_ap_match_workspace_bytes', NP, NT)
-    ws = torch.empty(((wsb + 15) // 16 * 2,), dtype=torch.int64, device=dev)
-    _lib.call('hdy_mask_ap_match', buf.data_ptr(), _nbytes(buf), slots, ptr(pa) if NP else None, ptr(ta) if NT else None, ptr(ps) if NP else None,
-              ptr(pl) if NP else None, ptr(pred_row), NP, ptr(tl) if NT else None, ptr(true_row), NT, c_thr, len(thr), float(pair_iou), c_ign,
-              len(ign), ptr(hit) if NP else None, ptr(live) if NP else None, ptr(match) if NP else None, ptr(miou) if NP else None, ws.data_ptr(),
-              _nbytes(ws), stream_ptr())
-    return hit, live, match, miou
+    out, ws = _ap_outputs(NP, dev), _workspace(_lib.query('hdy_mask_ap_match_workspace_bytes', NP, NT), dev)
+    p = lambda t: ptr(t) if t.numel() else None                     # noqa: E731  (no rows: a null pointer)
+    c_thr, n_thr, c_ign, n_ign = _ap_rules(iouv, ignore)
+    _lib.call('hdy_mask_ap_match', buf.data_ptr(), _nbytes(buf), slots, p(pa), p(ta), p(ps), p(pl), ptr(pred_row), NP, p(tl), ptr(true_row), NT, c_thr,
+              n_thr, float(pair_iou), c_ign, n_ign, *(p(t) for t in out), ws.data_ptr(), _nbytes(ws), stream_ptr())
+    return out
 
 
 # ------------------------------------------------------------------------------------------ mask branch primitives (row f2)

@@ -190,6 +190,52 @@ def test_label_overlap_argument_checks(lib):
     assert call(pm=FAKE + 2)[0] == _lib.EINVAL and call(table=FAKE + 8)[0] == _lib.EINVAL
 
 
+RULES = dict(ps=FAKE, pl=FAKE, tl=FAKE, n_iou=10, pair_iou=0.5, n_ign=2, hit=FAKE, live=FAKE, match=FAKE, miou=FAKE)
+
+
+def _rule_arrays(a):
+    a.setdefault('iouv', (ctypes.c_float * 17)(*np.linspace(0.5, 0.95, 17).tolist()))
+    a.setdefault('ignore', (ctypes.c_longlong * 5)(-100, -1, 7, 8, 9))
+    return a
+
+
+def _box_rules(lib, **kw):
+    a = _rule_arrays(dict(RULES, **kw))
+    rc = lib.hdy_ap_match(FAKE, a['ps'], a['pl'], FAKE, None, 40, FAKE, a['tl'], FAKE, None, 35, 2, a['iouv'], a['n_iou'], a['pair_iou'], a['ignore'],
+                          a['n_ign'], a['hit'], a['live'], a['match'], a['miou'], FAKE, lib.hdy_ap_match_workspace_bytes(2, 40, 35), None)
+    return rc, lib.hdy_last_error()
+
+
+def _mask_rules(lib, **kw):
+    a = _rule_arrays(dict(RULES, **kw))
+    rc = lib.hdy_mask_ap_match(FAKE, lib.hdy_label_overlap_workspace_bytes(256), 256, FAKE, FAKE, a['ps'], a['pl'], None, 40, a['tl'], None, 35, a['iouv'],
+                               a['n_iou'], a['pair_iou'], a['ignore'], a['n_ign'], a['hit'], a['live'], a['match'], a['miou'], FAKE,
+                               lib.hdy_mask_ap_match_workspace_bytes(40, 35), None)
+    return rc, lib.hdy_last_error()
+
+
+@pytest.mark.parametrize('call', [_box_rules, _mask_rules], ids=['ap_match', 'mask_ap_match'])
+def test_the_rule_checks_both_matchers_share(lib, call):
+    """the checks of csrc/ap_common.h (ap_check_rules), through hdy_ap_match and hdy_mask_ap_match: the same invalid rule block is refused by
+    both with the same words, before any launch"""
+    lib.hdy_dispatch_log_reset()
+    for name in ('iouv', 'ignore', 'hit', 'live', 'match', 'miou', 'ps', 'pl'):
+        rc, msg = call(lib, **{name: None})
+        assert rc == _lib.EINVAL and b'null' in msg, name
+    for n in (0, 17, -1):
+        rc, msg = call(lib, n_iou=n)
+        assert rc == _lib.EINVAL and b'n_iou=' in msg and b'[1, 16]' in msg, n
+    rc, msg = call(lib, n_ign=5)
+    assert rc == _lib.EINVAL and b'n_ignore=5' in msg
+    for v in (0.0, 1.5, float('nan')):
+        rc, msg = call(lib, pair_iou=v)
+        assert rc == _lib.EINVAL and b'pair_iou' in msg, v
+    for kw in ({'pl': FAKE + 4}, {'hit': FAKE + 1}):
+        rc, msg = call(lib, **kw)
+        assert rc == _lib.EINVAL and b'aligned' in msg, kw
+    assert _lib.dispatch_log() == []
+
+
 def test_mask_ap_match_argument_checks(lib):
     thr = (ctypes.c_float * 17)(*np.linspace(0.5, 0.95, 17).tolist())
     ign = (ctypes.c_longlong * 5)(-100, -1, 7, 8, 9)
