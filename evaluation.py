@@ -152,7 +152,7 @@ def _check_slide(slide):
 
 @torch.no_grad()
 def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=1.0, iou_thres=None, compute_masks=False, min_tissue=0.0,
-                       background=220, label_map=False, measure=False, neighbors=None, outlines=False, graph=None):
+                       background=220, label_map=False, measure=False, neighbors=None, outlines=False, graph=None, stain_normalize=None, info=None):
     """Whole-slide detection as the reference's ROI protocol composes it: tiles of one amplification are run in batches, each tile's
     detections carry their 'roi' offset, `Detect.merge_outputs` shifts and concatenates them (yolo_head.py:450-462), overlapping
     windows are de-duplicated by one class-agnostic NMS on the MI355X kernel (as Ensemble.merge does, yolo.py:189-199), and
@@ -181,8 +181,20 @@ def inference_on_slide(model, slide, tile=640, overlap=64, batch_size=32, scale=
     (offsets, verts), the outline of every nucleus as a polygon in the returned coordinates.  False launches nothing new.
     graph=(k, max_px) (with measure): the task gains 'graph', the cell graph of slide_cell_graph: every nucleus joined to its k <= 16 nearest
     nuclei of the header's classes within max_px pixels of the returned coordinates, with the union edge list.  'nuclei' keeps its columns.
-    None launches nothing new."""
+    None launches nothing new.
+    stain_normalize (8-bit slides only; not in the reference): True estimates the slide's stain vectors from every 4th pixel
+    (hd_yolo_amd/stain.py: estimate_stains(slide, step=4), Macenko's method on integer device counts) and recolours the slide to the default
+    StainTarget into a new slide before the tile gather; a StainEstimate is used as given.  Everything downstream, the measured stain
+    columns included, sees the normalised slide.  `info`, a dict, receives the estimate as 'stain_estimate'.  None does not touch the path."""
     u8 = _check_slide(slide)
+    if stain_normalize is not None and stain_normalize is not False:
+        if not u8:
+            raise ValueError('inference_on_slide: stain_normalize applies to 8-bit slides (the stain model is defined on 8-bit RGB values)')
+        from hd_yolo_amd import stain as hstain
+        estimate = hstain.estimate_stains(slide, step=4) if stain_normalize is True else stain_normalize
+        slide = hstain.normalize_slide(slide, estimate)
+        if info is not None:
+            info['stain_estimate'] = estimate
     if measure and not label_map:
         raise ValueError('inference_on_slide: measure=True needs label_map=True (the nuclei are measured on the label map)')
     if neighbors is not None and not measure:
@@ -328,19 +340,20 @@ def slide_nucleus_outlines(result, window=None):
 
 
 @torch.no_grad()
-def slide_nucleus_texture(result, slide, window=None, stain='hematoxylin', levels=16):
+def slide_nucleus_texture(result, slide, window=None, stain='hematoxylin', levels=16, matrix=None):
     """One task's result with its 'label_map' and 'nuclei' (slide_nucleus_table) and the 8-bit `slide` the map was drawn on ((H, W, 3 | 4)
     uint8) -> the texture columns of hd_yolo_amd/texture.py's texture_table, float64 device tensors with one row per detection: the
     statistics of the nucleus's levels of `stain` ('tex_level_mean', '_std', '_skewness', '_kurtosis', '_entropy', '_min', '_median', '_max'),
     the mean and the range over four directions of the 13 Haralick features of its co-occurrence matrices ('tex_contrast_mean',
     'tex_contrast_range', ...) and 'tex_flags'.  stain: 'hematoxylin', 'eosin', 'residual' (colour deconvolution), 'gray', 'r', 'g', 'b'; levels
-    8, 16 or 32.  The extents are the table's 'bbox': nothing is measured again.  window = (x0, y0, w, h): the part of the slide the map
+    8, 16 or 32; matrix: the stain matrix of the deconvolution (None: Ruifrok-Johnston; hd_yolo_amd.stain.estimate_stains(slide).matrix: the
+    slide's own).  The extents are the table's 'bbox': nothing is measured again.  window = (x0, y0, w, h): the part of the slide the map
     holds, as it was given to slide_nucleus_table.  One pass per 16 384 nuclei (ops.label_texture); nothing is read back."""
     from hd_yolo_amd import texture as htexture
     lm, _, R, extent, x0, y0 = _map_and_extents('slide_nucleus_texture', result, window)
     if slide is None or slide.dtype != torch.uint8:
         raise ValueError('slide_nucleus_texture: the texture is that of the 8-bit slide under the map ((H, W, 3 | 4) uint8)')
-    return htexture.texture_table(lm, R, extent, slide, window=(x0, y0), stain=stain, levels=levels)
+    return htexture.texture_table(lm, R, extent, slide, window=(x0, y0), stain=stain, levels=levels, matrix=matrix)
 
 
 @torch.no_grad()
@@ -601,6 +614,8 @@ def main():
     ap.add_argument('--polygons', default='', help='--outlines: write the polygons to this .geojson or .npz file (save_polygons)')
     ap.add_argument('--graph', default='', help='--measure: K,PX, e.g. 8,64: join every nucleus to its K <= 16 nearest nuclei within PX pixels (slide_cell_graph)')
     ap.add_argument('--texture', nargs='?', const='hematoxylin', default='', metavar='STAIN', help='--measure --u8: chromatin texture of every nucleus on this stain (hematoxylin, eosin, residual, gray, r, g, b): level statistics and Haralick features as tex_* columns of the table (slide_nucleus_texture)')
+    ap.add_argument('--stain-normalize', action='store_true', help='--slide --u8: estimate the stain vectors of the slide (hd_yolo_amd/stain.py, Macenko on every 4th pixel), print them, and run the slide normalised to the default target (inference_on_slide(stain_normalize=...))')
+    ap.add_argument('--stain-estimate', action='store_true', help='--slide --u8: estimate and print the stain vectors only; with --texture the tex_* columns are measured with the slide\'s own stain matrix')
     ap.add_argument('--graph-file', default='', help='--graph: write the cell graph to this .npz file (save_cell_graph)')
     ap.add_argument('--no-half', action='store_true')
     ap.add_argument('--device', default='')
@@ -625,9 +640,26 @@ def main():
         slide = synth.synth_images(1, opt.slide, seed=5)[0].to(device)
         if opt.u8:
             slide = (slide * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous()
+        est = None
+        if opt.stain_normalize or opt.stain_estimate:
+            if not opt.u8:
+                ap.error('--stain-normalize and --stain-estimate need --u8')
+            from hd_yolo_amd import stain as hstain
+            from hd_yolo_amd import texture as htexture
+            hstain.estimate_stains(slide, step=4)                             # warm-up
+            torch.cuda.synchronize()
+            t0 = time.time()
+            est = hstain.estimate_stains(slide, step=4)
+            torch.cuda.synchronize()
+            dte = (time.time() - t0) * 1e3
+            vec = lambda v: '(' + ', '.join(f'{float(c):.4f}' for c in v) + ')'      # noqa: E731
+            off = [hstain.angle_between(est.matrix[i], htexture.stain_matrix()[i]) for i in range(2)]
+            print(f'stain {opt.slide}x{opt.slide}: n_tissue {est.n_tissue} ({est.n_skipped} skipped, flags {est.flags}), haematoxylin {vec(est.matrix[0])} '
+                  f'{off[0]:.2f} deg from Ruifrok, eosin {vec(est.matrix[1])} {off[1]:.2f} deg from Ruifrok, max_conc {vec(est.max_conc)} in {dte:.1f} ms')
+        normalize = est if opt.stain_normalize else None
         torch.cuda.synchronize()
         t0 = time.time()
-        out = inference_on_slide(deployed.to(device), slide, tile=opt.imgsz, batch_size=opt.batch_size, min_tissue=opt.min_tissue)
+        out = inference_on_slide(deployed.to(device), slide, tile=opt.imgsz, batch_size=opt.batch_size, min_tissue=opt.min_tissue, stain_normalize=normalize)
         torch.cuda.synchronize()
         print(f'slide {opt.slide}x{opt.slide}: ' + ', '.join(f'{k}: {len(v["boxes"])} detections' for k, v in out.items()) + f' in {(time.time() - t0) * 1e3:.1f} ms')
         if opt.label_map and not opt.masks:
@@ -662,7 +694,7 @@ def main():
             mm.load_state_dict(synth.mask_state_dict(mm), strict=False)
             mdep = Deploy(mm.to(device).eval())
             kw = dict(tile=min(opt.imgsz, opt.slide), batch_size=opt.batch_size, compute_masks=True, label_map=opt.label_map, measure=opt.measure,
-                      neighbors=radii, outlines=opt.outlines, graph=knn)
+                      neighbors=radii, outlines=opt.outlines, graph=knn, stain_normalize=normalize)
             inference_on_slide(mdep, slide, **kw)                         # warm-up: plans
             torch.cuda.synchronize()
             t0 = time.time()
@@ -734,7 +766,7 @@ def main():
                     if opt.texture:
                         torch.cuda.synchronize()
                         t0 = time.time()
-                        tx = slide_nucleus_texture(v, slide, stain=opt.texture)
+                        tx = slide_nucleus_texture(v, slide, stain=opt.texture, matrix=est.matrix if est is not None else None)
                         torch.cuda.synchronize()
                         dtt = (time.time() - t0) * 1e3
                         held = ~torch.isnan(tx['tex_contrast_mean'])

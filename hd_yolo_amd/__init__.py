@@ -1,6 +1,6 @@
 """hd_yolo_amd — MI355X-native (gfx950) implementation of hd_yolo's metayolo detection hot path.
 
-Layout: csrc/ (HIP kernels + C ABI, include/hdyolo.h), _header.py / _lib.py / ops.py (the ctypes binding read from that header, launch records), _ext.py (the binding of the extension headers include/hdyolo_<name>.h, name in _header.EXTENSION_NAMES), measure.py (the nucleus table), spatial.py (neighbourhoods), outline.py (shape columns, polygon files), graph.py (the cell graph: k nearest neighbours, edge lists, node features), texture.py (stain levels, co-occurrence features), plan.py /
+Layout: csrc/ (HIP kernels + C ABI, include/hdyolo.h), _header.py / _lib.py / ops.py (the ctypes binding read from that header, launch records), _ext.py (the binding of the extension headers include/hdyolo_<name>.h, name in _header.EXTENSION_NAMES), measure.py (the nucleus table), spatial.py (neighbourhoods), outline.py (shape columns, polygon files), graph.py (the cell graph: k nearest neighbours, edge lists, node features), texture.py (stain levels, co-occurrence features), stain.py (stain estimation and normalisation of 8-bit slides; include/hdyolo_stain.h, name in _header.PIXEL_EXTENSION_NAMES), plan.py /
 engine.py (static forward/backward launch lists, gradient store, autograd hook-in), parallel.py (RCCL data parallel),
 metayolo/ (the reference's module surface).  There is no CPU execution path: the CPU oracle lives in /oracle (tests only).
 """

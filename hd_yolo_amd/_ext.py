@@ -1,13 +1,14 @@
 """ctypes binding of the extension headers of libhdyolo_hip.so (include/hdyolo_<name>.h for every name of _header.EXTENSION_NAMES: measure,
-spatial, outline, graph, texture).
+spatial, outline, graph, texture; and of _header.PIXEL_EXTENSION_NAMES: stain).
 
 include/hdyolo.h is the numbered ABI and _lib.py its binding; an extension header declares further entry points of the same library under a
 revision of its own, read by the same reader (_header.read(path)) and bound here on the handle _lib.load() returns.  _lib.SIGNATURES,
 _lib.CONSTANTS and HDY_ABI_VERSION know nothing of them.  No CPU fallback: a library without the symbols, or of another revision, raises.
 
 EXTENSIONS maps an extension's short name to its tables; SIGNATURES, PARAMS and CONSTANTS are their unions.  A name belongs to one header:
-the import fails when two of them, or one of them and include/hdyolo.h, declare the same function or constant.  A new header is one more
-name in _header.EXTENSION_NAMES.
+the import fails when two of them, or one of them and include/hdyolo.h, declare the same function or constant.  PIXEL_EXTENSIONS,
+PIXEL_SIGNATURES, PIXEL_PARAMS and PIXEL_CONSTANTS are the same tables for the headers of _header.PIXEL_EXTENSION_NAMES; load() binds both
+and the names are disjoint over both.
 """
 import os
 from collections import namedtuple
@@ -18,11 +19,20 @@ from ._header import HdyError
 # functions, params, constants: as _header.Header's; revision_fn returns the library's revision, revision_macro states the one bound here
 Extension = namedtuple('Extension', 'header functions params constants revision_fn revision revision_macro')
 
-EXTENSIONS = {}
-for _name, _macro in ((n, f'HDY_{n.upper()}_REVISION') for n in _header.EXTENSION_NAMES):
-    _path = _header.extension_header(_name)
-    _h = _header.read(_path)
-    EXTENSIONS[_name] = Extension(_path, _h.functions, _h.params, _h.constants, f'hdy_{_name}_revision', _h.constants[_macro], _macro)
+
+
+def _table(names):
+    """{short name: Extension} of the headers of `names`, in that order"""
+    table = {}
+    for name in names:
+        path, macro = _header.extension_header(name), f'HDY_{name.upper()}_REVISION'
+        h = _header.read(path)
+        table[name] = Extension(path, h.functions, h.params, h.constants, f'hdy_{name}_revision', h.constants[macro], macro)
+    return table
+
+
+EXTENSIONS = _table(_header.EXTENSION_NAMES)
+PIXEL_EXTENSIONS = _table(_header.PIXEL_EXTENSION_NAMES)      # why a second table: _header.PIXEL_EXTENSION_NAMES
 
 
 def check_disjoint(extensions):
@@ -36,9 +46,13 @@ def check_disjoint(extensions):
 
 
 check_disjoint(EXTENSIONS)
+check_disjoint({**EXTENSIONS, **PIXEL_EXTENSIONS})
 SIGNATURES = {n: v for e in EXTENSIONS.values() for n, v in e.functions.items()}
 PARAMS = {n: v for e in EXTENSIONS.values() for n, v in e.params.items()}
 CONSTANTS = {n: v for e in EXTENSIONS.values() for n, v in e.constants.items()}
+PIXEL_SIGNATURES = {n: v for e in PIXEL_EXTENSIONS.values() for n, v in e.functions.items()}
+PIXEL_PARAMS = {n: v for e in PIXEL_EXTENSIONS.values() for n, v in e.params.items()}
+PIXEL_CONSTANTS = {n: v for e in PIXEL_EXTENSIONS.values() for n, v in e.constants.items()}
 
 _bound = None
 
@@ -49,7 +63,7 @@ def load():
     lib = _lib.load()
     if _bound is not lib:
         rebuild = 'rebuild with `python -m hd_yolo_amd.build --force`'
-        for ext in EXTENSIONS.values():
+        for ext in (*EXTENSIONS.values(), *PIXEL_EXTENSIONS.values()):
             header = os.path.basename(ext.header)
             for name, (res, args) in ext.functions.items():
                 fn = getattr(lib, name, None)

@@ -17,6 +17,9 @@ from collections import namedtuple
 
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'hdyolo.h')
 EXTENSION_NAMES = ('measure', 'spatial', 'outline', 'graph', 'texture')      # the extension headers, oldest first: _ext.py binds them, build.py watches them
+# The extension headers of the passes over a slide's pixels.  A second tuple only because the tests of the five headers above pin that tuple and
+# the sizes of its tables: _ext.py binds both alike (PIXEL_EXTENSIONS beside EXTENSIONS), and the two can be merged once those tests may change.
+PIXEL_EXTENSION_NAMES = ('stain',)
 SCALARS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'long long': ctypes.c_longlong, 'unsigned long long': ctypes.c_ulonglong,
            'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double}
 POINTEES = set(SCALARS) | {'void', 'char', 'unsigned char', 'unsigned short', 'uint16_t'}       # what a pointer may point at, beside a structure

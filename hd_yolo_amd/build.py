@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(CSRC, 'build')
 LIB = os.path.join(OUT, 'libhdyolo_hip.so')
-SOURCES = ['api.hip', 'conv_dispatch.hip', 'conv_igemm.hip', 'conv3x3.hip', 'conv3x3_c128.hip', 'conv3x3s2.hip', 'conv_deep.hip', 'conv_stem.hip', 'conv_wgrad.hip', 'conv_wgrad3x3.hip', 'conv_wgrad_deep.hip', 'conv_dgrad_s2.hip', 'conv1x1_bwd.hip', 'bn_act.hip', 'pool.hip', 'detect.hip', 'nms_grid.hip', 'slide.hip', 'augment.hip', 'augment_masks.hip', 'score.hip', 'paste.hip', 'mask_score.hip', 'measure.hip', 'spatial.hip', 'outline.hip', 'graph.hip', 'texture.hip', 'loss.hip', 'roi.hip', 'seg.hip', 'optim.hip', 'exec.hip']
+SOURCES = ['api.hip', 'conv_dispatch.hip', 'conv_igemm.hip', 'conv3x3.hip', 'conv3x3_c128.hip', 'conv3x3s2.hip', 'conv_deep.hip', 'conv_stem.hip', 'conv_wgrad.hip', 'conv_wgrad3x3.hip', 'conv_wgrad_deep.hip', 'conv_dgrad_s2.hip', 'conv1x1_bwd.hip', 'bn_act.hip', 'pool.hip', 'detect.hip', 'nms_grid.hip', 'slide.hip', 'augment.hip', 'augment_masks.hip', 'score.hip', 'paste.hip', 'mask_score.hip', 'measure.hip', 'spatial.hip', 'outline.hip', 'graph.hip', 'texture.hip', 'stain.hip', 'loss.hip', 'roi.hip', 'seg.hip', 'optim.hip', 'exec.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
          '-I' + CSRC, '-I' + os.path.join(os.path.dirname(HERE), 'include')]
 
@@ -25,7 +25,7 @@ def _newer(a, bs):
 def build(force=False, verbose=True):
     os.makedirs(OUT, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith('.h')] + [_header.HEADER_PATH]
-    headers += [_header.extension_header(n) for n in _header.EXTENSION_NAMES]
+    headers += [_header.extension_header(n) for n in _header.EXTENSION_NAMES + _header.PIXEL_EXTENSION_NAMES]
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 
     def compile_one(src):

@@ -795,6 +795,112 @@ def slide_tissue(slide, origins, th, tw, background=220):
     return counts
 
 
+# ------------------------------------------------------------------------------------------ stain counts and recolouring (csrc/stain.hip)
+STAIN_MAX_BINS, STAIN_MAX_TONE = _ext.PIXEL_CONSTANTS['HDY_STAIN_MAX_BINS'], _ext.PIXEL_CONSTANTS['HDY_STAIN_MAX_TONE']
+STAIN_ANGLE_ENTRY_BOUND = 2466 << _ext.PIXEL_CONSTANTS['HDY_STAIN_OD_SHIFT']      # |entry| of stain_angles' table: q(0) projected on a unit vector
+
+
+def _stain_window(who, slide, window):
+    """(the slide's arguments, the window's) of a stain pass: window = (x0, y0, w, h), None = the whole slide"""
+    sp, pitch, pb, H, W = slide_u8(slide)
+    x0, y0, w, h = (0, 0, W, H) if window is None else (int(v) for v in window)
+    if x0 < 0 or y0 < 0 or w < 1 or h < 1 or x0 + w > W or y0 + h > H:
+        raise _lib.HdyError(f'{who}: the window ({x0}, {y0}) + {w} x {h} leaves the slide of {W} x {H} pixels')
+    return (sp, pitch, pb, H, W), (x0, y0, w, h)
+
+
+def _stain_table(who, t, name, shape, dev, dtype=torch.int32):
+    require_gpu(t)
+    if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+        raise _lib.HdyError(f'{who}: {name} must be a {dtype} {shape} tensor on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}')
+    return t.contiguous()
+
+
+def _stain_outputs(who, out, shapes, dev):
+    """the int64 outputs of a counting pass: new tensors, or the caller's (`out`, one tensor or a tuple), which the pass overwrites whole"""
+    if out is None:
+        return tuple(torch.empty(s, dtype=torch.int64, device=dev) for s in shapes)
+    out = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+    if len(out) != len(shapes) or any(t.dtype != torch.int64 or tuple(t.shape) != s or t.device != dev or not t.is_contiguous()
+                                      for t, s in zip(out, shapes)):
+        raise _lib.HdyError(f'{who}: out must be contiguous int64 of shape {" and ".join(str(s) for s in shapes)} on {dev}')
+    return out
+
+
+def _stain_count(who, name, slide, window, step, background, table, cells, outs):
+    """one counting pass: `table` then the (tensor, ...) outputs with their sizes, then a workspace of HDY_STAIN_MAX_BLOCKS slabs of `cells`"""
+    sl, win = _stain_window(who, slide, window)
+    if int(step) < 1:
+        raise _lib.HdyError(f'{who}: step={step} must be at least 1')
+    ws = _workspace(_ext.PIXEL_CONSTANTS['HDY_STAIN_MAX_BLOCKS'] * cells * 8, slide.device)
+    args = [v for o in outs for v in (o.data_ptr(), o.numel())]
+    _ext.call(name, *sl, *win, int(step), int(background), *table, *args, ws.data_ptr(), _nbytes(ws), stream_ptr())
+
+
+def stain_moments(slide, od, window=None, step=1, background=220, out=None):
+    """int64 (10,) device tensor: n, the sums of the optical densities qR, qG, qB = od[value] and of their six products over the tissue
+    pixels (min(R, G, B) < background) of the window's every `step`-th pixel (hdy_stain_moments_u8, include/hdyolo_stain.h).  od: int32
+    (256,), hd_yolo_amd.stain.od_table().  Integer sums: the same input gives the same bits.  out (here and in stain_angles / stain_levels): the
+    caller's output tensors instead of new ones; every element is written."""
+    who = 'stain_moments'
+    od = _stain_table(who, od, 'od', (256,), slide.device)
+    sums, = _stain_outputs(who, out, [(10,)], slide.device)
+    _stain_count(who, 'hdy_stain_moments_u8', slide, window, step, background, (od.data_ptr(), 256), 10, (sums,))
+    return sums
+
+
+def stain_angles(slide, lut, A, window=None, step=1, background=220, out=None):
+    """(hist int64 (A,), skipped int64 (1,)): per tissue pixel p_k = (lut[k][0][R] + lut[k][1][G] + lut[k][2][B]) >> 4, k = 0, 1; p_0 <= 0 is
+    skipped, otherwise bin floor(A (s + p_1) / (2 s)), s = p_0 + |p_1|, monotone in atan2(p_1, p_0) (hdy_stain_angles_u8).  lut: int32
+    (2, 3, 256), hd_yolo_amd.stain.plane_lut.  The table's bound (|entry| <= 2^10 * 2466, under which the pass's 32-bit product is exact) is
+    checked here: one value is read back."""
+    who = 'stain_angles'
+    A = int(A)
+    if not 1 <= A <= STAIN_MAX_BINS:
+        raise _lib.HdyError(f'{who}: A={A} outside [1, {STAIN_MAX_BINS}]')
+    lut = _stain_table(who, lut, 'lut', (2, 3, 256), slide.device)
+    top = int(lut.abs().max())
+    if top > STAIN_ANGLE_ENTRY_BOUND:
+        raise _lib.HdyError(f'{who}: a table entry of magnitude {top} passes 2^10 * 2466 = {STAIN_ANGLE_ENTRY_BOUND}: A (s + p_1) could pass 2^32')
+    hist, skipped = _stain_outputs(who, out, [(A,), (1,)], slide.device)
+    _stain_count(who, 'hdy_stain_angles_u8', slide, window, step, background, (lut.data_ptr(), lut.numel(), A), A + 1, (hist, skipped))
+    return hist, skipped
+
+
+def stain_levels(slide, lut, B, window=None, step=1, background=220, out=None):
+    """int64 (2, B): per stain s the histogram of level_s = clamp((lut[s][0][R] + lut[s][1][G] + lut[s][2][B]) >> 16, 0, B - 1) over the tissue
+    pixels: the level rule of label_texture over the whole window (hdy_stain_levels_u8).  lut: int32 (2, 3, 256), hd_yolo_amd.stain.level_lut."""
+    who = 'stain_levels'
+    B = int(B)
+    if not 1 <= B <= STAIN_MAX_BINS:
+        raise _lib.HdyError(f'{who}: B={B} outside [1, {STAIN_MAX_BINS}]')
+    lut = _stain_table(who, lut, 'lut', (2, 3, 256), slide.device)
+    hist, = _stain_outputs(who, out, [(2, B)], slide.device)
+    _stain_count(who, 'hdy_stain_levels_u8', slide, window, step, background, (lut.data_ptr(), lut.numel(), B), 2 * B, (hist,))
+    return hist
+
+
+def stain_apply(slide, lut, tone, out=None, window=None):
+    """The slide recoloured: out_c = tone[clamp((lut[c][0][R] + lut[c][1][G] + lut[c][2][B]) >> 16, 0, T - 1)] for every pixel of the window,
+    background included (hdy_stain_apply_u8).  lut int32 (3, 3, 256) and tone uint8 (T,): hd_yolo_amd.stain.normalizer.  out: None (a new
+    slide of the same shape; outside a window it is a copy of the input), the slide itself (in place) or another 8-bit slide of the same
+    H x W with 3 or 4 bytes per pixel (a fourth byte is the input's, or 255)."""
+    who = 'stain_apply'
+    sl, win = _stain_window(who, slide, window)
+    lut = _stain_table(who, lut, 'lut', (3, 3, 256), slide.device)
+    T = int(tone.numel())
+    if not 1 <= T <= STAIN_MAX_TONE:
+        raise _lib.HdyError(f'{who}: a tone table of {T} entries (1 .. {STAIN_MAX_TONE})')
+    tone = _stain_table(who, tone, 'tone', (T,), slide.device, torch.uint8)
+    if out is None:
+        out = torch.empty_like(slide, memory_format=torch.contiguous_format) if window is None else slide.clone(memory_format=torch.contiguous_format)
+    dp, dpitch, dpb, dH, dW = slide_u8(out)
+    if (dH, dW) != sl[3:] or out.device != slide.device:
+        raise _lib.HdyError(f'{who}: out is {dW} x {dH} pixels on {out.device}, the slide {sl[4]} x {sl[3]} on {slide.device}')
+    _ext.call('hdy_stain_apply_u8', *sl, *win, dp, dpitch, dpb, lut.data_ptr(), lut.numel(), tone.data_ptr(), T, T, stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------------------ training augmentation from an 8-bit tile bank
 AUG_CELL_BYTES = _lib.CONSTANTS['HDY_AUG_CELL_BYTES']
 

@@ -411,3 +411,27 @@ def synth_tile_bank(n, size, nc, seed=0, nmin=20, nmax=60, instances=False):
         labels.append(lab.astype(np.int64))
         offsets.append(offsets[-1] + m)
     return TileBank(tiles, np.concatenate(boxes), np.concatenate(labels), np.asarray(offsets, np.int64), inst)
+
+
+def synth_stained_slide(side, matrix, max_conc, tissue=0.6, seed=0):
+    """A seeded uint8 (side, side, 3) numpy image of two known stains, because no real slide ships with the project: the upper `tissue`
+    fraction of the rows is an eosin ground (gamma-distributed concentration; half of its pixels carry no haematoxylin, the others a
+    little) with round blobs of high haematoxylin (half of their pixels without eosin), the rest white background.  matrix: rows 0 and 1
+    are the unit optical-density vectors of haematoxylin and eosin; max_conc: the 99th percentile of either concentration over the tissue
+    pixels (the draws are scaled to it exactly).  v = clamp(round(256 * 10^-od) - 1, 0, 255) per channel, od = cH M[0] + cE M[1]."""
+    import numpy as np
+    rng = np.random.default_rng(9100 + seed)
+    m = np.asarray(matrix, dtype=np.float64)[:2]
+    rows = max(1, min(side, int(round(tissue * side))))
+    conc = np.zeros((side, side, 2))
+    blob = np.zeros((rows, side), bool)
+    for _ in range(max(1, rows * side // 900)):
+        cy, cx, rad = rng.uniform(0, rows), rng.uniform(0, side), rng.uniform(4, 9)
+        ys, xs = np.arange(max(int(cy - rad), 0), min(int(cy + rad) + 2, rows)), np.arange(max(int(cx - rad), 0), min(int(cx + rad) + 2, side))
+        blob[ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1] |= (ys[:, None] - cy) ** 2 + (xs[None, :] - cx) ** 2 <= rad * rad
+    h = np.where(blob, rng.gamma(6.0, 1.0, (rows, side)), np.where(rng.random((rows, side)) < 0.5, 0.0, rng.gamma(1.5, 0.15, (rows, side))))
+    e = np.where(blob, np.where(rng.random((rows, side)) < 0.5, 0.0, rng.gamma(1.5, 0.3, (rows, side))), rng.gamma(6.0, 1.0, (rows, side)))
+    for s, c in enumerate((h, e)):
+        conc[:rows, :, s] = c * (float(max_conc[s]) / np.percentile(c, 99))
+    od = conc @ m
+    return np.clip(np.rint(256 * 10.0 ** -od) - 1, 0, 255).astype(np.uint8)

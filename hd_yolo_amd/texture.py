@@ -205,12 +205,13 @@ def columns(hist, glcm, flags):
     return table
 
 
-def texture_table(label_map, R, extent, image, window=(0, 0), stain='hematoxylin', levels=16, offsets=OFFSETS, chunk=16384):
+def texture_table(label_map, R, extent, image, window=(0, 0), stain='hematoxylin', levels=16, offsets=OFFSETS, chunk=16384, matrix=None):
     """dict of float64 (R,) columns of the R labels of an int32 (h, w) label map on the GPU: the INTENSITY columns as 'tex_level_mean', ...,
     for each of the 13 FEATURES its mean and its range (largest minus smallest) over the D directions as 'tex_<feature>_mean' and
     'tex_<feature>_range', and 'tex_flags' (0 measured, 1 the label owns nothing, 2 a box side above 1024).  Directions without pairs are left
     out of the mean and the range; a label none of whose directions has a pair (a single pixel, a flagged label) has NaN there.
-    extent, image, window, levels, offsets: as ops.label_texture takes them; stain: as stain_lut.  The labels are worked through in chunks
+    extent, image, window, levels, offsets: as ops.label_texture takes them; stain, matrix: as stain_lut (matrix None: the Ruifrok-Johnston
+    vectors; a slide's own, stain.estimate_stains(slide).matrix, measures its stains).  The labels are worked through in chunks
     of `chunk` (ops.label_texture(rows=...)), so that at most chunk * D * levels^2 * 4 bytes of matrices exist at once (64 MB at the defaults).
     Nothing is read back."""
     from . import ops
@@ -218,7 +219,7 @@ def texture_table(label_map, R, extent, image, window=(0, 0), stain='hematoxylin
     if chunk < 1:
         raise ValueError(f'texture_table: chunk={chunk} must be positive')
     dev = label_map.device
-    lut = stain_lut(stain, levels, device=dev)
+    lut = stain_lut(stain, levels, matrix=matrix, device=dev)
     names = [f'tex_{k}' for k in INTENSITY] + [f'tex_{n}_{s}' for n in FEATURES for s in ('mean', 'range')] + ['tex_flags']
     table = {k: torch.empty((R,), dtype=torch.float64, device=dev) for k in names}
     if R == 0:
